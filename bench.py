@@ -15,8 +15,10 @@ these scenes the frame is within ~1e-6 of the exact one, tests/test_gpu_parity.p
 Device stages per frame: march_kernel (scatter records) -> record cut-offs ->
 secondary_ww_kernel (light + environment transmittance, the dominant kernel) -> accumulate_kernel.
 
-Prints ONE JSON line on rank 0 (contract in the task statement); roofline and cpu_baseline
-objects are documented in DESIGN.md.
+Prints ONE JSON line on rank 0. A plain run sets up, warms up,
+times the steps and prints that line; --full adds the measurements that take runs of their own (the
+instrumented work count behind `roofline`, `cpu_baseline`, `render_call`; documented in DESIGN.md).
+--dump-outputs DIR saves what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -155,6 +157,27 @@ def host_cores():
         pass
     return use, {"nproc": os.cpu_count(), "affinity": avail, "omp_num_threads": omp, "cpu_model": model,
                  "cgroup_cpu_quota": cgroup_cpu_quota()}
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: per array, under the 64 MB the whole dump may take
+DUMP_SAMPLE_SEED = 20250101
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array of `arrays` (name -> ndarray) as out_dir/<name>.npy, f32 or f64. An array
+    over DUMP_BUDGET_BYTES is cut to a fixed, seeded sample of its rows along the flattened leading axes
+    (a frame: pixels, in ascending row-major order), the same rows for every run of the same shape."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if a is None:
+            continue
+        a = np.ascontiguousarray(a, dtype=np.float64 if np.asarray(a).dtype == np.float64 else np.float32)
+        if a.nbytes > DUMP_BUDGET_BYTES:
+            rows = a.reshape(-1, a.shape[-1])
+            keep = DUMP_BUDGET_BYTES // (rows.shape[1] * a.itemsize)
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows.shape[0], size=keep, replace=False))
+            a = rows[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def build_scene(cfg, seed):
@@ -297,6 +320,9 @@ def bench_sfd(args, scene, camera, W, H, t_setup):
         opt = one_iter()
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) / args.steps * 1e3
+    if args.dump_outputs:
+        # (not last_grads: measured, they differ between two runs of the same command; params and losses do not)
+        dump_outputs(args.dump_outputs, {"params": opt.params, "loss_history": np.asarray(opt.history, np.float64)})
     paths = 5 * W * H * args.spp
     # Roofline of the iteration: its five forward renders (base + num_stoch_samples perturbed) are the
     # multi-scatter path and shadow-ray kernels; the instrumented build of those kernels counts one render of the
@@ -396,10 +422,12 @@ def main():
     ap.add_argument("--t-eps", type=float, default=1e-6,
                     help="stop a ray once T <= t_eps (SURVEY §8(d) benchmark setting; error bound in DESIGN.md)")
     ap.add_argument("--seed", type=int, default=2025)
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU-baseline work (0 = skip)")
+    ap.add_argument("--cpu-budget", type=float, default=20.0,
+                    help="with --full: seconds of CPU-baseline work (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU-baseline threads (0 = every core this process may use, see host_cores)")
-    ap.add_argument("--flops", type=int, default=1, help="run one instrumented frame to count algorithmic work")
+    ap.add_argument("--flops", type=int, default=1,
+                    help="with --full: run one instrumented frame to count algorithmic work (0 = skip)")
     ap.add_argument("--integrator", default="raymarch", choices=["raymarch", "freeflight", "multiscatter", "sfd"],
                     help="raymarch = RayMarchingGaussians (the headline); the free-flight integrators are "
                          "secondary lines (unit Mpaths/s = pixel samples per second)")
@@ -409,7 +437,17 @@ def main():
                     help="rank 0 saves the last timed frame (H x W x 3 f32 .npy; ray-march): multi-GPU equality tests")
     ap.add_argument("--opt", action="append", default=[],
                     help="name=value device option (vr_set_option, e.g. ff_kernel=2) for A/B runs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the instrumented work count behind the "
+                         "roofline (--flops), the CPU baseline (--cpu-budget) and the render-call wall times")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 saves what the last timed step computed as DIR/<name>.npy (f32 / f64; an array over "
+                         "48 MB as a fixed, seeded sample of its rows)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run times its steps and nothing else
+        args.cpu_budget, args.flops = 0.0, 0
     if args.config == "main":  # tests/main.cpp renders MultiScatterGaussians
         if args.integrator == "raymarch":
             args.integrator = "multiscatter"
@@ -509,6 +547,8 @@ def main():
     stage_ms = {k: float(np.mean([st["stage_ms"][k] for st in per_step])) for k in vr.Device.STAGES}
     if args.dump_frame and rank == 0 and not ff:
         np.save(args.dump_frame, frame.cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"frame": frame.cpu().numpy()})
     t = torch.tensor([elapsed, kernel_ms], dtype=torch.float64, device="cuda")
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -530,7 +570,7 @@ def main():
                 cpu["all_cores"] = all_core_baseline(
                     lambda n: cpu_baseline_ff(scene, W, H, multi, args.spp, args.cpu_budget / 2, n, log), host,
                     args.cpu_threads, log)
-            call = render_call_times(dev, integ, scene, W, H) if world == 1 else None
+            call = render_call_times(dev, integ, scene, W, H) if world == 1 and args.full else None
             print(json.dumps({
                 "metric": f"Mpaths/s, {args.integrator} render", "value": paths / (ms_per_step * 1e-3) / 1e6,
                 "unit": "Mpaths/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -623,7 +663,7 @@ def main():
             cpu["all_cores"] = all_core_baseline(
                 lambda n: cpu_baseline(scene, W, H, args.env_samples, args.cpu_budget / 2, n, log), host,
                 args.cpu_threads, log)
-        call = render_call_times(dev, integ, scene, W, H) if world == 1 else None
+        call = render_call_times(dev, integ, scene, W, H) if world == 1 and args.full else None
         out = {
             "metric": "Mrays/s + achieved HBM GB/s, 4096² render of 1M Gaussians, 1/2/4/8 GPU",
             "value": value, "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,

@@ -43,6 +43,27 @@ def test_primary_depths_stop_at_t_eps():
     assert np.all(d2[~miss] <= d6[~miss]) and np.all(d6[~miss] <= d0[~miss])
 
 
+def test_dump_outputs_writes_whole_small_arrays_and_a_fixed_sample_of_large_ones(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): an array within the budget is saved whole, as f32 (f64 stays
+    f64); a larger one as a seeded sample of its rows in ascending order that fits the budget and is the
+    same rows for every call, so that two builds can be compared output for output."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1200)
+    small = np.arange(7 * 5 * 3, dtype=np.float64).reshape(7, 5, 3)
+    frame = np.arange(13 * 11 * 3, dtype=np.float32).reshape(13, 11, 3)  # 1716 B > 1200 B: 100 of 143 pixels
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "ints": np.arange(4), "frame": frame})
+    a = np.load(tmp_path / "a" / "frame.npy")
+    assert a.dtype == np.float32 and a.shape == (100, 3) and a.nbytes <= 1200
+    rows = frame.reshape(-1, 3)
+    idx = (a[:, 0] / 3).astype(int)
+    assert np.array_equal(a, rows[idx]) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(a, np.load(tmp_path / "b" / "frame.npy"))
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, small)
+    assert np.load(tmp_path / "a" / "ints.npy").dtype == np.float32
+
+
 def test_free_flight_roofline_from_work_counts():
     """bench.ff_roofline: the path kernel's executed flops are its counted node steps, ray-Gaussian
     tests and erf evaluations times FF_FLOP_WEIGHTS over its HIP-event time; the shadow-ray kernel is

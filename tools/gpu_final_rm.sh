@@ -8,7 +8,7 @@ bash tools/pmc_c4.sh || exit 1
 python3 tools/pmc_summary.py profiles/r04_c4_pmc_summary.json gpurun_out/pmc_c4/p1 gpurun_out/pmc_c4/p2 gpurun_out/pmc_c4/p3 gpurun_out/pmc_c4/p4 > /dev/null || exit 1
 run() {  # name, args...
   local n=$1; shift
-  timeout -k 10 300 python3 bench.py "$@" > $O/$n.json 2> $O/$n.log || { echo "$n failed"; tail -5 $O/$n.log; exit 1; }
+  timeout -k 10 300 python3 bench.py --full "$@" > $O/$n.json 2> $O/$n.log || { echo "$n failed"; tail -5 $O/$n.log; exit 1; }
   python3 -c "import json;d=json.load(open('$O/$n.json'));r=d.get('roofline') or {};print('$n', round(d['value'],3), d['unit'], round(d['ms_per_step'],2), 'ms', 'frac', r.get('frac'), 'alg_s8d', r.get('alg_frac_s8d'), 'traffic', r.get('traffic'))"
 }
 stats() {  # name, args...

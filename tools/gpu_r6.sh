@@ -10,7 +10,7 @@ rc=$?
 grep -E "passed|failed" $OUT/gpu_tests.log | tail -2
 grep -E "^FAILED|^ERROR" $OUT/gpu_tests.log | head -20
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || { echo "pytest exit $rc"; tail -20 $OUT/gpu_tests.log; exit 1; }
-timeout -k 10 400 python3 bench.py --cpu-budget 0 > $OUT/c4.json 2> $OUT/c4.log || { tail -5 $OUT/c4.log; exit 1; }
+timeout -k 10 400 python3 bench.py --full --cpu-budget 0 > $OUT/c4.json 2> $OUT/c4.log || { tail -5 $OUT/c4.log; exit 1; }
 python3 -c "import json;d=json.load(open('$OUT/c4.json'));r=d['roofline'];print(round(d['value'],2), d['unit'], round(d['ms_per_step'],2), 'frac', round(r['frac'],4), 'alg_s8d', round(r['alg_frac_s8d'],4), r['stage_ms'])"
 timeout -k 10 300 python3 tools/diag_c4.py --frames 2 --counts 0 > $OUT/diag.json 2> $OUT/diag.log || { tail -5 $OUT/diag.log; exit 1; }
 cat $OUT/diag.json
