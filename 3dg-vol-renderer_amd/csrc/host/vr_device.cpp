@@ -35,6 +35,19 @@ hipError_t gauss_refit_secondary(const HNode4* src, HNode4* dst, HNode4* dst_t, 
 hipError_t gauss_bin_scan(const uint32_t* cnt, uint32_t* off, uint32_t n, void* tmp, size_t& tmp_bytes, hipStream_t stream);
 hipError_t launch_pixel_losses(const float* img, const float* ref, uint32_t npix, float* out, hipStream_t stream);
 
+// kernels/vr_query.hip
+hipError_t query_transmittance(const RenderArgs& A, const vr_ray* rays, uint32_t n, float* tr, float* tau, uint32_t* next,
+                               int refill, int cus, hipStream_t s);
+hipError_t query_sigma(const RenderArgs& A, const float* xyz, uint32_t n, float* out, uint32_t* n_active, hipStream_t s);
+hipError_t query_events_count(const RenderArgs& A, const vr_ray* rays, uint32_t n, uint32_t* counts, uint32_t* offsets,
+                              unsigned long long* total, uint32_t* next, int refill, int cus, void* tmp, size_t& tmp_bytes,
+                              hipStream_t s);
+hipError_t query_events_fill(const RenderArgs& A, const vr_ray* rays, uint32_t n, const uint32_t* offsets, uint32_t total,
+                             unsigned long long* keys, unsigned long long* keys2, float* t, uint32_t* ev, uint32_t* next,
+                             int refill, int cus, void* tmp, size_t& tmp_bytes, hipStream_t s);
+hipError_t query_pack_rays(const float* o, const float* d, const float* tmax, uint32_t tmax_stride, uint32_t n, vr_ray* rays,
+                           hipStream_t s);
+
 hipError_t launch_unshuffle(const float* slabs, uint32_t nslabs, uint32_t tiles_per_slab, uint32_t tiles_x, uint32_t W,
                             uint32_t H, float* img, hipStream_t stream);
 hipError_t launch_unshuffle_part(const float* slabs, uint32_t first, uint32_t nslabs, uint32_t stride, uint32_t tiles_per_slab,
@@ -125,6 +138,14 @@ struct vr_ctx {
     uint32_t rec_npix[2] = {0, 0}, rec_n[2] = {0, 0};
     Buf sfd_tmp;                      // vr_sfd_loss_diff: losses + output
     Buf sfd_ref, sfd_loss[2], sfd_out;  // device inverse loop (vr_sfd_optimize): I_ref, base / perturbed losses
+    // mixture queries (vr_query_*, kernels/vr_query.hip): their own workspaces, grown on demand; nothing of a
+    // frame (report, statistics, hints) is touched by a query
+    Buf q_in, q_out, q_out2;          // host forms: the batch on the device and its results
+    Buf q_off, q_cnt, q_keys, q_keys2, q_tmp;  // events: offsets (host form), counts, sort keys (in / out), scan + sort scratch
+    Buf q_ctl;                        // [0..2] ray counters of the three persistent walks, [4..5] the 64-bit event total
+    bool q_count_valid = false;       // the last vr_query_events_count_device of this scene: its n and total
+    uint64_t q_count_n = 0, q_count_total = 0;
+    int q_cus = 0;                    // compute units of the device (grid of the persistent walks)
     int pcg_jump_n = -1;
     uint32_t* h_sizing = nullptr;  // pinned copy of rec_alloc for the sizing march of a context's first frame
     uint64_t rec_hint = 0, ovf_hint = 0;  // record / overflow-pool capacities (0: not known yet)
@@ -1113,7 +1134,8 @@ void vr_destroy(vr_ctx* c) {
                            &c->rec_alloc, &c->rec_bloom, &c->slowq, &c->fixq, &c->pcg_jump, &c->ray_next,
                            &c->stack_ovf, &c->env_order, &c->env_base, &c->rec_cut, &c->rec_start, &c->deep, &c->bin_cnt, &c->bin_off, &c->bin_ent,
                            &c->ff_scratch, &c->ff_tail, &c->ff_sum, &c->ff_nee, &c->ff_fb, &c->rec_bits[0], &c->rec_bits[1],
-                           &c->sfd_tmp, &c->sfd_ref, &c->sfd_loss[0], &c->sfd_loss[1], &c->sfd_out})
+                           &c->sfd_tmp, &c->sfd_ref, &c->sfd_loss[0], &c->sfd_loss[1], &c->sfd_out, &c->q_in, &c->q_out,
+                           &c->q_out2, &c->q_off, &c->q_cnt, &c->q_keys, &c->q_keys2, &c->q_tmp, &c->q_ctl})
         if (b->p) (void)hipFree(b->p);
     if (c->d_frame) (void)hipFree(c->d_frame);
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
@@ -1197,6 +1219,7 @@ vr_status vr_upload_scene(vr_ctx* c, const vr_scene* sc) {
     HIP_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
     if (vr_status cs = collect(c); cs != VR_OK) return cs;  // the previous scene's last report, before the reset
     free_scene(c);
+    c->q_count_valid = false;
     c->march_big = false;
     c->nee_inline = false;  // (nee_hint is kept: the inverse loop re-uploads every iteration and renders alike)
     c->type = s.type;
@@ -1752,6 +1775,215 @@ vr_status vr_get_stats(vr_ctx* c, vr_render_stats* o) {
     o->deep_pixels = c->report_gauss ? (int64_t)std::min(c->h_report[5], kDeepQueue) : 0;
     o->slow_rays = c->report_gauss ? (int64_t)c->h_report[8] : 0;
     o->band_rays = c->report_gauss ? (int64_t)c->h_report[9] : 0;
+    return VR_OK;
+}
+
+}  // extern "C"
+
+// ---------------- mixture queries (kernels/vr_query.hip) ----------------
+namespace {
+
+// The scene part of the kernel arguments, after the checks every query shares. `n` entries of a batch.
+vr_status query_begin(vr_ctx* c, const char* what, size_t n, RenderArgs& A) {
+    if (!c) return fail(VR_ERR_INVALID, std::string(what) + ": NULL ctx");
+    if (!c->has_scene) return fail(VR_ERR_NOSCENE, "no scene uploaded (call vr_upload_scene first)");
+    if (c->type != VR_VOLUME_GAUSSIANS) return fail(VR_ERR_UNSUPPORTED, std::string(what) + ": mixture queries need a Gaussian scene");
+    if (n >= (1ull << 31)) return fail(VR_ERR_INVALID, std::string(what) + ": more than 2^31 - 1 entries in one call");
+    HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+    if (c->q_cus == 0) HIP_TRY(hipDeviceGetAttribute(&c->q_cus, hipDeviceAttributeMultiprocessorCount, c->device), "hipDeviceGetAttribute");
+    std::memset(&A, 0, sizeof(A));
+    A.gauss = c->d_gauss;
+    A.nodes = c->d_nodes;
+    A.hnodes = c->d_hnodes;
+    // the 4-wide walks read the per-axis copy, which exists whenever the 4-wide tree does (upload_parents)
+    A.hnodes4 = c->d_hnodes4w ? c->d_hnodes4 : nullptr;
+    A.hnodes4w = c->d_hnodes4w;
+    A.num_nodes4 = (uint32_t)c->num_nodes4;
+    for (int k = 0; k < 3; ++k) A.hn_center[k] = c->hn_center[k];
+    A.hn_scale = c->hn_scale;
+    A.num_prims = c->num_prims;
+    A.bvh_depth = c->bvh_depth;
+    A.gauss_order = c->d_order;
+    return grow(c->q_ctl, 32, "hipMalloc(query counters)");
+}
+int query_refill(const vr_ctx* c) { return std::clamp<int>(c->auto_nee_refill, 1, 64); }
+bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+vr_status vr_query_transmittance_device(vr_ctx* c, const vr_ray* d_rays, size_t n, float* d_tr, float* d_tau, void* stream) {
+    c = first_device(c);
+    RenderArgs A;
+    if (vr_status st = query_begin(c, "vr_query_transmittance", n, A); st != VR_OK) return st;
+    if (n == 0) return VR_OK;
+    if (!d_rays || !d_tr) return fail(VR_ERR_INVALID, "vr_query_transmittance: NULL argument");
+    if (!aligned16(d_rays)) return fail(VR_ERR_INVALID, "vr_query_transmittance: the device ray array must be 16-byte aligned");
+    HIP_TRY(query_transmittance(A, d_rays, (uint32_t)n, d_tr, d_tau, (uint32_t*)c->q_ctl.p, query_refill(c), c->q_cus,
+                                (hipStream_t)stream),
+            "query_transmittance_kernel");
+    return VR_OK;
+}
+
+vr_status vr_query_transmittance(vr_ctx* c, const vr_ray* rays, size_t n, float* tr, float* tau) {
+    c = first_device(c);
+    RenderArgs A;
+    vr_status st = query_begin(c, "vr_query_transmittance", n, A);
+    if (st != VR_OK || n == 0) return st;
+    if (!rays || !tr) return fail(VR_ERR_INVALID, "vr_query_transmittance: NULL argument");
+    if ((st = grow(c->q_in, n * sizeof(vr_ray), "hipMalloc(query rays)")) != VR_OK) return st;
+    if ((st = grow(c->q_out, n * sizeof(float), "hipMalloc(query results)")) != VR_OK) return st;
+    if (tau && (st = grow(c->q_out2, n * sizeof(float), "hipMalloc(query results)")) != VR_OK) return st;
+    HIP_TRY(hipMemcpy(c->q_in.p, rays, n * sizeof(vr_ray), hipMemcpyHostToDevice), "hipMemcpy(query rays)");
+    st = vr_query_transmittance_device(c, (const vr_ray*)c->q_in.p, n, (float*)c->q_out.p, tau ? (float*)c->q_out2.p : nullptr,
+                                       c->stream);
+    if (st != VR_OK) return st;
+    HIP_TRY(hipStreamSynchronize(c->stream), "query_transmittance_kernel");
+    HIP_TRY(hipMemcpy(tr, c->q_out.p, n * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    if (tau) HIP_TRY(hipMemcpy(tau, c->q_out2.p, n * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    return VR_OK;
+}
+
+vr_status vr_query_sigma_device(vr_ctx* c, const float* d_xyz, size_t n, float* d_sigma_as, uint32_t* d_n_active, void* stream) {
+    c = first_device(c);
+    RenderArgs A;
+    if (vr_status st = query_begin(c, "vr_query_sigma", n, A); st != VR_OK) return st;
+    if (n == 0) return VR_OK;
+    if (!d_xyz || !d_sigma_as) return fail(VR_ERR_INVALID, "vr_query_sigma: NULL argument");
+    HIP_TRY(query_sigma(A, d_xyz, (uint32_t)n, d_sigma_as, d_n_active, (hipStream_t)stream), "query_sigma_kernel");
+    return VR_OK;
+}
+
+vr_status vr_query_sigma(vr_ctx* c, const float* xyz, size_t n, float* sigma_as, uint32_t* n_active) {
+    c = first_device(c);
+    RenderArgs A;
+    vr_status st = query_begin(c, "vr_query_sigma", n, A);
+    if (st != VR_OK || n == 0) return st;
+    if (!xyz || !sigma_as) return fail(VR_ERR_INVALID, "vr_query_sigma: NULL argument");
+    if ((st = grow(c->q_in, n * 3 * sizeof(float), "hipMalloc(query points)")) != VR_OK) return st;
+    if ((st = grow(c->q_out, n * 2 * sizeof(float), "hipMalloc(query results)")) != VR_OK) return st;
+    if (n_active && (st = grow(c->q_out2, n * sizeof(uint32_t), "hipMalloc(query results)")) != VR_OK) return st;
+    HIP_TRY(hipMemcpy(c->q_in.p, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(query points)");
+    st = vr_query_sigma_device(c, (const float*)c->q_in.p, n, (float*)c->q_out.p, n_active ? (uint32_t*)c->q_out2.p : nullptr,
+                               c->stream);
+    if (st != VR_OK) return st;
+    HIP_TRY(hipStreamSynchronize(c->stream), "query_sigma_kernel");
+    HIP_TRY(hipMemcpy(sigma_as, c->q_out.p, n * 2 * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    if (n_active) HIP_TRY(hipMemcpy(n_active, c->q_out2.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    return VR_OK;
+}
+
+vr_status vr_query_events_count_device(vr_ctx* c, const vr_ray* d_rays, size_t n, uint32_t* d_offsets, uint64_t* total) {
+    c = first_device(c);
+    RenderArgs A;
+    if (vr_status st = query_begin(c, "vr_query_events", n, A); st != VR_OK) return st;
+    if (!total) return fail(VR_ERR_INVALID, "vr_query_events: NULL total");
+    *total = 0;
+    if (n == 0) return VR_OK;
+    if (!d_rays || !d_offsets) return fail(VR_ERR_INVALID, "vr_query_events: NULL argument");
+    if (!aligned16(d_rays)) return fail(VR_ERR_INVALID, "vr_query_events: the device ray array must be 16-byte aligned");
+    c->q_count_valid = false;
+    HIP_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");  // d_rays may come from any stream
+    vr_status st = grow(c->q_cnt, (n + 1) * sizeof(uint32_t), "hipMalloc(event counts)");
+    if (st != VR_OK) return st;
+    uint32_t* ctl = (uint32_t*)c->q_ctl.p;
+    unsigned long long* d_total = (unsigned long long*)(ctl + 4);
+    size_t tmp_bytes = 0;
+    HIP_TRY(query_events_count(A, d_rays, (uint32_t)n, (uint32_t*)c->q_cnt.p, d_offsets, d_total, ctl + 1, query_refill(c), c->q_cus,
+                               nullptr, tmp_bytes, c->stream),
+            "event count scratch");
+    if ((st = grow(c->q_tmp, tmp_bytes + 16, "hipMalloc(event scan scratch)")) != VR_OK) return st;
+    HIP_TRY(query_events_count(A, d_rays, (uint32_t)n, (uint32_t*)c->q_cnt.p, d_offsets, d_total, ctl + 1, query_refill(c), c->q_cus,
+                               c->q_tmp.p, tmp_bytes, c->stream),
+            "query_events_count_kernel");
+    unsigned long long tot = 0;
+    HIP_TRY(hipMemcpyAsync(&tot, d_total, sizeof(tot), hipMemcpyDeviceToHost, c->stream), "hipMemcpy(event total)");
+    HIP_TRY(hipStreamSynchronize(c->stream), "query_events_count_kernel");
+    *total = tot;
+    if (tot > 0xffffffffull) return fail(VR_ERR_INVALID, "vr_query_events: more than 2^32 - 1 events in one call (split the batch)");
+    c->q_count_valid = true;
+    c->q_count_n = n;
+    c->q_count_total = tot;
+    return VR_OK;
+}
+
+vr_status vr_query_events_fill_device(vr_ctx* c, const vr_ray* d_rays, size_t n, const uint32_t* d_offsets, float* d_t,
+                                      uint32_t* d_ev, uint64_t cap, void* stream) {
+    c = first_device(c);
+    RenderArgs A;
+    if (vr_status st = query_begin(c, "vr_query_events", n, A); st != VR_OK) return st;
+    if (n == 0) return VR_OK;
+    if (!d_rays || !d_offsets) return fail(VR_ERR_INVALID, "vr_query_events: NULL argument");
+    if (!aligned16(d_rays)) return fail(VR_ERR_INVALID, "vr_query_events: the device ray array must be 16-byte aligned");
+    if (!c->q_count_valid || c->q_count_n != n)
+        return fail(VR_ERR_INVALID, "vr_query_events_fill_device: no vr_query_events_count_device call for this many rays preceded it");
+    const uint64_t tot = c->q_count_total;
+    if (cap < tot)
+        return fail(VR_ERR_OVERFLOW, "vr_query_events: " + std::to_string(tot) + " events, room for " + std::to_string(cap));
+    if (tot == 0) return VR_OK;
+    if (!d_t || !d_ev) return fail(VR_ERR_INVALID, "vr_query_events: NULL argument");
+    vr_status st = grow(c->q_keys, tot * 8, "hipMalloc(event keys)");
+    if (st != VR_OK) return st;
+    if ((st = grow(c->q_keys2, tot * 8, "hipMalloc(event keys)")) != VR_OK) return st;
+    uint32_t* ctl = (uint32_t*)c->q_ctl.p;
+    size_t tmp_bytes = 0;
+    HIP_TRY(query_events_fill(A, d_rays, (uint32_t)n, d_offsets, (uint32_t)tot, (unsigned long long*)c->q_keys.p,
+                              (unsigned long long*)c->q_keys2.p, d_t, d_ev, ctl + 2, query_refill(c), c->q_cus, nullptr, tmp_bytes,
+                              (hipStream_t)stream),
+            "event sort scratch");
+    if ((st = grow(c->q_tmp, tmp_bytes + 16, "hipMalloc(event sort scratch)")) != VR_OK) return st;
+    HIP_TRY(query_events_fill(A, d_rays, (uint32_t)n, d_offsets, (uint32_t)tot, (unsigned long long*)c->q_keys.p,
+                              (unsigned long long*)c->q_keys2.p, d_t, d_ev, ctl + 2, query_refill(c), c->q_cus, c->q_tmp.p, tmp_bytes,
+                              (hipStream_t)stream),
+            "query_events_fill_kernel");
+    return VR_OK;
+}
+
+vr_status vr_query_events(vr_ctx* c, const vr_ray* rays, size_t n, uint32_t* offsets, float* t, uint32_t* ev, uint64_t cap,
+                          uint64_t* total) {
+    c = first_device(c);
+    RenderArgs A;
+    vr_status st = query_begin(c, "vr_query_events", n, A);
+    if (st != VR_OK) return st;
+    if (!total) return fail(VR_ERR_INVALID, "vr_query_events: NULL total");
+    *total = 0;
+    if (n == 0) {
+        if (offsets) offsets[0] = 0;
+        return VR_OK;
+    }
+    if (!rays || (cap > 0 && (!t || !ev)) || (cap == 0 && ((t == nullptr) != (ev == nullptr))))
+        return fail(VR_ERR_INVALID, "vr_query_events: NULL argument");
+    if ((st = grow(c->q_in, n * sizeof(vr_ray), "hipMalloc(query rays)")) != VR_OK) return st;
+    if ((st = grow(c->q_off, (n + 1) * sizeof(uint32_t), "hipMalloc(event offsets)")) != VR_OK) return st;
+    HIP_TRY(hipMemcpy(c->q_in.p, rays, n * sizeof(vr_ray), hipMemcpyHostToDevice), "hipMemcpy(query rays)");
+    if ((st = vr_query_events_count_device(c, (const vr_ray*)c->q_in.p, n, (uint32_t*)c->q_off.p, total)) != VR_OK) return st;
+    if (offsets) HIP_TRY(hipMemcpy(offsets, c->q_off.p, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy(event offsets)");
+    if (cap == 0 && !t && !ev) return VR_OK;
+    const uint64_t tot = *total;
+    if (cap < tot) return fail(VR_ERR_OVERFLOW, "vr_query_events: " + std::to_string(tot) + " events, room for " + std::to_string(cap));
+    if (tot == 0) return VR_OK;
+    if ((st = grow(c->q_out, tot * sizeof(float), "hipMalloc(query results)")) != VR_OK) return st;
+    if ((st = grow(c->q_out2, tot * sizeof(uint32_t), "hipMalloc(query results)")) != VR_OK) return st;
+    st = vr_query_events_fill_device(c, (const vr_ray*)c->q_in.p, n, (const uint32_t*)c->q_off.p, (float*)c->q_out.p,
+                                     (uint32_t*)c->q_out2.p, tot, c->stream);
+    if (st != VR_OK) return st;
+    HIP_TRY(hipStreamSynchronize(c->stream), "query_events_fill_kernel");
+    HIP_TRY(hipMemcpy(t, c->q_out.p, tot * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    HIP_TRY(hipMemcpy(ev, c->q_out2.p, tot * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    return VR_OK;
+}
+
+vr_status vr_query_pack_rays_device(vr_ctx* c, const float* d_origins, const float* d_directions, const float* d_tmax,
+                                    uint32_t tmax_stride, size_t n, vr_ray* d_rays, void* stream) {
+    c = first_device(c);
+    if (!c) return fail(VR_ERR_INVALID, "vr_query_pack_rays_device: NULL ctx");
+    if (n == 0) return VR_OK;
+    if (!d_origins || !d_directions || !d_tmax || !d_rays || tmax_stride > 1 || n >= (1ull << 31) || !aligned16(d_rays))
+        return fail(VR_ERR_INVALID, "vr_query_pack_rays_device: bad argument");
+    HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+    HIP_TRY(query_pack_rays(d_origins, d_directions, d_tmax, tmax_stride, (uint32_t)n, d_rays, (hipStream_t)stream),
+            "query_pack_rays_kernel");
     return VR_OK;
 }
 

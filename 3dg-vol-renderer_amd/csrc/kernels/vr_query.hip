@@ -1,0 +1,545 @@
+// Batched mixture queries over the uploaded scene (include/vr_hip.h, vr_query_*): the three questions
+// the reference's GaussianMixtureModel answers about the mixture itself, for a caller's rays / points:
+//   transmittance_up_to(ray, tmax)          gmm.h:517-578   query_transmittance_kernel
+//   intersect_events(ray, events)           gmm.h:457-515   query_events_count_kernel / _fill_kernel + sort
+//   evaluate_sigma(active, pos, sa, ss)     gmm.h:98-126    query_sigma_kernel (active = the 3-sigma ellipsoids
+//                                                            holding pos, the set the integrators pass)
+//
+// Floating point: a query is an API for fidelity, so every Gaussian is tested with the exact forms of
+// vr_march.h (quad / intersect / optical_depth / mu_t: the reference's evaluation order, correctly rounded
+// division and square root, no contraction): hit decisions and t_enter / t_exit are bit-identical to
+// intersect_direct (gaussian.h:126-164). erf / exp come from the device library (a few ulp from glibc's).
+// Sums over Gaussians (optical depth, mu_t, mu_t * albedo) are kept in double, where adding a few dozen f32
+// terms is exact, so a result does not depend on the order in which a tree hands the Gaussians out:
+// VR_OPT_HALF_NODES / VR_OPT_DEVICE_BVH change the walk, not the answer.
+//
+// Ray walks (transmittance, events) are the shadow-ray kernel's scheme (ff_nee_kernel, vr_freeflight.hip): a
+// persistent grid, one ray per lane, a wave claims new rays by ballot once enough of its lanes are idle, and
+// each wave iteration is a NODE iteration (4-wide node steps, leaf children into an LDS FIFO) or a PRIM
+// iteration (Gaussians of the queued leaves), whichever more lanes can use. A walk whose LDS stack could
+// overflow, and every walk of a scene without the 4-wide tree (VR_OPT_HALF_NODES = 0, or boxes too small for
+// f16), is redone on the child-pair tree at the ray's completion.
+#include <hipcub/hipcub.hpp>
+#include <rocprim/rocprim.hpp>
+
+#include <algorithm>
+
+#include "vr_dev_common.h"
+
+namespace vr {
+namespace dev {
+
+constexpr int kQBlock = 256;
+#ifndef VR_QUERY_BLOCKS
+#define VR_QUERY_BLOCKS 4  // resident 256-lane blocks per CU (40 KB of LDS each: 4 waves per SIMD)
+#endif
+constexpr int kQQueue = 8, kQSteps = 4;  // leaf FIFO entries; node steps / Gaussians per lane per wave iteration
+
+// vr_ray row i (32 B, 16-B aligned): {origin, tmax}, {direction, unit}. The direction is normalised as the Ray
+// constructor does (make_ray, ray.h:11-12) unless `unit` says it already was (a Ray object's: normalising
+// twice would move it by an ulp). False: a non-finite origin, or a direction whose squared norm is 0, NaN or
+// infinite.
+__device__ __forceinline__ bool load_query_ray(const vr_ray* __restrict__ rays, uint32_t id, Ray& r, float& tmax) {
+    const float4* p = reinterpret_cast<const float4*>(rays) + 2 * (size_t)id;
+    const float4 a = p[0], b = p[1];
+    tmax = a.w;
+    const float s = dot3(b.x, b.y, b.z, b.x, b.y, b.z);
+    const bool ok = isfinite(a.x) && isfinite(a.y) && isfinite(a.z) && s > 0.0f && isfinite(s);
+    r = b.w != 0.0f ? Ray{a.x, a.y, a.z, b.x, b.y, b.z} : make_ray(a.x, a.y, a.z, b.x, b.y, b.z);
+    return ok;
+}
+
+// ---- per-ray operations of the walk ----
+// Op: kPrune (children beyond tmax are skipped; rays with tmax <= 0 / NaN finish at once), reset(),
+// prim(A, r, tmax, j) for record j (false: the ray is done), finish(id), invalid(id).
+
+// gmm.h:539-551: a = max(0, t_enter), b = min(tmax, t_exit), optical_depth(a, b) added if b > a.
+// TAU: the caller wants the optical depth itself, so the sum runs to the end; otherwise it stops at 104,
+// where expf(-x) is 0 in f32 whatever follows (the shadow kernel's early-out: the same Tr bit for bit).
+template <bool TAU>
+struct TransOp {
+    static constexpr bool kPrune = true;
+    float* tr;
+    float* tau;
+    double sum;
+    __device__ __forceinline__ void reset() { sum = 0.0; }
+    __device__ __forceinline__ bool prim(const RenderArgs& A, const Ray& r, float tmax, uint32_t j) {
+        const GRec g = load_rec(A.gauss, (int)j);
+        const Quad q = quad(g, r);
+        float t0, t1;
+        if (intersect(q, t0, t1)) {
+            const float a = fmaxf(0.0f, t0);
+            const float b = fminf(tmax, t1);
+            if (b > a) sum += (double)optical_depth(g, q, a, b);
+        }
+        return TAU ? true : sum < 104.0;
+    }
+    __device__ __forceinline__ void finish(uint32_t id) {
+        tr[id] = expf(-(float)sum);
+        if constexpr (TAU) tau[id] = (float)sum;
+    }
+    __device__ __forceinline__ void invalid(uint32_t id) {
+        tr[id] = __builtin_nanf("");
+        if constexpr (TAU) tau[id] = __builtin_nanf("");
+    }
+};
+
+// gmm.h:482-485: an entry event if t_enter >= 0, an exit event if t_exit >= 0.
+struct EventCountOp {
+    static constexpr bool kPrune = false;
+    uint32_t* counts;
+    uint32_t cnt;
+    __device__ __forceinline__ void reset() { cnt = 0; }
+    __device__ __forceinline__ bool prim(const RenderArgs& A, const Ray& r, float, uint32_t j) {
+        const GRec g = load_rec(A.gauss, (int)j);
+        float t0, t1;
+        if (intersect(quad(g, r), t0, t1)) cnt += (t0 >= 0.0f ? 1u : 0u) + (t1 >= 0.0f ? 1u : 0u);
+        return true;
+    }
+    __device__ __forceinline__ void finish(uint32_t id) { counts[id] = cnt; }
+    __device__ __forceinline__ void invalid(uint32_t id) { counts[id] = 0; }
+};
+
+// The same walk again, writing each event as a 64-bit sort key at the ray's offset: high word the bits of
+// t + 0.0f (-0 becomes +0; every t is >= 0, so the bits order as unsigned integers), low word
+// scene_index << 1 | exiting. Sorted per ray, events with equal t therefore come in scene order, a
+// Gaussian's entry before its exit, whatever order the tree produced them in.
+struct EventFillOp {
+    static constexpr bool kPrune = false;
+    const uint32_t* offsets;
+    unsigned long long* keys;
+    unsigned long long cap;
+    uint32_t base, room, w;
+    __device__ __forceinline__ void reset() { w = 0; }
+    __device__ __forceinline__ void put(float t, uint32_t low) {
+        // (room: the count pass's number for this ray; cap: the caller's buffers. Neither is ever passed.)
+        if (w < room && (unsigned long long)base + w < cap)
+            keys[(size_t)base + w] = ((unsigned long long)__float_as_uint(t + 0.0f) << 32) | low;
+        ++w;
+    }
+    __device__ __forceinline__ bool prim(const RenderArgs& A, const Ray& r, float, uint32_t j) {
+        const GRec g = load_rec(A.gauss, (int)j);
+        float t0, t1;
+        if (intersect(quad(g, r), t0, t1)) {
+            const uint32_t si = A.gauss_order[j] << 1;
+            if (t0 >= 0.0f) put(t0, si);
+            if (t1 >= 0.0f) put(t1, si | 1u);
+        }
+        return true;
+    }
+    __device__ __forceinline__ void finish(uint32_t) {}
+    __device__ __forceinline__ void invalid(uint32_t) {}
+};
+
+// The whole walk of one ray on the child-pair tree (half-precision nodes if the scene has them).
+template <class Op>
+__device__ __forceinline__ void pair_walk(const RenderArgs& A, const Ray& r, float tmax, float lim, int* stack, Op& op) {
+    auto prune = [&](float tmin, float) { return !Op::kPrune || tmin <= lim; };
+    auto leaf = [&](uint32_t first, uint32_t count) {
+        for (uint32_t j = first; j < first + count; ++j)
+            if (!op.prim(A, r, tmax, j)) return false;
+        return true;
+    };
+    if (A.hnodes) traverse<true>(A, r, stack, kQBlock, prune, leaf);
+    else traverse<false>(A, r, stack, kQBlock, prune, leaf);
+}
+
+template <class Op>
+__device__ __forceinline__ void query_walk(const RenderArgs& A, const vr_ray* __restrict__ rays, uint32_t n,
+                                           uint32_t* __restrict__ next, int refill, int* stack, int* ring, Op& op) {
+    const uint32_t lane = threadIdx.x & 63u;
+    bool live = false, exhausted = false;
+    uint32_t id = 0;
+    Ray r{};
+    float tmax = 0.0f, lim = 0.0f, ix = 0.0f, iy = 0.0f, iz = 0.0f, oxi = 0.0f, oyi = 0.0f, ozi = 0.0f;
+    int sp = 0, node = -1, qh = 0, qn = 0;
+    uint32_t j = 0, end = 0;  // Gaussians of the leaf being tested
+    bool redo = false;        // no 4-wide tree, or its stack could overflow: the pair-tree walk at completion
+    bool stop = false;        // the operation needs no further Gaussian
+    for (;;) {
+        const uint64_t idle = __ballot(!live);
+        if (!exhausted && (idle == ~0ull || __popcll(idle) >= refill)) {
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(next, (uint32_t)__popcll(idle));
+            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+            // (64-bit compare: the counter stays below n + 64 * waves, but base + 64 must not wrap)
+            exhausted = (uint64_t)base + (uint64_t)__popcll(idle) >= (uint64_t)n;
+            if (!live) {
+                const uint64_t mine = (uint64_t)base +
+                                      __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                if (mine < (uint64_t)n) {
+                    id = (uint32_t)mine;
+                    op.begin(id);
+                    if (!load_query_ray(rays, id, r, tmax)) {
+                        op.invalid(id);
+                    } else if ((Op::kPrune && !(tmax > 0.0f)) || A.num_prims <= 0) {
+                        op.reset();  // gmm.h:518-519 / :462: no walk
+                        op.finish(id);
+                    } else {
+                        float ox = r.ox, oy = r.oy, oz = r.oz;
+                        node_space<true>(A, ox, oy, oz);
+                        auto inv = [&](float d) {
+                            d *= A.hn_scale;
+                            return __frcp_rn(fabsf(d) > 1e-30f ? d : copysignf(1e-30f, d));
+                        };
+                        ix = inv(r.dx), iy = inv(r.dy), iz = inv(r.dz);
+                        oxi = ox * ix, oyi = oy * iy, ozi = oz * iz;
+                        // the shadow walk's prune bound (tmax padded by a few ulp of the slab distances)
+                        lim = Op::kPrune ? tmax + kTPad * (1.0f + fminf(tmax, 1e30f)) : INFINITY;
+                        op.reset();
+                        sp = 0;
+                        qh = qn = 0;
+                        j = end = 0;
+                        stop = false;
+                        redo = A.hnodes4 == nullptr;
+                        node = redo ? -1 : 0;
+                        live = true;
+                    }
+                }
+            }
+        }
+        if (!__any(live)) {
+            if (exhausted) break;
+            continue;
+        }
+        const bool has_prim = live && !stop && (j < end || qn > 0);
+        const bool can_node = live && !stop && node >= 0 && qn <= kQQueue - 4;
+        const int np = __popcll(__ballot(has_prim)), nn = __popcll(__ballot(can_node));
+        if (nn == 0 || (np > 0 && np >= nn)) {  // PRIM iteration
+            bool go = has_prim;
+            for (int k = 0; k < kQSteps; ++k) {
+                if (go) {
+                    if (j == end) {
+                        const int32_t ref = ring[qh * kQBlock];
+                        qh = (qh + 1) & (kQQueue - 1);
+                        --qn;
+                        j = leaf_first(ref);
+                        end = j + leaf_count(ref);
+                    }
+                    stop = !op.prim(A, r, tmax, j);
+                    ++j;
+                }
+                go = go && (j < end || qn > 0) && !stop;
+            }
+        } else {  // NODE iteration
+            bool go = can_node;
+            for (int k = 0; k < kQSteps; ++k) {
+                if (go) {
+                    float key[4];
+                    int32_t kr[4];
+                    wide_children(A, node, ix, iy, iz, oxi, oyi, ozi, [&](float tmin, float) { return !Op::kPrune || tmin <= lim; },
+                                  key, kr);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)  // leaves, near first
+                        if (kr[i] < 0) {
+                            ring[((qh + qn) & (kQQueue - 1)) * kQBlock] = kr[i];
+                            ++qn;
+                        }
+                    int first = -1;
+                    int32_t nxt = 0;
+#pragma unroll
+                    for (int i = 3; i >= 0; --i) {
+                        first = kr[i] > 0 ? i : first;
+                        nxt = kr[i] > 0 ? kr[i] : nxt;
+                    }
+                    if (sp + 3 > kStackSize) {
+                        redo = true;
+                        node = -1;
+                    } else {
+#pragma unroll
+                        for (int i = 3; i >= 0; --i)
+                            if (kr[i] > 0 && i != first) stack[(sp++) * kQBlock] = kr[i];
+                        if (first >= 0) node = nxt;
+                        else if (sp > 0) node = stack[(--sp) * kQBlock];
+                        else node = -1;
+                    }
+                }
+                go = go && node >= 0 && qn <= kQQueue - 4;
+            }
+        }
+        if (live && (redo || stop || (node < 0 && j == end && qn == 0))) {
+            if (redo) {
+                op.reset();
+                pair_walk(A, r, tmax, lim, stack, op);
+            }
+            op.finish(id);
+            live = false;
+        }
+    }
+}
+
+// `begin` (per claimed ray) is only needed by the fill pass; the other operations inherit this one.
+struct NoBegin {
+    __device__ __forceinline__ void begin(uint32_t) {}
+};
+template <bool TAU>
+struct TransOpB : TransOp<TAU>, NoBegin {};
+struct EventCountOpB : EventCountOp, NoBegin {};
+struct EventFillOpB : EventFillOp {
+    __device__ __forceinline__ void begin(uint32_t id) {
+        base = offsets[id];
+        room = offsets[id + 1] - base;
+    }
+};
+
+template <bool TAU>
+__global__ void __launch_bounds__(kQBlock) query_transmittance_kernel(RenderArgs A, const vr_ray* __restrict__ rays, uint32_t n,
+                                                                      float* __restrict__ tr, float* __restrict__ tau,
+                                                                      uint32_t* __restrict__ next, int refill) {
+    __shared__ int s_stack[(kStackSize + kQQueue) * kQBlock];
+    int* stack = s_stack + threadIdx.x;
+    TransOpB<TAU> op;
+    op.tr = tr;
+    op.tau = tau;
+    op.sum = 0.0;
+    query_walk(A, rays, n, next, refill, stack, stack + kStackSize * kQBlock, op);
+}
+
+__global__ void __launch_bounds__(kQBlock) query_events_count_kernel(RenderArgs A, const vr_ray* __restrict__ rays, uint32_t n,
+                                                                     uint32_t* __restrict__ counts, uint32_t* __restrict__ next,
+                                                                     int refill) {
+    __shared__ int s_stack[(kStackSize + kQQueue) * kQBlock];
+    int* stack = s_stack + threadIdx.x;
+    if (blockIdx.x == 0 && threadIdx.x == 0) counts[n] = 0;  // the scan's last input: offsets[n] = total
+    EventCountOpB op;
+    op.counts = counts;
+    op.cnt = 0;
+    query_walk(A, rays, n, next, refill, stack, stack + kStackSize * kQBlock, op);
+}
+
+__global__ void __launch_bounds__(kQBlock) query_events_fill_kernel(RenderArgs A, const vr_ray* __restrict__ rays, uint32_t n,
+                                                                    const uint32_t* __restrict__ offsets,
+                                                                    unsigned long long* __restrict__ keys, unsigned long long cap,
+                                                                    uint32_t* __restrict__ next, int refill) {
+    __shared__ int s_stack[(kStackSize + kQQueue) * kQBlock];
+    int* stack = s_stack + threadIdx.x;
+    EventFillOpB op;
+    op.offsets = offsets;
+    op.keys = keys;
+    op.cap = cap;
+    op.base = op.room = op.w = 0;
+    query_walk(A, rays, n, next, refill, stack, stack + kStackSize * kQBlock, op);
+}
+
+// Sorted keys -> the caller's arrays: t, and ev = scene_index << 1 | entering.
+__global__ void __launch_bounds__(256) query_events_unpack_kernel(const unsigned long long* __restrict__ keys,
+                                                                  unsigned long long total, float* __restrict__ t,
+                                                                  uint32_t* __restrict__ ev) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    if (i >= total) return;
+    const unsigned long long k = keys[i];
+    t[i] = __uint_as_float((uint32_t)(k >> 32));
+    ev[i] = (uint32_t)k ^ 1u;
+}
+
+// ---- sigma: containment walk, one point per lane ----
+// Gaussian i is active at x iff p.(M p) - 9 <= 0, p = x - mean, in f32 in quad's order for Cq (the value
+// whose sign decides intersect_direct's C for a ray starting at x). A child is entered iff the point lies
+// in its box: the leaf boxes are the 3-sigma boxes grown by 5 % (gaussian_bounds), and the f16 boxes of the
+// 4-wide tree are rounded outward from them (f16_directed, host and device builders), so every ellipsoid
+// holding x is reached. Sums in double (see the head of this file).
+struct SigmaAcc {
+    double sum, sum_alb;
+    uint32_t cnt;
+    __device__ __forceinline__ void reset() {
+        sum = sum_alb = 0.0;
+        cnt = 0;
+    }
+    __device__ __forceinline__ void leaf(const RenderArgs& A, int32_t ref, float x, float y, float z) {
+        const uint32_t first = leaf_first(ref), end = first + leaf_count(ref);
+        for (uint32_t j = first; j < end; ++j) {
+            const GRec g = load_rec(A.gauss, (int)j);
+            const float px = x - g.mx, py = y - g.my, pz = z - g.mz;
+            const float mpx = g.m00 * px + (g.m01 * py + g.m02 * pz);
+            const float mpy = g.m01 * px + (g.m11 * py + g.m12 * pz);
+            const float mpz = g.m02 * px + (g.m12 * py + g.m22 * pz);
+            const float C = dot3(px, py, pz, mpx, mpy, mpz) - 9.0f;
+            if (C <= 0.0f) {
+                const float m = mu_t(g, x, y, z);
+                sum += (double)m;
+                sum_alb += (double)(m * g.albedo);
+                ++cnt;
+            }
+        }
+    }
+};
+
+__global__ void __launch_bounds__(kQBlock) query_sigma_kernel(RenderArgs A, const float* __restrict__ xyz, uint32_t n,
+                                                              float* __restrict__ out, uint32_t* __restrict__ n_active) {
+    __shared__ int s_stack[kStackSize * kQBlock];
+    int* stack = s_stack + threadIdx.x;
+    const uint64_t i = (uint64_t)blockIdx.x * kQBlock + threadIdx.x;
+    if (i >= n) return;
+    const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+    SigmaAcc acc;
+    acc.reset();
+    bool redo = A.hnodes4 == nullptr;
+    if (A.num_prims > 0 && !redo) {
+        float ux = x, uy = y, uz = z;
+        node_space<true>(A, ux, uy, uz);
+        int sp = 0, node = 0;
+        for (;;) {
+            const uint4* np = reinterpret_cast<const uint4*>(A.hnodes4 + node);
+            const uint4 q0 = np[0], q1 = np[1], q2 = np[2], rf = np[3];
+            const uint32_t w[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
+            const int32_t ref[4] = {(int32_t)rf.x, (int32_t)rf.y, (int32_t)rf.z, (int32_t)rf.w};
+            if (sp + 4 > kStackSize) {
+                redo = true;
+                break;
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {  // child c: halves 6c .. 6c + 5 = min xyz, max xyz
+                float b[6];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) {
+                    const int h = 6 * c + k;
+                    const uint32_t word = w[h >> 1];
+                    b[k] = (float)__builtin_bit_cast(_Float16, (uint16_t)((h & 1) ? (word >> 16) : (word & 0xffffu)));
+                }
+                const bool in = ref[c] != 0 && ux >= b[0] && ux <= b[3] && uy >= b[1] && uy <= b[4] && uz >= b[2] && uz <= b[5];
+                if (in) {
+                    if (ref[c] < 0) acc.leaf(A, ref[c], x, y, z);
+                    else stack[(sp++) * kQBlock] = ref[c];
+                }
+            }
+            if (sp == 0) break;
+            node = stack[(--sp) * kQBlock];
+        }
+    }
+    if (A.num_prims > 0 && redo) {  // f32 child-pair tree: one push per level at most
+        acc.reset();
+        int sp = 0, node = 0;
+        bool bad = false;
+        for (;;) {
+            float f[12];
+            int2 nc;
+            load_pair<false>(A, node, f, nc);
+            int32_t go[2] = {0, 0};
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const float* b = f + 6 * s;
+                const int32_t c = s == 0 ? nc.x : nc.y;
+                const bool in = c != 0 && x >= b[0] && x <= b[3] && y >= b[1] && y <= b[4] && z >= b[2] && z <= b[5];
+                if (in) {
+                    if (c < 0) acc.leaf(A, c, x, y, z);
+                    else go[s] = c;
+                }
+            }
+            if (go[0] > 0 && go[1] > 0) {
+                if (sp >= kStackSize) {  // (deeper than the builder allows)
+                    bad = true;
+                    break;
+                }
+                stack[(sp++) * kQBlock] = go[1];
+                node = go[0];
+            } else if (go[0] > 0 || go[1] > 0) {
+                node = go[0] > 0 ? go[0] : go[1];
+            } else {
+                if (sp == 0) break;
+                node = stack[(--sp) * kQBlock];
+            }
+        }
+        if (bad) {
+            out[2 * i] = out[2 * i + 1] = __builtin_nanf("");
+            if (n_active) n_active[i] = 0;
+            return;
+        }
+    }
+    // gmm.h:115-125
+    const float sum = (float)acc.sum, sum_alb = (float)acc.sum_alb;
+    float sa = 0.0f, ss = 0.0f;
+    if (!(sum <= 0.0f)) {
+        const float a_mix = __fdiv_rn(sum_alb, sum);
+        ss = a_mix * sum;
+        sa = (1.0f - a_mix) * sum;
+    }
+    out[2 * i] = sa;
+    out[2 * i + 1] = ss;
+    if (n_active) n_active[i] = acc.cnt;
+}
+
+// Device-side packing of the Python mirror's torch inputs into vr_ray rows (tmax: one value per ray, or one
+// for all with tmax_stride = 0).
+__global__ void __launch_bounds__(256) query_pack_rays_kernel(const float* __restrict__ o, const float* __restrict__ d,
+                                                              const float* __restrict__ tmax, uint32_t tmax_stride, uint32_t n,
+                                                              vr_ray* __restrict__ rays) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    float4* p = reinterpret_cast<float4*>(rays) + 2 * i;
+    p[0] = make_float4(o[3 * i], o[3 * i + 1], o[3 * i + 2], tmax[(size_t)tmax_stride * i]);
+    p[1] = make_float4(d[3 * i], d[3 * i + 1], d[3 * i + 2], 0.0f);
+}
+
+struct ToU64 {
+    __host__ __device__ __forceinline__ unsigned long long operator()(uint32_t v) const { return v; }
+};
+
+}  // namespace dev
+
+// ---- launchers (host/vr_device.cpp) ----
+static inline dim3 query_grid(int cus) { return dim3((unsigned)std::max(1, cus) * VR_QUERY_BLOCKS); }
+
+hipError_t query_transmittance(const RenderArgs& A, const vr_ray* rays, uint32_t n, float* tr, float* tau, uint32_t* next,
+                               int refill, int cus, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(next, 0, sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    if (tau) hipLaunchKernelGGL(dev::query_transmittance_kernel<true>, query_grid(cus), dim3(dev::kQBlock), 0, s, A, rays, n, tr, tau, next, refill);
+    else hipLaunchKernelGGL(dev::query_transmittance_kernel<false>, query_grid(cus), dim3(dev::kQBlock), 0, s, A, rays, n, tr, tau, next, refill);
+    return hipGetLastError();
+}
+
+hipError_t query_sigma(const RenderArgs& A, const float* xyz, uint32_t n, float* out, uint32_t* n_active, hipStream_t s) {
+    hipLaunchKernelGGL(dev::query_sigma_kernel, dim3((n + dev::kQBlock - 1) / dev::kQBlock), dim3(dev::kQBlock), 0, s, A, xyz, n,
+                       out, n_active);
+    return hipGetLastError();
+}
+
+// counts: n + 1 words of scratch; offsets: n + 1 words (exclusive scan of the counts, offsets[n] = the
+// total modulo 2^32); total: the 64-bit sum. tmp == nullptr: only tmp_bytes is set.
+hipError_t query_events_count(const RenderArgs& A, const vr_ray* rays, uint32_t n, uint32_t* counts, uint32_t* offsets,
+                              unsigned long long* total, uint32_t* next, int refill, int cus, void* tmp, size_t& tmp_bytes,
+                              hipStream_t s) {
+    hipcub::TransformInputIterator<unsigned long long, dev::ToU64, const uint32_t*> it(counts, dev::ToU64());
+    if (!tmp) {
+        size_t a = 0, b = 0;
+        hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, a, counts, offsets, (int)(n + 1), s);
+        if (e != hipSuccess) return e;
+        e = hipcub::DeviceReduce::Sum(nullptr, b, it, total, (int)(n + 1), s);
+        tmp_bytes = std::max(a, b);
+        return e;
+    }
+    hipError_t e = hipMemsetAsync(next, 0, sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(dev::query_events_count_kernel, query_grid(cus), dim3(dev::kQBlock), 0, s, A, rays, n, counts, next, refill);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    size_t bytes = tmp_bytes;
+    if ((e = hipcub::DeviceScan::ExclusiveSum(tmp, bytes, counts, offsets, (int)(n + 1), s)) != hipSuccess) return e;
+    bytes = tmp_bytes;
+    return hipcub::DeviceReduce::Sum(tmp, bytes, it, total, (int)(n + 1), s);
+}
+
+// keys / keys2: `total` 64-bit words each. tmp == nullptr: only tmp_bytes is set.
+hipError_t query_events_fill(const RenderArgs& A, const vr_ray* rays, uint32_t n, const uint32_t* offsets, uint32_t total,
+                             unsigned long long* keys, unsigned long long* keys2, float* t, uint32_t* ev, uint32_t* next,
+                             int refill, int cus, void* tmp, size_t& tmp_bytes, hipStream_t s) {
+    if (!tmp) return rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, keys, keys2, total, n, offsets, offsets + 1, 0, 63, s);
+    hipError_t e = hipMemsetAsync(next, 0, sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(dev::query_events_fill_kernel, query_grid(cus), dim3(dev::kQBlock), 0, s, A, rays, n, offsets, keys,
+                       (unsigned long long)total, next, refill);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    size_t bytes = tmp_bytes;
+    if ((e = rocprim::segmented_radix_sort_keys(tmp, bytes, keys, keys2, total, n, offsets, offsets + 1, 0, 63, s)) != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(dev::query_events_unpack_kernel, dim3((unsigned)(((unsigned long long)total + 255u) / 256u)), dim3(256), 0, s,
+                       keys2, (unsigned long long)total, t, ev);
+    return hipGetLastError();
+}
+
+hipError_t query_pack_rays(const float* o, const float* d, const float* tmax, uint32_t tmax_stride, uint32_t n, vr_ray* rays,
+                           hipStream_t s) {
+    hipLaunchKernelGGL(dev::query_pack_rays_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, o, d, tmax, tmax_stride, n, rays);
+    return hipGetLastError();
+}
+
+}  // namespace vr

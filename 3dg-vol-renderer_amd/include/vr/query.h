@@ -1,0 +1,103 @@
+// query.h — the reference's GaussianMixtureModel queries (include/gmm.h) in batch form over the C ABI
+// (include/vr_hip.h, vr_query_*): the mixture is the uploaded scene, the batch runs on the GPU.
+#pragma once
+#include <limits>
+
+#include "integrator.h"
+#include "ray.h"
+
+// smm.h:7-15
+struct PrimitiveHitEvent {
+    float t;        // distance along ray
+    bool entering;  // entering/exiting primitive
+    size_t index;   // index in mixture model array
+    bool operator<(const PrimitiveHitEvent& other) const { return t < other.t; }
+};
+
+// The three questions the reference's integrators ask scene.gmm, for many rays / points at once. The
+// context is obtained as HipIntegrator obtains its own (one per GPU, created on first use) and the scene is
+// uploaded when it changed, so a MixtureQuery and the integrators of one program share the uploaded scene.
+class MixtureQuery {
+    const Scene& scene_;
+    int device_;
+
+    vr_ctx* ready() const {
+        vr_ctx* ctx = context();
+        HipIntegrator::upload(ctx, scene_);
+        return ctx;
+    }
+    // A Ray's direction was normalised by its constructor (ray.h:11-12): it goes to the device as it stands.
+    static std::vector<vr_ray> pack(const std::vector<Ray>& rays, const std::vector<float>* tmax, float tmax_all) {
+        std::vector<vr_ray> r(rays.size());
+        for (size_t i = 0; i < rays.size(); ++i) {
+            for (int k = 0; k < 3; ++k) {
+                r[i].origin[k] = rays[i].origin[k];
+                r[i].direction[k] = rays[i].direction[k];
+            }
+            r[i].tmax = tmax ? (*tmax)[i] : tmax_all;
+            r[i].unit = 1.0f;
+        }
+        return r;
+    }
+
+public:
+    explicit MixtureQuery(const Scene& scene, int dev = 0) : scene_(scene), device_(dev) {}
+    vr_ctx* context() const { return vr_cpp::device(device_); }
+
+    // gmm.h:517-578 transmittance_up_to(ray, tmax) per ray; *tau (if given) receives the optical depths.
+    std::vector<float> transmittance_up_to(const std::vector<Ray>& rays, const std::vector<float>& tmax,
+                                           std::vector<float>* tau = nullptr) const {
+        if (tmax.size() != rays.size()) throw std::runtime_error("transmittance_up_to: one tmax per ray");
+        return transmittance(pack(rays, &tmax, 0.0f), tau);
+    }
+    std::vector<float> transmittance_up_to(const std::vector<Ray>& rays, float tmax = std::numeric_limits<float>::infinity(),
+                                           std::vector<float>* tau = nullptr) const {
+        return transmittance(pack(rays, nullptr, tmax), tau);
+    }
+
+    // gmm.h:457-515 intersect_events(ray, events) per ray: sorted by t; events with equal t in scene order,
+    // entry before exit (not the order the reference's std::sort happens to leave).
+    std::vector<std::vector<PrimitiveHitEvent>> intersect_events(const std::vector<Ray>& rays) const {
+        vr_ctx* ctx = ready();
+        const std::vector<vr_ray> r = pack(rays, nullptr, 0.0f);
+        std::vector<uint32_t> off(rays.size() + 1, 0u);
+        uint64_t total = 0;
+        vr_cpp::check(vr_query_events(ctx, r.data(), r.size(), off.data(), nullptr, nullptr, 0, &total));
+        std::vector<float> t(total);
+        std::vector<uint32_t> ev(total);
+        if (total) vr_cpp::check(vr_query_events(ctx, r.data(), r.size(), off.data(), t.data(), ev.data(), total, &total));
+        std::vector<std::vector<PrimitiveHitEvent>> out(rays.size());
+        for (size_t i = 0; i < rays.size(); ++i) {
+            out[i].reserve(off[i + 1] - off[i]);
+            for (uint32_t k = off[i]; k < off[i + 1]; ++k) out[i].push_back(PrimitiveHitEvent{t[k], (ev[k] & 1u) != 0, ev[k] >> 1});
+        }
+        return out;
+    }
+
+    // gmm.h:98-126 evaluate_sigma(active, pos, sigma_a, sigma_s) per point, `active` being the Gaussians
+    // whose 3-sigma ellipsoid holds the point; *n_active (if given) receives how many those are.
+    void evaluate_sigma(const std::vector<Eigen::Vector3f>& pos, std::vector<float>& sigma_a, std::vector<float>& sigma_s,
+                        std::vector<uint32_t>* n_active = nullptr) const {
+        vr_ctx* ctx = ready();
+        std::vector<float> xyz(3 * pos.size()), as(2 * pos.size());
+        for (size_t i = 0; i < pos.size(); ++i)
+            for (int k = 0; k < 3; ++k) xyz[3 * i + k] = pos[i][k];
+        if (n_active) n_active->assign(pos.size(), 0u);
+        vr_cpp::check(vr_query_sigma(ctx, xyz.data(), pos.size(), as.data(), n_active ? n_active->data() : nullptr));
+        sigma_a.resize(pos.size());
+        sigma_s.resize(pos.size());
+        for (size_t i = 0; i < pos.size(); ++i) {
+            sigma_a[i] = as[2 * i];
+            sigma_s[i] = as[2 * i + 1];
+        }
+    }
+
+private:
+    std::vector<float> transmittance(const std::vector<vr_ray>& r, std::vector<float>* tau) const {
+        vr_ctx* ctx = ready();
+        std::vector<float> tr(r.size());
+        if (tau) tau->assign(r.size(), 0.0f);
+        vr_cpp::check(vr_query_transmittance(ctx, r.data(), r.size(), tr.data(), tau ? tau->data() : nullptr));
+        return tr;
+    }
+};

@@ -458,11 +458,173 @@ class Device:
         check(lib().vr_unshuffle_tiles_device(self._h, ctypes.c_void_p(slabs_ptr), nslabs, tiles_per_slab, width,
                                               height, ctypes.c_void_p(image_ptr), ctypes.c_void_p(stream_ptr)))
 
+    # ---- mixture queries (vr_query_*, include/vr_hip.h): gmm.h:517-578, :457-515, :98-126 in batch form ----
+    # Arguments are numpy arrays (host entry points) or torch tensors on this context's GPU (the `_device`
+    # entry points on torch's current stream, no host copy); results are of the same kind. The scene is
+    # uploaded lazily, as Integrator._device does. Shapes and dtypes are checked before the library is called.
+
+    def _first_gpu(self):
+        return self.device[0] if isinstance(self.device, tuple) else self.device
+
+    def _check_torch(self, *tensors):
+        for t in tensors:
+            if t.device.type != "cuda" or t.device.index != self._first_gpu():
+                raise ValueError(f"tensor on {t.device}: this context queries cuda:{self._first_gpu()}")
+
+    def _pack_rays_torch(self, o, d, tmax):
+        import torch
+        n = o.shape[0]
+        o, d = o.contiguous(), d.contiguous()
+        if _is_torch(tmax):
+            tm, stride = tmax.contiguous(), 0 if tmax.numel() == 1 else 1
+        else:
+            tm, stride = torch.full((1,), float(tmax), dtype=torch.float32, device=o.device), 0
+        rays = torch.empty((n, 8), dtype=torch.float32, device=o.device)
+        stream = torch.cuda.current_stream(o.device).cuda_stream
+        check(lib().vr_query_pack_rays_device(self._h, o.data_ptr(), d.data_ptr(), tm.data_ptr(), stride, n,
+                                              rays.data_ptr(), stream))
+        return rays, stream
+
+    @staticmethod
+    def _pack_rays_numpy(o, d, tmax):
+        rays = np.zeros((o.shape[0], 8), np.float32)
+        rays[:, 0:3] = o
+        rays[:, 3] = tmax
+        rays[:, 4:7] = d
+        return rays
+
+    def query_transmittance(self, scene, origins, directions, tmax=float("inf"), return_tau=False):
+        """GaussianMixtureModel::transmittance_up_to (gmm.h:517-578) for n rays: origins, directions (n, 3)
+        float32, tmax a scalar or (n,) float32 (it broadcasts). Returns Tr (n,), or (Tr, tau) with the
+        optical depth itself (Tr == expf(-tau) bit for bit). Rays with a non-finite origin or a zero /
+        non-finite direction give NaN."""
+        torch_in = _query_ray_args(origins, directions, tmax)
+        self.upload(scene)
+        n = origins.shape[0]
+        if torch_in:
+            import torch
+            self._check_torch(origins, directions, *([tmax] if _is_torch(tmax) else []))
+            rays, stream = self._pack_rays_torch(origins, directions, tmax)
+            tr = torch.empty(n, dtype=torch.float32, device=origins.device)
+            tau = torch.empty(n, dtype=torch.float32, device=origins.device) if return_tau else None
+            check(lib().vr_query_transmittance_device(self._h, rays.data_ptr(), n, tr.data_ptr(),
+                                                      tau.data_ptr() if return_tau else None, stream))
+        else:
+            rays = self._pack_rays_numpy(origins, directions, tmax)
+            tr = np.empty(n, np.float32)
+            tau = np.empty(n, np.float32) if return_tau else None
+            check(lib().vr_query_transmittance(self._h, rays.ctypes.data, n, fptr(tr), fptr(tau) if return_tau else None))
+        return (tr, tau) if return_tau else tr
+
+    def query_sigma(self, scene, points, return_active=False):
+        """GaussianMixtureModel::evaluate_sigma (gmm.h:98-126) at n points (n, 3) float32, over the Gaussians
+        whose 3-sigma ellipsoid holds the point. Returns sigma (n, 2) = (sigma_a, sigma_s), or (sigma,
+        n_active) with the size of that set per point."""
+        torch_in = _query_point_args(points)
+        self.upload(scene)
+        n = points.shape[0]
+        if torch_in:
+            import torch
+            self._check_torch(points)
+            pts = points.contiguous()
+            sig = torch.empty((n, 2), dtype=torch.float32, device=points.device)
+            act = torch.empty(n, dtype=torch.int32, device=points.device) if return_active else None
+            check(lib().vr_query_sigma_device(self._h, pts.data_ptr(), n, sig.data_ptr(),
+                                              act.data_ptr() if return_active else None,
+                                              torch.cuda.current_stream(points.device).cuda_stream))
+        else:
+            pts = np.ascontiguousarray(points)
+            sig = np.empty((n, 2), np.float32)
+            cnt = np.empty(n, np.uint32) if return_active else None
+            check(lib().vr_query_sigma(self._h, fptr(pts), n, fptr(sig),
+                                       cnt.ctypes.data_as(L.U32P) if return_active else None))
+            act = cnt.astype(np.int32) if return_active else None
+        return (sig, act) if return_active else sig
+
+    def query_events(self, scene, origins, directions):
+        """GaussianMixtureModel::intersect_events (gmm.h:457-515) for n rays. Returns (offsets, t, gaussian,
+        entering): ray i's events are the slice offsets[i]:offsets[i + 1] (offsets: (n + 1,) int64) of t
+        (float32, non-decreasing per ray), gaussian (int32 scene index) and entering (bool). Events of a ray with
+        equal t come in scene order, entry before exit: deterministic, but not the tie order of the
+        reference's std::sort."""
+        torch_in = _query_ray_args(origins, directions, 0.0)
+        self.upload(scene)
+        n = origins.shape[0]
+        total = ctypes.c_uint64()
+        if torch_in:
+            import torch
+            self._check_torch(origins, directions)
+            rays, stream = self._pack_rays_torch(origins, directions, 0.0)
+            off = torch.zeros(n + 1, dtype=torch.int32, device=origins.device)  # (uint32 words)
+            check(lib().vr_query_events_count_device(self._h, rays.data_ptr(), n, off.data_ptr(), ctypes.byref(total)))
+            t = torch.empty(total.value, dtype=torch.float32, device=origins.device)
+            ev = torch.empty(total.value, dtype=torch.int32, device=origins.device)
+            check(lib().vr_query_events_fill_device(self._h, rays.data_ptr(), n, off.data_ptr(), t.data_ptr(),
+                                                    ev.data_ptr(), total.value, stream))
+            return off.to(torch.int64) & 0xffffffff, t, ev >> 1, (ev & 1).to(torch.bool)
+        rays = self._pack_rays_numpy(origins, directions, 0.0)
+        off = np.zeros(n + 1, np.uint32)
+        check(lib().vr_query_events(self._h, rays.ctypes.data, n, off.ctypes.data_as(L.U32P), None, None, 0,
+                                    ctypes.byref(total)))
+        t = np.empty(total.value, np.float32)
+        ev = np.empty(total.value, np.uint32)
+        if total.value:
+            check(lib().vr_query_events(self._h, rays.ctypes.data, n, off.ctypes.data_as(L.U32P), fptr(t),
+                                        ev.ctypes.data_as(L.U32P), total.value, ctypes.byref(total)))
+        return off.astype(np.int64), t, (ev >> 1).astype(np.int32), (ev & 1).astype(bool)
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and L is not None and L._lib is not None:  # (L is None during interpreter teardown)
             L._lib.vr_destroy(h)
             self._h = None
+
+
+def _is_torch(x):
+    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
+
+
+def _query_f32(x, name, shape_tail):
+    """x is an (n,) + shape_tail float32 numpy array or torch tensor (ValueError otherwise); True for torch."""
+    if _is_torch(x):
+        import torch
+        ok_dtype = x.dtype == torch.float32
+    elif isinstance(x, np.ndarray):
+        ok_dtype = x.dtype == np.float32
+    else:
+        raise ValueError(f"{name} must be a numpy array or a torch tensor, not {type(x).__name__}")
+    if not ok_dtype:
+        raise ValueError(f"{name} must be float32, not {x.dtype}")
+    if len(x.shape) != 1 + len(shape_tail) or tuple(x.shape[1:]) != tuple(shape_tail):
+        raise ValueError(f"{name} must have shape (n{''.join(', %d' % k for k in shape_tail)}), not {tuple(x.shape)}")
+    return _is_torch(x)
+
+
+def _query_ray_args(origins, directions, tmax):
+    """Checks the ray arguments of a query before anything reaches the library; True for torch input."""
+    t_o = _query_f32(origins, "origins", (3,))
+    t_d = _query_f32(directions, "directions", (3,))
+    if t_o != t_d:
+        raise ValueError("origins and directions must both be numpy arrays or both torch tensors")
+    if origins.shape[0] != directions.shape[0]:
+        raise ValueError(f"{origins.shape[0]} origins but {directions.shape[0]} directions")
+    if _is_torch(tmax) or isinstance(tmax, np.ndarray):
+        if len(tmax.shape) == 0:
+            tmax = tmax.reshape(1)
+        if _query_f32(tmax, "tmax", ()) != t_o:
+            raise ValueError("tmax must be a scalar or of the same kind as origins")
+        if tmax.shape[0] not in (1, origins.shape[0]):
+            raise ValueError(f"tmax has {tmax.shape[0]} entries for {origins.shape[0]} rays")
+    else:
+        try:
+            float(tmax)
+        except (TypeError, ValueError):
+            raise ValueError(f"tmax must be a number or a float32 array, not {type(tmax).__name__}") from None
+    return t_o
+
+
+def _query_point_args(points):
+    return _query_f32(points, "points", (3,))
 
 
 def num_tiles(width, height):

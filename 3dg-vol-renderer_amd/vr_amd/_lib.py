@@ -81,6 +81,10 @@ class vr_sfd_result(ctypes.Structure):
                 ("final_loss", ctypes.c_double)]
 
 
+class vr_ray(ctypes.Structure):
+    _fields_ = [("origin", f3), ("tmax", ctypes.c_float), ("direction", f3), ("unit", ctypes.c_float)]
+
+
 # name -> (restype, argtypes). Every symbol declared in include/vr_hip.h.
 P = ctypes.c_void_p
 PP = ctypes.POINTER(ctypes.c_void_p)
@@ -153,6 +157,14 @@ SIGNATURES = {
     "vr_synchronize": (ST, [P]),
     "vr_get_stats": (ST, [P, ctypes.POINTER(vr_render_stats)]),
     "vr_get_fallback_pixels": (ST, [P, ctypes.POINTER(ctypes.c_uint32), ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "vr_query_transmittance": (ST, [P, P, ctypes.c_size_t, FP, FP]),
+    "vr_query_transmittance_device": (ST, [P, P, ctypes.c_size_t, P, P, P]),
+    "vr_query_sigma": (ST, [P, FP, ctypes.c_size_t, FP, U32P]),
+    "vr_query_sigma_device": (ST, [P, P, ctypes.c_size_t, P, P, P]),
+    "vr_query_events_count_device": (ST, [P, P, ctypes.c_size_t, P, ctypes.POINTER(ctypes.c_uint64)]),
+    "vr_query_events_fill_device": (ST, [P, P, ctypes.c_size_t, P, P, P, ctypes.c_uint64, P]),
+    "vr_query_events": (ST, [P, P, ctypes.c_size_t, U32P, FP, U32P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    "vr_query_pack_rays_device": (ST, [P, P, P, P, ctypes.c_uint32, ctypes.c_size_t, P, P]),
     "vr_debug_pixel_records": (ST, [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_float), ctypes.c_size_t,
                                     ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
 }

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define VR_ABI_VERSION 7
+#define VR_ABI_VERSION 8
 
 typedef enum vr_status {
     VR_OK = 0,
@@ -421,6 +421,78 @@ vr_status vr_get_fallback_pixels(vr_ctx* ctx, uint32_t* xy, size_t cap, size_t* 
  * otherwise: a narrower buffer would be written past its end); call with cap = 0 to learn both. */
 vr_status vr_debug_pixel_records(vr_ctx* ctx, uint32_t x, uint32_t y, float* out, size_t cap, size_t row, size_t* n,
                                  size_t* row_out);
+
+/* ---------------- mixture queries (gmm.h) ---------------- */
+/* The three questions GaussianMixtureModel answers about the mixture itself, for a batch of the caller's
+ * rays or points against the uploaded Gaussian scene (sphere scenes: VR_ERR_UNSUPPORTED). Every Gaussian is
+ * tested with the exact forms (intersect_direct gaussian.h:126-164, optical_depth :208-231, mu_t :111-117 in
+ * the reference's evaluation order), so hit decisions and entry / exit distances are the reference's bit for
+ * bit; erf / exp come from the device library. Results do not depend on VR_OPT_HALF_NODES / VR_OPT_DEVICE_BVH.
+ * Queries leave the last frame's report and statistics (vr_synchronize, vr_get_stats) untouched; on a
+ * vr_init_multi context they act on the first device. A context runs one query at a time (they share its
+ * workspaces): calls on one context are ordered by the caller, as renders are.
+ * Common errors: VR_ERR_NOSCENE before an upload; VR_ERR_INVALID for a NULL pointer with n > 0, a device ray
+ * array that is not 16-byte aligned, or n >= 2^31; n == 0 is VR_OK and touches nothing.
+ * The `_device` forms take device pointers and are asynchronous on `stream` (a hipStream_t, NULL: the default
+ * stream), like vr_render_tiles_device; the host forms copy and synchronise. */
+
+/* One query ray, Ray(origin, direction) (ray.h:5-13) plus the distance bound of transmittance_up_to. 32 bytes. */
+typedef struct vr_ray {
+    float origin[3];
+    float tmax;      /* transmittance only; +inf is valid */
+    float direction[3];
+    float unit;      /* 0: the direction is normalised as the Ray constructor does (ray.h:11-12); non-zero: it is a
+                        Ray object's, normalised already, and is used as it stands (normalising twice would
+                        move it by an ulp, and with it every entry / exit distance) */
+} vr_ray;
+
+/* GaussianMixtureModel::transmittance_up_to (gmm.h:517-578): tr[i] = expf(-(float)sum) with sum the double
+ * sum over the Gaussians ray i hits of optical_depth(max(0, t_enter), min(tmax, t_exit)) where that interval
+ * is not empty; tau[i] = (float)sum if tau is not NULL (then tr[i] == expf(-tau[i]) bit for bit). tmax <= 0 or
+ * NaN: tr = 1, tau = 0 (gmm.h:518). A ray with a non-finite origin, or a direction whose squared norm is 0,
+ * NaN or infinite in f32, gets NaN in both. */
+vr_status vr_query_transmittance(vr_ctx* ctx, const vr_ray* rays, size_t n, float* tr, float* tau);
+vr_status vr_query_transmittance_device(vr_ctx* ctx, const vr_ray* d_rays, size_t n, float* d_tr, float* d_tau,
+                                        void* stream);
+
+/* GaussianMixtureModel::evaluate_sigma (gmm.h:98-126) at n points xyz[3n], with `active` = the Gaussians
+ * whose 3-sigma ellipsoid holds the point (p.(M p) - 9 <= 0 in f32, p = x - mean: the sign of
+ * intersect_direct's C, gaussian.h:136, for a ray starting there), the set the integrators pass.
+ * sigma_as[2i] = sigma_a, sigma_as[2i + 1] = sigma_s (both 0 when the summed mu_t is <= 0, gmm.h:115-118; no
+ * clamp); n_active[i] (may be NULL) = the size of that set. The two sums are kept in double and rounded to
+ * f32 once (the reference adds in f32 in scene order), so they do not depend on a visit order. */
+vr_status vr_query_sigma(vr_ctx* ctx, const float* xyz, size_t n, float* sigma_as, uint32_t* n_active);
+vr_status vr_query_sigma_device(vr_ctx* ctx, const float* d_xyz, size_t n, float* d_sigma_as, uint32_t* d_n_active,
+                                void* stream);
+
+/* GaussianMixtureModel::intersect_events (gmm.h:457-515; tmax is not read): per ray the events of every
+ * Gaussian it hits, an entry at t_enter (clamped to 0 for an origin inside) and an exit at t_exit, sorted by
+ * t. Ray i's events are t[offsets[i] .. offsets[i + 1]) and ev[..] = scene_index << 1 | entering
+ * (PrimitiveHitEvent{t, entering, index}); t is canonical (-0 is stored as +0). Events of one ray with equal
+ * t come in scene order, a Gaussian's entry before its exit: deterministic and independent of the tree, but
+ * NOT the order the reference's std::sort leaves them in (which depends on its BVH's traversal order); it
+ * may change when the reference's tie order is settled. A ray with a non-finite origin or an unusable
+ * direction has no events.
+ * Two passes. Count: writes the n + 1 offsets and the total (= offsets[n]); it is synchronous (it waits for
+ * the device's earlier work, whatever stream produced d_rays, and for its own, to return the total).
+ * VR_ERR_INVALID if the total exceeds 2^32 - 1. Fill (asynchronous on `stream`): writes
+ * the sorted events of the same rays; d_offsets must be the array that count call wrote and cap (the length
+ * of d_t and d_ev) at least its total, VR_ERR_OVERFLOW otherwise (nothing is written); VR_ERR_INVALID if no
+ * count call for n rays preceded it on this context. */
+vr_status vr_query_events_count_device(vr_ctx* ctx, const vr_ray* d_rays, size_t n, uint32_t* d_offsets, uint64_t* total);
+vr_status vr_query_events_fill_device(vr_ctx* ctx, const vr_ray* d_rays, size_t n, const uint32_t* d_offsets, float* d_t,
+                                      uint32_t* d_ev, uint64_t cap, void* stream);
+/* Host form, a two-call protocol as vr_get_fallback_pixels: *total is always set and offsets (n + 1 words, may
+ * be NULL) filled whenever it is given. cap = 0 with t and ev NULL asks for those only (VR_OK). Otherwise t and
+ * ev hold cap events each: with cap >= *total the events are written, with a smaller cap nothing is written to
+ * t or ev and the call returns VR_ERR_OVERFLOW. */
+vr_status vr_query_events(vr_ctx* ctx, const vr_ray* rays, size_t n, uint32_t* offsets, float* t, uint32_t* ev, uint64_t cap,
+                          uint64_t* total);
+/* Packs n rays from separate device arrays (origins[3n], directions[3n], tmax[n], or one tmax for all rays
+ * with tmax_stride = 0, else 1) into vr_ray rows on the device. Asynchronous on `stream`. */
+vr_status vr_query_pack_rays_device(vr_ctx* ctx, const float* d_origins, const float* d_directions, const float* d_tmax,
+                                    uint32_t tmax_stride, size_t n, vr_ray* d_rays, void* stream);
+
 
 #ifdef __cplusplus
 } /* extern "C" */

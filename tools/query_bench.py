@@ -1,0 +1,103 @@
+#!/usr/bin/env python
+"""Throughput of the batched mixture queries (Device.query_transmittance / query_events / query_sigma) on the
+benchmark's 1M-Gaussian make_random scene: 2^22 camera-like rays with tmax = inf, the same rays for the events,
+2^22 points uniform in the scene's bounds. Inputs live on the device (torch tensors: the `_device` entry points,
+rays packed on the device), every query is warmed up, and the figure is the median of timed repeats between HIP
+events on torch's current stream. Prints one JSON line and, with --out, writes it to a file.
+
+    python tools/query_bench.py [--gaussians 1000000] [--rays 4194304] [--points 4194304] [--repeats 5] [--out F]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "3dg-vol-renderer_amd"))
+
+import vr_amd as vr  # noqa: E402
+
+CAM_POS = np.array([0.0, 1.0, 6.0], np.float32)  # tests/main.cpp:21-34, as bench.py
+CAM_VIEW = np.array([0.0, 0.0, -1.0], np.float32)
+FOV = np.float32(0.25 * np.pi)
+
+
+def camera_rays(n):
+    """The primary rays of a square pinhole frame of n pixels (camera.h:45-53), unnormalised directions."""
+    side = int(round(n ** 0.5))
+    assert side * side == n, "--rays must be a square number"
+    cam = vr.Pinhole_Camera(CAM_POS, CAM_VIEW, FOV).basis()
+    u = 1.0 - (np.arange(side, dtype=np.float32) + 0.5) / side * 2.0
+    v = (np.arange(side, dtype=np.float32) + 0.5) / side * 2.0 - 1.0
+    uu, vv = np.meshgrid(u, v)
+    o = cam["position"] + uu[..., None] * cam["right"] + vv[..., None] * cam["up"]
+    d = cam["pinhole"] - o
+    return o.reshape(-1, 3).astype(np.float32), d.reshape(-1, 3).astype(np.float32)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gaussians", type=int, default=1_000_000)
+    ap.add_argument("--rays", type=int, default=1 << 22)
+    ap.add_argument("--points", type=int, default=1 << 22)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--seed", type=int, default=2025)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("query_bench: no GPU (there is no CPU path to time)")
+
+    scene = vr.Scene(vr.Scene.GAUSSIANS)
+    scene.add_random_gaussians(args.gaussians, seed=args.seed, variant=0)
+    info = scene.info()
+    lo, hi = np.array(list(info.bounds_min), np.float32), np.array(list(info.bounds_max), np.float32)
+    o, d = camera_rays(args.rays)
+    p = np.random.default_rng(7).uniform(lo, hi, (args.points, 3)).astype(np.float32)
+    o, d, p = (torch.tensor(a).cuda() for a in (o, d, p))
+    dev = vr.Device.get(0)
+    dev.upload(scene)
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            out = fn()
+        ms = []
+        for _ in range(args.repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return statistics.median(ms), ms, out
+
+    tr_ms, tr_all, tr = timed(lambda: dev.query_transmittance(scene, o, d))
+    tau_ms, tau_all, _ = timed(lambda: dev.query_transmittance(scene, o, d, return_tau=True))
+    ev_ms, ev_all, ev = timed(lambda: dev.query_events(scene, o, d))
+    sg_ms, sg_all, sg = timed(lambda: dev.query_sigma(scene, p, return_active=True))
+    n_events = int(ev[0][-1])
+    res = {
+        "gaussians": args.gaussians, "rays": args.rays, "points": args.points, "repeats": args.repeats,
+        "transmittance_ms": tr_ms, "transmittance_mrays_s": args.rays / tr_ms / 1e3,
+        "transmittance_tau_ms": tau_ms, "transmittance_tau_mrays_s": args.rays / tau_ms / 1e3,
+        "events": n_events, "events_per_ray": n_events / args.rays, "events_ms": ev_ms,
+        "events_mevents_s": n_events / ev_ms / 1e3, "events_mrays_s": args.rays / ev_ms / 1e3,
+        "sigma_ms": sg_ms, "sigma_mpoints_s": args.points / sg_ms / 1e3,
+        "mean_active": float(sg[1].float().mean()), "mean_transmittance": float(tr.mean()),
+        "all_ms": {"transmittance": tr_all, "transmittance_tau": tau_all, "events": ev_all, "sigma": sg_all},
+        "timing": "median of HIP-event intervals on torch's current stream; the events figure spans both passes, "
+                  "the count pass's host synchronisation and the allocation of the output tensors",
+    }
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -18,9 +18,14 @@
 // --devices renders on a multi-GPU context over exactly these GPUs (tiles split, RCCL gather); by
 // default every visible GPU is used (one GPU: a plain single-device context).
 // --dump-rays N prints the first N primary rays (host only, no GPU) — used by the CPU tests.
+// --query RAYS.bin runs the three mixture queries of vr/query.h (MixtureQuery: transmittance_up_to,
+// intersect_events, evaluate_sigma) on the scene and prints every result with the bits of its floats. The
+// file: uint32 n_rays, uint32 n_points, then n_rays rows of 7 floats (origin, direction, tmax; the direction
+// is normalised by Ray's constructor), then n_points rows of 3 floats.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <iostream>
 #include <cmath>
 #include <numbers>
@@ -28,9 +33,48 @@
 #include <vector>
 
 #include "vr/integrator.h"
+#include "vr/query.h"
 #include "vr/gif.h"
 #include "vr/inverse_integrator.h"
 #include "vr/test_integrators.h"
+
+static uint32_t fbits(float f) {
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    return u;
+}
+
+static int run_queries(const Scene& scene, const std::string& path) {
+    std::FILE* f = std::fopen(path.c_str(), "rb");
+    if (!f) throw std::runtime_error("cannot open " + path);
+    uint32_t hdr[2] = {0, 0};
+    bool ok = std::fread(hdr, 4, 2, f) == 2;
+    std::vector<float> rows(ok ? 7 * (size_t)hdr[0] : 0), pts(ok ? 3 * (size_t)hdr[1] : 0);
+    ok = ok && std::fread(rows.data(), 4, rows.size(), f) == rows.size() && std::fread(pts.data(), 4, pts.size(), f) == pts.size();
+    std::fclose(f);
+    if (!ok) throw std::runtime_error("short query file " + path);
+    std::vector<Ray> rays;
+    std::vector<float> tmax;
+    for (uint32_t i = 0; i < hdr[0]; ++i) {
+        const float* r = &rows[7 * (size_t)i];
+        rays.emplace_back(Eigen::Vector3f(r[0], r[1], r[2]), Eigen::Vector3f(r[3], r[4], r[5]));
+        tmax.push_back(r[6]);
+    }
+    std::vector<Eigen::Vector3f> pos;
+    for (uint32_t i = 0; i < hdr[1]; ++i) pos.emplace_back(pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]);
+    MixtureQuery q(scene);
+    std::vector<float> tau;
+    const std::vector<float> tr = q.transmittance_up_to(rays, tmax, &tau);
+    for (size_t i = 0; i < tr.size(); ++i) std::printf("tr %zu %08x %08x\n", i, fbits(tr[i]), fbits(tau[i]));
+    const auto events = q.intersect_events(rays);
+    for (size_t i = 0; i < events.size(); ++i)
+        for (const PrimitiveHitEvent& e : events[i]) std::printf("ev %zu %08x %zu %d\n", i, fbits(e.t), e.index, e.entering ? 1 : 0);
+    std::vector<float> sa, ss;
+    std::vector<uint32_t> na;
+    q.evaluate_sigma(pos, sa, ss, &na);
+    for (size_t i = 0; i < sa.size(); ++i) std::printf("sigma %zu %08x %08x %u\n", i, fbits(sa[i]), fbits(ss[i]), na[i]);
+    return 0;
+}
 
 static Eigen::Vector3f parse3(const char* s) {
     float a = 0, b = 0, c = 0;
@@ -49,7 +93,7 @@ int main(int argc, char** argv) try {
     int inverse = 0, stoch = 4, final_spp = 0;
     uint64_t seed = 0;
     float lr = 1e-2f;
-    std::string ref_path, sfd_out, gif_path;
+    std::string ref_path, sfd_out, gif_path, query_path;
     int frames = 120;
     float fps = 30.0f;
     Eigen::Vector3f pos(0, 1, 6), lookat(0, 1, 0);
@@ -74,6 +118,7 @@ int main(int argc, char** argv) try {
         else if (a == "--out") out = next();
         else if (a == "--dump-rays") dump = std::atoi(next());
         else if (a == "--record") record = true;
+        else if (a == "--query") query_path = next();
         else if (a == "--gif") gif_path = next();
         else if (a == "--frames") frames = std::atoi(next());
         else if (a == "--fps") fps = std::strtof(next(), nullptr);
@@ -128,6 +173,8 @@ int main(int argc, char** argv) try {
         }
         return 0;
     }
+
+    if (!query_path.empty()) return run_queries(scene, query_path);
 
     if (!gif_path.empty()) {  // main.cpp:81-114
         const float radius = 6.0f, height_pos = 1.0f;
