@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "vr_dev_common.h"
+#include "vr_walk.h"
 
 namespace vr {
 namespace dev {
@@ -352,7 +353,6 @@ __device__ __forceinline__ void shadow_leaf(const RenderArgs& A, const Ray& r, f
         }
     }
 }
-__device__ __forceinline__ float shadow_prune_lim(float tmax) { return tmax + kTPad * (1.0f + fminf(tmax, 1e30f)); }
 
 __device__ __forceinline__ float transmittance_up_to(const RenderArgs& A, const Ray& r, float tmax, int* stack, int stride) {
     if (!(tmax > 0.0f)) return 1.0f;
@@ -389,14 +389,7 @@ constexpr int kCollectQueue = 8, kCollectSteps = VR_COLLECT_STEPS, kSmCollectSte
 template <typename Prune, typename Prim, typename Cnt>
 __device__ __forceinline__ bool collect_walk(const RenderArgs& A, const Ray& r0, int* stack, int* ring, Prune prune,
                                              Prim prim, Cnt* cnt) {
-    float ox = r0.ox, oy = r0.oy, oz = r0.oz;
-    node_space<true>(A, ox, oy, oz);
-    auto inv = [&](float d) {
-        d *= A.hn_scale;
-        return __frcp_rn(fabsf(d) > 1e-30f ? d : copysignf(1e-30f, d));
-    };
-    const float ix = inv(r0.dx), iy = inv(r0.dy), iz = inv(r0.dz);
-    const float oxi = ox * ix, oyi = oy * iy, ozi = oz * iz;
+    const auto [ix, iy, iz, oxi, oyi, ozi] = wide_slab(A, r0);
     int sp = 0, node = 0, qh = 0, qn = 0;
     uint32_t j = 0, end = 0;
     bool ovf = false;
@@ -1384,9 +1377,10 @@ __global__ void __launch_bounds__(kFFBlock) ff_fallback_kernel(RenderArgs A) {
 }
 
 // Traces the launch's queued shadow rays (the walk of transmittance_up_to on the 4-wide tree, the
-// same double sum and early stop) as a persistent while-while kernel: a lane whose ray is done takes
-// the next queued ray, claimed per wave once ff_nee_refill lanes are idle, so a wave never waits for
-// its longest ray. Each ray's contribution m * Li replaces its weight m in place.
+// same double sum and early stop) as an operation on the persistent ray-queue walk (ray_queue_walk,
+// vr_walk.h): a lane whose ray is done takes the next queued ray, claimed per wave once ff_nee_refill
+// lanes are idle, so a wave never waits for its longest ray. Each ray's contribution m * Li replaces
+// its weight m in place.
 __device__ __forceinline__ void nee_finish(const RenderArgs& A, uint32_t id, float tmax, float Tr) {
     float4& c = A.ff_nee[3 * (size_t)id + 2];
     const float4 m = c;
@@ -1398,138 +1392,51 @@ __device__ __forceinline__ void nee_finish(const RenderArgs& A, uint32_t id, flo
 #ifndef VR_NEE_BLOCKS
 #define VR_NEE_BLOCKS 4  // resident 256-lane blocks per CU
 #endif
-// A wave iteration is either a NODE iteration (lanes with room in their leaf FIFO take up to
-// kNeeSteps 4-wide node steps, leaf children queued near-first) or a PRIM iteration (lanes with queued leaves test up to kNeeSteps
-// Gaussians), whichever more lanes can use, so node and primitive work no longer split a wave. The
-// FIFO hands leaves out in the order the walk reaches them, so the double sum adds the same terms in
-// the same order as transmittance_up_to (bit-identical Tr; a sum stopped mid-leaf is >= 104 either way).
 #ifndef VR_NEE_STEPS
 #define VR_NEE_STEPS 4  // node steps / primitives per lane per wave iteration of the shadow-ray kernel
 #endif
 constexpr int kNeeQueue = 8, kNeeSteps = VR_NEE_STEPS;
+// The leaf FIFO hands leaves out in the order the walk reaches them, so the double sum adds the same terms in
+// the same order as transmittance_up_to (bit-identical Tr; a sum stopped mid-leaf is >= 104 either way).
+template <bool CNT>
+struct NeeOp {
+    static constexpr bool kPrune = true;
+    FFCount<CNT> C;
+    double sum;
+    __device__ __forceinline__ int load(const RenderArgs& A, uint32_t id, Ray& r, float& tmax) {
+        const float4 a = A.ff_nee[3 * (size_t)id], b = A.ff_nee[3 * (size_t)id + 1];
+        r = Ray{a.x, a.y, a.z, b.x, b.y, b.z};
+        tmax = a.w;
+        if (!(tmax > 0.0f)) return kRayFinish;  // Tr = 1
+        C.add(kNeeRays);
+        return kRayWalk;
+    }
+    __device__ __forceinline__ void reset() { sum = 0.0; }
+    __device__ __forceinline__ bool prim(const RenderArgs& A, const Ray& r, float tmax, uint32_t j) {
+        shadow_leaf(A, r, tmax, j, 1u, sum, &C);
+        return sum < 104.0;  // expf(-x) == 0 in f32 for x >= 104: later terms cannot change Tr
+    }
+    __device__ __forceinline__ void on_node() { C.add(kNeeNode4); }
+    // transmittance_up_to itself: traverse_wide if the scene has the 4-wide tree, then the pair tree
+    __device__ __forceinline__ void redo(const RenderArgs& A, uint32_t id, const Ray& r, float tmax, float, int* stack) {
+        nee_finish(A, id, tmax, transmittance_up_to(A, r, tmax, stack, kFFBlock));
+    }
+    __device__ __forceinline__ void finish(const RenderArgs& A, uint32_t id, float tmax) {
+        nee_finish(A, id, tmax, expf(-(float)sum));
+    }
+    __device__ __forceinline__ void invalid(uint32_t) {}
+};
+
 template <bool CNT = false>
 __global__ void __launch_bounds__(kFFBlock) ff_nee_kernel(RenderArgs A) {
-    FFCount<CNT> C;
     __shared__ int s_stack[(kStackSize + kNeeQueue) * kFFBlock];
     int* stack = s_stack + threadIdx.x;
-    int* ring = stack + kStackSize * kFFBlock;
-    const uint32_t n = min(A.ff_nee_n[0], A.ff_nee_cap);
-    const uint32_t lane = threadIdx.x & 63u;
-    bool live = false, exhausted = false;
-    uint32_t id = 0;
-    Ray r{};
-    float tmax = 0.0f, lim = 0.0f, ix = 0.0f, iy = 0.0f, iz = 0.0f, oxi = 0.0f, oyi = 0.0f, ozi = 0.0f;
-    double sum = 0.0;
-    int sp = 0, node = -1, qh = 0, qn = 0;
-    uint32_t j = 0, end = 0;  // primitives of the leaf being tested
-    bool redo = false;        // the 4-wide stack could overflow: whole walk at the end (pair-tree fallback)
-    for (;;) {
-        const uint64_t idle = __ballot(!live);
-        if (!exhausted && (idle == ~0ull || __popcll(idle) >= A.ff_nee_refill)) {
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(A.ff_nee_n + 1, (uint32_t)__popcll(idle));
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            exhausted = base + (uint32_t)__popcll(idle) >= n;
-            if (!live) {
-                id = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-                if (id < n) {
-                    const float4 a = A.ff_nee[3 * (size_t)id], b = A.ff_nee[3 * (size_t)id + 1];
-                    r = Ray{a.x, a.y, a.z, b.x, b.y, b.z};
-                    tmax = a.w;
-                    if (!(tmax > 0.0f)) {
-                        nee_finish(A, id, tmax, 1.0f);
-                    } else {
-                        float ox = r.ox, oy = r.oy, oz = r.oz;
-                        node_space<true>(A, ox, oy, oz);
-                        auto inv = [&](float d) {
-                            d *= A.hn_scale;
-                            return __frcp_rn(fabsf(d) > 1e-30f ? d : copysignf(1e-30f, d));
-                        };
-                        ix = inv(r.dx), iy = inv(r.dy), iz = inv(r.dz);
-                        oxi = ox * ix, oyi = oy * iy, ozi = oz * iz;
-                        lim = shadow_prune_lim(tmax);
-                        sum = 0.0;
-                        sp = 0;
-                        qh = qn = 0;
-                        j = end = 0;
-                        // no 4-wide tree (VR_OPT_HALF_NODES = 0 or f32 boxes): the ray goes straight to the
-                        // pair-tree walk of transmittance_up_to at its completion
-                        redo = A.hnodes4 == nullptr;
-                        node = redo ? -1 : 0;
-                        live = true;
-                        C.add(kNeeRays);
-                    }
-                }
-            }
-        }
-        if (!__any(live)) {
-            if (exhausted) break;
-            continue;
-        }
-        const bool has_prim = live && (j < end || qn > 0);
-        const bool can_node = live && node >= 0 && qn <= kNeeQueue - 4;
-        const int np = __popcll(__ballot(has_prim)), nn = __popcll(__ballot(can_node));
-        if (nn == 0 || (np > 0 && np >= nn)) {  // PRIM iteration
-            bool go = has_prim;
-            for (int k = 0; k < kNeeSteps; ++k) {
-                if (go) {
-                    if (j == end) {
-                        const int32_t ref = ring[qh * kFFBlock];
-                        qh = (qh + 1) & (kNeeQueue - 1);
-                        --qn;
-                        j = leaf_first(ref);
-                        end = j + leaf_count(ref);
-                    }
-                    shadow_leaf(A, r, tmax, j, 1u, sum, &C);
-                    ++j;
-                }
-                go = go && (j < end || qn > 0) && sum < 104.0;
-            }
-        } else {  // NODE iteration
-            bool go = can_node;
-            for (int k = 0; k < kNeeSteps; ++k) {
-                if (go) {
-                    C.add(kNeeNode4);
-                    float key[4];
-                    int32_t kr[4];
-                    wide_children(A, node, ix, iy, iz, oxi, oyi, ozi, [&](float tmin, float) { return tmin <= lim; }, key, kr);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)  // leaves, near first
-                        if (kr[i] < 0) {
-                            ring[((qh + qn) & (kNeeQueue - 1)) * kFFBlock] = kr[i];
-                            ++qn;
-                        }
-                    int first = -1;
-                    int32_t next = 0;
-#pragma unroll
-                    for (int i = 3; i >= 0; --i) {
-                        first = kr[i] > 0 ? i : first;
-                        next = kr[i] > 0 ? kr[i] : next;
-                    }
-                    if (sp + 3 > kStackSize) {
-                        redo = true;
-                        node = -1;
-                    } else {
-#pragma unroll
-                        for (int i = 3; i >= 0; --i)
-                            if (kr[i] > 0 && i != first) stack[(sp++) * kFFBlock] = kr[i];
-                        if (first >= 0) node = next;
-                        else if (sp > 0) node = stack[(--sp) * kFFBlock];
-                        else node = -1;
-                    }
-                }
-                go = go && node >= 0 && qn <= kNeeQueue - 4;
-            }
-        }
-        if (live && (redo || !(sum < 104.0) || (node < 0 && j == end && qn == 0))) {
-            const float Tr = redo ? transmittance_up_to(A, r, tmax, stack, kFFBlock) : expf(-(float)sum);
-            nee_finish(A, id, tmax, Tr);
-            live = false;
-        }
-    }
+    NeeOp<CNT> op{};
+    ray_queue_walk<kNeeQueue, kNeeSteps>(A, min(A.ff_nee_n[0], A.ff_nee_cap), A.ff_nee_n + 1, A.ff_nee_refill, stack,
+                                         stack + kStackSize * kFFBlock, kFFBlock, op);
     if constexpr (CNT) {
         Ctr c{};
-        for (int i = 0; i < kFFNumCtr; ++i) c.v[i] = C.v[i];
+        for (int i = 0; i < kFFNumCtr; ++i) c.v[i] = op.C.v[i];
         flush_counters(A.work + 8, c);
     }
 }

@@ -539,6 +539,24 @@ __device__ __forceinline__ void wide_children(const RenderArgs& A, int node, flo
     }
 }
 
+// The slab constants wide_children takes, for a ray in world coordinates: 1/d in the nodes' normalised
+// coordinates and origin * 1/d.
+struct WideSlab {
+    float ix, iy, iz, oxi, oyi, ozi;
+};
+__device__ __forceinline__ WideSlab wide_slab(const RenderArgs& A, const Ray& r) {
+    float ox = r.ox, oy = r.oy, oz = r.oz;
+    node_space<true>(A, ox, oy, oz);
+    // |d| clamped away from 0 (axis-parallel rays, e.g. an orthographic camera looking along an
+    // axis): the fma slab form b/d - o/d must never see inf - inf
+    auto inv = [&](float d) {
+        d *= A.hn_scale;
+        return __frcp_rn(fabsf(d) > 1e-30f ? d : copysignf(1e-30f, d));
+    };
+    const float ix = inv(r.dx), iy = inv(r.dy), iz = inv(r.dz);
+    return {ix, iy, iz, ox * ix, oy * iy, oz * iz};
+}
+
 // Stack traversal of the 4-wide half-precision tree (HNode4) with the generic traverse's
 // contract (prune / leaf / on_node); leaves are handled near-first as a node's children are
 // reached, the nearest inner child is walked next and the others pushed far-first. Returns false
@@ -551,16 +569,7 @@ template <int CAP, typename Prune, typename Leaf, typename OnNode = NoCount, boo
 __device__ __forceinline__ bool traverse_wide(const RenderArgs& A, const Ray& r0, int* stack, int stride, Prune prune,
                                               Leaf leaf, OnNode on_node = OnNode()) {
     [[maybe_unused]] volatile int deep[DEEP > 0 ? DEEP : 1];
-    float ox = r0.ox, oy = r0.oy, oz = r0.oz;
-    node_space<true>(A, ox, oy, oz);
-    // |d| clamped away from 0 (axis-parallel rays, e.g. an orthographic camera looking along an
-    // axis): the fma slab form b/d - o/d must never see inf - inf
-    auto inv = [&](float d) {
-        d *= A.hn_scale;
-        return __frcp_rn(fabsf(d) > 1e-30f ? d : copysignf(1e-30f, d));
-    };
-    const float ix = inv(r0.dx), iy = inv(r0.dy), iz = inv(r0.dz);
-    const float oxi = ox * ix, oyi = oy * iy, ozi = oz * iz;
+    const auto [ix, iy, iz, oxi, oyi, ozi] = wide_slab(A, r0);
     int sp = 0;
     int node = 0;
     for (;;) {

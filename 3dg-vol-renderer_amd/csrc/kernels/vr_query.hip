@@ -13,18 +13,17 @@
 // terms is exact, so a result does not depend on the order in which a tree hands the Gaussians out:
 // VR_OPT_HALF_NODES / VR_OPT_DEVICE_BVH change the walk, not the answer.
 //
-// Ray walks (transmittance, events) are the shadow-ray kernel's scheme (ff_nee_kernel, vr_freeflight.hip): a
-// persistent grid, one ray per lane, a wave claims new rays by ballot once enough of its lanes are idle, and
-// each wave iteration is a NODE iteration (4-wide node steps, leaf children into an LDS FIFO) or a PRIM
-// iteration (Gaussians of the queued leaves), whichever more lanes can use. A walk whose LDS stack could
-// overflow, and every walk of a scene without the 4-wide tree (VR_OPT_HALF_NODES = 0, or boxes too small for
-// f16), is redone on the child-pair tree at the ray's completion.
+// Ray walks (transmittance, events) are operations on the persistent ray-queue walk the shadow-ray kernel
+// uses too (ray_queue_walk, vr_walk.h): a walk whose LDS stack could overflow, and every walk of a scene without
+// the 4-wide tree (VR_OPT_HALF_NODES = 0, or boxes too small for f16), is redone on the child-pair tree at the
+// ray's completion.
 #include <hipcub/hipcub.hpp>
 #include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 
 #include "vr_dev_common.h"
+#include "vr_walk.h"
 
 namespace vr {
 namespace dev {
@@ -35,30 +34,47 @@ constexpr int kQBlock = 256;
 #endif
 constexpr int kQQueue = 8, kQSteps = 4;  // leaf FIFO entries; node steps / Gaussians per lane per wave iteration
 
-// vr_ray row i (32 B, 16-B aligned): {origin, tmax}, {direction, unit}. The direction is normalised as the Ray
-// constructor does (make_ray, ray.h:11-12) unless `unit` says it already was (a Ray object's: normalising
-// twice would move it by an ulp). False: a non-finite origin, or a direction whose squared norm is 0, NaN or
-// infinite.
-__device__ __forceinline__ bool load_query_ray(const vr_ray* __restrict__ rays, uint32_t id, Ray& r, float& tmax) {
-    const float4* p = reinterpret_cast<const float4*>(rays) + 2 * (size_t)id;
-    const float4 a = p[0], b = p[1];
-    tmax = a.w;
-    const float s = dot3(b.x, b.y, b.z, b.x, b.y, b.z);
-    const bool ok = isfinite(a.x) && isfinite(a.y) && isfinite(a.z) && s > 0.0f && isfinite(s);
-    r = b.w != 0.0f ? Ray{a.x, a.y, a.z, b.x, b.y, b.z} : make_ray(a.x, a.y, a.z, b.x, b.y, b.z);
-    return ok;
-}
-
-// ---- per-ray operations of the walk ----
-// Op: kPrune (children beyond tmax are skipped; rays with tmax <= 0 / NaN finish at once), reset(),
-// prim(A, r, tmax, j) for record j (false: the ray is done), finish(id), invalid(id).
+// ---- per-ray operations of the walk (ray_queue_walk's Op) ----
+// What the three share. vr_ray row i (32 B, 16-B aligned): {origin, tmax}, {direction, unit}. The direction is
+// normalised as the Ray constructor does (make_ray, ray.h:11-12) unless `unit` says it already was (a Ray
+// object's: normalising twice would move it by an ulp). Invalid: a non-finite origin, or a direction whose
+// squared norm is 0, NaN or infinite. PRUNE: rays with tmax <= 0 / NaN finish at once.
+template <class Op, bool PRUNE>
+struct QueryOp {
+    static constexpr bool kPrune = PRUNE;
+    const vr_ray* __restrict__ rays;
+    __device__ __forceinline__ int load(const RenderArgs& A, uint32_t id, Ray& r, float& tmax) {
+        const float4* p = reinterpret_cast<const float4*>(rays) + 2 * (size_t)id;
+        const float4 a = p[0], b = p[1];
+        tmax = a.w;
+        const float s = dot3(b.x, b.y, b.z, b.x, b.y, b.z);
+        const bool ok = isfinite(a.x) && isfinite(a.y) && isfinite(a.z) && s > 0.0f && isfinite(s);
+        r = b.w != 0.0f ? Ray{a.x, a.y, a.z, b.x, b.y, b.z} : make_ray(a.x, a.y, a.z, b.x, b.y, b.z);
+        if (!ok) return kRayInvalid;
+        return (PRUNE && !(tmax > 0.0f)) || A.num_prims <= 0 ? kRayFinish : kRayWalk;  // gmm.h:518-519 / :462: no walk
+    }
+    __device__ __forceinline__ void on_node() {}
+    // The whole walk of the ray on the child-pair tree (half-precision nodes if the scene has them), and its result.
+    __device__ __forceinline__ void redo(const RenderArgs& A, uint32_t id, const Ray& r, float tmax, float lim, int* stack) {
+        Op& op = static_cast<Op&>(*this);
+        op.reset();
+        auto prune = [&](float tmin, float) { return !PRUNE || tmin <= lim; };
+        auto leaf = [&](uint32_t first, uint32_t count) {
+            for (uint32_t j = first; j < first + count; ++j)
+                if (!op.prim(A, r, tmax, j)) return false;
+            return true;
+        };
+        if (A.hnodes) traverse<true>(A, r, stack, kQBlock, prune, leaf);
+        else traverse<false>(A, r, stack, kQBlock, prune, leaf);
+        op.finish(A, id, tmax);
+    }
+};
 
 // gmm.h:539-551: a = max(0, t_enter), b = min(tmax, t_exit), optical_depth(a, b) added if b > a.
 // TAU: the caller wants the optical depth itself, so the sum runs to the end; otherwise it stops at 104,
 // where expf(-x) is 0 in f32 whatever follows (the shadow kernel's early-out: the same Tr bit for bit).
 template <bool TAU>
-struct TransOp {
-    static constexpr bool kPrune = true;
+struct TransOp : QueryOp<TransOp<TAU>, true> {
     float* tr;
     float* tau;
     double sum;
@@ -74,7 +90,7 @@ struct TransOp {
         }
         return TAU ? true : sum < 104.0;
     }
-    __device__ __forceinline__ void finish(uint32_t id) {
+    __device__ __forceinline__ void finish(const RenderArgs&, uint32_t id, float) {
         tr[id] = expf(-(float)sum);
         if constexpr (TAU) tau[id] = (float)sum;
     }
@@ -85,8 +101,7 @@ struct TransOp {
 };
 
 // gmm.h:482-485: an entry event if t_enter >= 0, an exit event if t_exit >= 0.
-struct EventCountOp {
-    static constexpr bool kPrune = false;
+struct EventCountOp : QueryOp<EventCountOp, false> {
     uint32_t* counts;
     uint32_t cnt;
     __device__ __forceinline__ void reset() { cnt = 0; }
@@ -96,7 +111,7 @@ struct EventCountOp {
         if (intersect(quad(g, r), t0, t1)) cnt += (t0 >= 0.0f ? 1u : 0u) + (t1 >= 0.0f ? 1u : 0u);
         return true;
     }
-    __device__ __forceinline__ void finish(uint32_t id) { counts[id] = cnt; }
+    __device__ __forceinline__ void finish(const RenderArgs&, uint32_t id, float) { counts[id] = cnt; }
     __device__ __forceinline__ void invalid(uint32_t id) { counts[id] = 0; }
 };
 
@@ -104,12 +119,16 @@ struct EventCountOp {
 // t + 0.0f (-0 becomes +0; every t is >= 0, so the bits order as unsigned integers), low word
 // scene_index << 1 | exiting. Sorted per ray, events with equal t therefore come in scene order, a
 // Gaussian's entry before its exit, whatever order the tree produced them in.
-struct EventFillOp {
-    static constexpr bool kPrune = false;
+struct EventFillOp : QueryOp<EventFillOp, false> {
     const uint32_t* offsets;
     unsigned long long* keys;
     unsigned long long cap;
     uint32_t base, room, w;
+    __device__ __forceinline__ int load(const RenderArgs& A, uint32_t id, Ray& r, float& tmax) {
+        base = offsets[id];
+        room = offsets[id + 1] - base;
+        return QueryOp::load(A, id, r, tmax);
+    }
     __device__ __forceinline__ void reset() { w = 0; }
     __device__ __forceinline__ void put(float t, uint32_t low) {
         // (room: the count pass's number for this ray; cap: the caller's buffers. Neither is ever passed.)
@@ -127,198 +146,52 @@ struct EventFillOp {
         }
         return true;
     }
-    __device__ __forceinline__ void finish(uint32_t) {}
+    __device__ __forceinline__ void finish(const RenderArgs&, uint32_t, float) {}
     __device__ __forceinline__ void invalid(uint32_t) {}
 };
 
-// The whole walk of one ray on the child-pair tree (half-precision nodes if the scene has them).
+// One block of the persistent grid: its LDS stack and leaf FIFO, then the walk.
 template <class Op>
-__device__ __forceinline__ void pair_walk(const RenderArgs& A, const Ray& r, float tmax, float lim, int* stack, Op& op) {
-    auto prune = [&](float tmin, float) { return !Op::kPrune || tmin <= lim; };
-    auto leaf = [&](uint32_t first, uint32_t count) {
-        for (uint32_t j = first; j < first + count; ++j)
-            if (!op.prim(A, r, tmax, j)) return false;
-        return true;
-    };
-    if (A.hnodes) traverse<true>(A, r, stack, kQBlock, prune, leaf);
-    else traverse<false>(A, r, stack, kQBlock, prune, leaf);
+__device__ __forceinline__ void query_walk(const RenderArgs& A, uint32_t n, uint32_t* next, int refill, Op& op) {
+    __shared__ int s_stack[(kStackSize + kQQueue) * kQBlock];
+    int* stack = s_stack + threadIdx.x;
+    ray_queue_walk<kQQueue, kQSteps>(A, n, next, refill, stack, stack + kStackSize * kQBlock, kQBlock, op);
 }
-
-template <class Op>
-__device__ __forceinline__ void query_walk(const RenderArgs& A, const vr_ray* __restrict__ rays, uint32_t n,
-                                           uint32_t* __restrict__ next, int refill, int* stack, int* ring, Op& op) {
-    const uint32_t lane = threadIdx.x & 63u;
-    bool live = false, exhausted = false;
-    uint32_t id = 0;
-    Ray r{};
-    float tmax = 0.0f, lim = 0.0f, ix = 0.0f, iy = 0.0f, iz = 0.0f, oxi = 0.0f, oyi = 0.0f, ozi = 0.0f;
-    int sp = 0, node = -1, qh = 0, qn = 0;
-    uint32_t j = 0, end = 0;  // Gaussians of the leaf being tested
-    bool redo = false;        // no 4-wide tree, or its stack could overflow: the pair-tree walk at completion
-    bool stop = false;        // the operation needs no further Gaussian
-    for (;;) {
-        const uint64_t idle = __ballot(!live);
-        if (!exhausted && (idle == ~0ull || __popcll(idle) >= refill)) {
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(next, (uint32_t)__popcll(idle));
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            // (64-bit compare: the counter stays below n + 64 * waves, but base + 64 must not wrap)
-            exhausted = (uint64_t)base + (uint64_t)__popcll(idle) >= (uint64_t)n;
-            if (!live) {
-                const uint64_t mine = (uint64_t)base +
-                                      __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-                if (mine < (uint64_t)n) {
-                    id = (uint32_t)mine;
-                    op.begin(id);
-                    if (!load_query_ray(rays, id, r, tmax)) {
-                        op.invalid(id);
-                    } else if ((Op::kPrune && !(tmax > 0.0f)) || A.num_prims <= 0) {
-                        op.reset();  // gmm.h:518-519 / :462: no walk
-                        op.finish(id);
-                    } else {
-                        float ox = r.ox, oy = r.oy, oz = r.oz;
-                        node_space<true>(A, ox, oy, oz);
-                        auto inv = [&](float d) {
-                            d *= A.hn_scale;
-                            return __frcp_rn(fabsf(d) > 1e-30f ? d : copysignf(1e-30f, d));
-                        };
-                        ix = inv(r.dx), iy = inv(r.dy), iz = inv(r.dz);
-                        oxi = ox * ix, oyi = oy * iy, ozi = oz * iz;
-                        // the shadow walk's prune bound (tmax padded by a few ulp of the slab distances)
-                        lim = Op::kPrune ? tmax + kTPad * (1.0f + fminf(tmax, 1e30f)) : INFINITY;
-                        op.reset();
-                        sp = 0;
-                        qh = qn = 0;
-                        j = end = 0;
-                        stop = false;
-                        redo = A.hnodes4 == nullptr;
-                        node = redo ? -1 : 0;
-                        live = true;
-                    }
-                }
-            }
-        }
-        if (!__any(live)) {
-            if (exhausted) break;
-            continue;
-        }
-        const bool has_prim = live && !stop && (j < end || qn > 0);
-        const bool can_node = live && !stop && node >= 0 && qn <= kQQueue - 4;
-        const int np = __popcll(__ballot(has_prim)), nn = __popcll(__ballot(can_node));
-        if (nn == 0 || (np > 0 && np >= nn)) {  // PRIM iteration
-            bool go = has_prim;
-            for (int k = 0; k < kQSteps; ++k) {
-                if (go) {
-                    if (j == end) {
-                        const int32_t ref = ring[qh * kQBlock];
-                        qh = (qh + 1) & (kQQueue - 1);
-                        --qn;
-                        j = leaf_first(ref);
-                        end = j + leaf_count(ref);
-                    }
-                    stop = !op.prim(A, r, tmax, j);
-                    ++j;
-                }
-                go = go && (j < end || qn > 0) && !stop;
-            }
-        } else {  // NODE iteration
-            bool go = can_node;
-            for (int k = 0; k < kQSteps; ++k) {
-                if (go) {
-                    float key[4];
-                    int32_t kr[4];
-                    wide_children(A, node, ix, iy, iz, oxi, oyi, ozi, [&](float tmin, float) { return !Op::kPrune || tmin <= lim; },
-                                  key, kr);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)  // leaves, near first
-                        if (kr[i] < 0) {
-                            ring[((qh + qn) & (kQQueue - 1)) * kQBlock] = kr[i];
-                            ++qn;
-                        }
-                    int first = -1;
-                    int32_t nxt = 0;
-#pragma unroll
-                    for (int i = 3; i >= 0; --i) {
-                        first = kr[i] > 0 ? i : first;
-                        nxt = kr[i] > 0 ? kr[i] : nxt;
-                    }
-                    if (sp + 3 > kStackSize) {
-                        redo = true;
-                        node = -1;
-                    } else {
-#pragma unroll
-                        for (int i = 3; i >= 0; --i)
-                            if (kr[i] > 0 && i != first) stack[(sp++) * kQBlock] = kr[i];
-                        if (first >= 0) node = nxt;
-                        else if (sp > 0) node = stack[(--sp) * kQBlock];
-                        else node = -1;
-                    }
-                }
-                go = go && node >= 0 && qn <= kQQueue - 4;
-            }
-        }
-        if (live && (redo || stop || (node < 0 && j == end && qn == 0))) {
-            if (redo) {
-                op.reset();
-                pair_walk(A, r, tmax, lim, stack, op);
-            }
-            op.finish(id);
-            live = false;
-        }
-    }
-}
-
-// `begin` (per claimed ray) is only needed by the fill pass; the other operations inherit this one.
-struct NoBegin {
-    __device__ __forceinline__ void begin(uint32_t) {}
-};
-template <bool TAU>
-struct TransOpB : TransOp<TAU>, NoBegin {};
-struct EventCountOpB : EventCountOp, NoBegin {};
-struct EventFillOpB : EventFillOp {
-    __device__ __forceinline__ void begin(uint32_t id) {
-        base = offsets[id];
-        room = offsets[id + 1] - base;
-    }
-};
 
 template <bool TAU>
 __global__ void __launch_bounds__(kQBlock) query_transmittance_kernel(RenderArgs A, const vr_ray* __restrict__ rays, uint32_t n,
                                                                       float* __restrict__ tr, float* __restrict__ tau,
                                                                       uint32_t* __restrict__ next, int refill) {
-    __shared__ int s_stack[(kStackSize + kQQueue) * kQBlock];
-    int* stack = s_stack + threadIdx.x;
-    TransOpB<TAU> op;
+    TransOp<TAU> op;
+    op.rays = rays;
     op.tr = tr;
     op.tau = tau;
     op.sum = 0.0;
-    query_walk(A, rays, n, next, refill, stack, stack + kStackSize * kQBlock, op);
+    query_walk(A, n, next, refill, op);
 }
 
 __global__ void __launch_bounds__(kQBlock) query_events_count_kernel(RenderArgs A, const vr_ray* __restrict__ rays, uint32_t n,
                                                                      uint32_t* __restrict__ counts, uint32_t* __restrict__ next,
                                                                      int refill) {
-    __shared__ int s_stack[(kStackSize + kQQueue) * kQBlock];
-    int* stack = s_stack + threadIdx.x;
     if (blockIdx.x == 0 && threadIdx.x == 0) counts[n] = 0;  // the scan's last input: offsets[n] = total
-    EventCountOpB op;
+    EventCountOp op;
+    op.rays = rays;
     op.counts = counts;
     op.cnt = 0;
-    query_walk(A, rays, n, next, refill, stack, stack + kStackSize * kQBlock, op);
+    query_walk(A, n, next, refill, op);
 }
 
 __global__ void __launch_bounds__(kQBlock) query_events_fill_kernel(RenderArgs A, const vr_ray* __restrict__ rays, uint32_t n,
                                                                     const uint32_t* __restrict__ offsets,
                                                                     unsigned long long* __restrict__ keys, unsigned long long cap,
                                                                     uint32_t* __restrict__ next, int refill) {
-    __shared__ int s_stack[(kStackSize + kQQueue) * kQBlock];
-    int* stack = s_stack + threadIdx.x;
-    EventFillOpB op;
+    EventFillOp op;
+    op.rays = rays;
     op.offsets = offsets;
     op.keys = keys;
     op.cap = cap;
     op.base = op.room = op.w = 0;
-    query_walk(A, rays, n, next, refill, stack, stack + kStackSize * kQBlock, op);
+    query_walk(A, n, next, refill, op);
 }
 
 // Sorted keys -> the caller's arrays: t, and ev = scene_index << 1 | entering.
