@@ -1,0 +1,173 @@
+// The device context (vr_ctx) and what its host files share: vr_device.cpp (init / destroy, options,
+// vr_synchronize, the SFD helpers), vr_upload.cpp (vr_upload_scene), vr_frame.cpp (the frame pipelines,
+// their report and the render entry points) and vr_query_host.cpp (vr_query_*).
+#pragma once
+#include <map>
+
+#include "vr_devmem.h"
+#include "vr_kernels.h"
+
+#pragma GCC visibility push(hidden)  // internal to libvr_hip.so
+
+// Pinned report of a frame's counts, copied on the render stream after its last kernel (launch) and read
+// once ev_report has passed (collect).
+enum Report {
+    kRepFallback = 0,  // fallback-queue length (pixels re-marched)
+    kRepErrors,        // error pixels / paths (over every per-ray capacity: NaN)
+    kRepRecords,       // rec_alloc: scatter records,
+    kRepOverflowWords, //   overflow-pool words,
+    kRepExceeded,      //   record capacity exceeded (the frame is invalid and must be rendered again)
+    kRepDeep,          // deep-pass queue length
+    kRepFFFallback,    // counter 2: free-flight paths re-run in ff_fallback_kernel
+    kRepNeeNeed,       // counter 3: free-flight, the most shadow rays one launch tried to queue
+    kRepSlow,          // exact slow-path queue length
+    kRepFix,           // band fix-up queue length
+    kReportWords
+};
+
+// The active list indexes the hit buffer, so it never holds more than kFFHitCap entries: the only
+// capacity a path can exceed is kFFHitCap Gaussians overlapping one point; such a path re-runs in
+// ff_fallback_kernel with kFFBigCap-entry rows (only beyond that: error path, NaN).
+constexpr int32_t kFFHitCap = 128, kFFActCap = kFFHitCap;
+
+// 32-record chunks of the environment-ray order (A/B at C4: 8/16/32/64/128 -> 156.1/150.4/149.1/152.9/161.9 ms)
+#ifndef VR_CHUNK_SHIFT
+#define VR_CHUNK_SHIFT 5
+#endif
+
+// The uploaded scene on the device. A fresh value frees all of it (free_scene).
+struct SceneDev {
+    vr::DevBuf<vr::GaussianRecord> gauss;
+    vr::DevBuf<vr::WRecord> wrec;  // whitened copy (secondary rays)
+    bool wrec_pd = true;           // every record's M is positive definite (else the secondary rays use the M forms)
+    vr::DevBuf<vr::BVHNode> nodes;
+    vr::DevBuf<vr::HNode> hnodes;
+    vr::DevBuf<vr::HNode4> hnodes4;
+    vr::DevBuf<vr::HNode4> hnodes4s;   // the secondary rays' copy with tight boxes (VR_OPT_SEC_TIGHT)
+    vr::DevBuf<vr::HNode4> hnodes4w;   // hnodes4 laid out per axis (the 4-wide walks' node tests, wide_children)
+    vr::DevBuf<int32_t> parent4;       // parent of every HNode4 (the secondary rays' climb out of their start subtree)
+    vr::DevBuf<int32_t> prim_node4;    // the HNode4 whose child is each record's leaf (record starts)
+    vr::DevBuf<uint32_t> order;        // record (leaf order) -> scene index
+    vr::DevBuf<vr::SphereRecord> spheres;
+    size_t num_nodes = 0, num_nodes4 = 0;
+    int bvh_depth = 0;
+    float bmin[3] = {0, 0, 0}, bmax[3] = {0, 0, 0};
+    float hn_center[3] = {0, 0, 0}, hn_scale = 1.0f;
+    bool last_upload_device_bvh = false;  // the tree came from the device builder
+};
+
+struct vr_ctx {
+    int device = 0;
+    int cus = 1;  // compute units of the device (vr_init)
+    // The stream and the events come before every buffer: they are destroyed after them.
+    vr::Stream stream;  // used by the synchronous vr_render
+    vr::Event ev_start, ev_stop;
+    vr::Event ev_report;    // after the frame report's copies (collect() waits for it)
+    vr::Event ev_stage[3];  // stage boundaries of gauss_pipeline
+    // free-flight frames: per launch, events before the path kernel, after it, after the shadow-ray
+    // kernel and after the accumulation (stage_ms of vr_get_stats sums them over the frame's launches)
+    std::vector<vr::Event> ff_ev;
+    vr::PinnedBuf<uint32_t> h_report;  // kReportWords words (Report)
+    vr::PinnedBuf<uint32_t> h_sizing;  // copy of rec_alloc for the sizing march of a context's first frame
+    // scene
+    bool has_scene = false;
+    int32_t type = VR_VOLUME_GAUSSIANS;
+    int32_t num_prims = 0;
+    SceneDev scene;
+    std::vector<vr::LightRecord> lights;
+    float env[3] = {0, 0, 0};
+    // step tables keyed by step size
+    struct Table {
+        vr::DevBuf<float> d;
+        int n = 0;
+        float tmax = 0;
+    };
+    std::map<uint32_t, Table> tables;
+    // workspaces
+    vr::DevBuf<uint32_t> queue;  // [0] length, then queue_cap entries
+    uint32_t queue_cap = 0;
+    vr::DevBuf<uint32_t> counters;  // [0] error pixels / paths of the frame, [2..3] see Report
+    bool report_gauss = false;  // the last frame ran the RayMarchingGaussians pipeline (kRepRecords .. kRepExceeded)
+    uint64_t report_pixels = 0; // pixels of that frame (its march)
+    bool march_big = false;     // this scene's frames overflow the primary march's 16 slots often: kActBig (reset at upload)
+    vr::DevBuf<float> frame;    // exactly the largest frame so far
+    bool staged = false;        // last launch recorded ev_stage
+    uint32_t ff_launches = 0;
+    bool stats_pending = false;  // h_report of the last frame has not been collected yet
+    bool sync_pending = false;   // the last frame's outcome (retry / overflow) is collected but not yet reported by
+                                 // vr_synchronize: sticky, whoever collected it (vr_get_stats, an upload, ...)
+    int64_t last_pixels = 0;
+    uint32_t last_first_tile = 0, last_tile_stride = 1, last_tiles_x = 1, last_w = 0, last_h = 0;  // tile map of the last frame
+    uint32_t last_secondary_per_record = 0;
+    // wavefront pipeline buffers (grown on demand, never shrunk)
+    vr::DevBuf<uint32_t> px_first, rec_next, rec_alloc, slowq, fixq;
+    vr::DevBuf<float> px_T, tr, rec_cut;
+    vr::DevBuf<float4> rec_pos, rec_rad;
+    vr::DevBuf<uint4> rec_meta;
+    vr::DevBuf<int32_t> rec_act, stack_ovf, rec_start;
+    vr::DevBuf<unsigned long long> rec_bloom, pcg_jump, ray_next;
+    vr::DevBuf<uint16_t> env_order;
+    vr::DevBuf<uint64_t> env_base;
+    vr::DevBuf<std::byte> deep;  // march_deep_kernel: pixel queue + global active lists (vr_gauss.hip)
+    vr::DevBuf<uint32_t> bin_cnt, bin_off, bin_ent;  // tile bins of the binned march (VR_OPT_MARCH_BINNED)
+    vr::DevBuf<std::byte> ff_scratch;                // free-flight integrators (vr_freeflight.hip)
+    vr::DevBuf<float4> ff_tail, ff_nee;
+    vr::DevBuf<float> ff_sum;
+    vr::DevBuf<std::byte> ff_fb;      // ff_fallback_kernel: path queue + kFFBigCap rows
+    vr::DevBuf<uint32_t> rec_bits[2];  // RECORD_PIXEL_GAUSSIANS bitsets (vr_render_record slots)
+    uint32_t rec_npix[2] = {0, 0}, rec_n[2] = {0, 0};
+    vr::DevBuf<std::byte> sfd_tmp;     // vr_sfd_loss_diff: losses + output
+    vr::DevBuf<float> sfd_ref, sfd_loss[2];  // device inverse loop (vr_sfd_optimize): I_ref, base / perturbed losses
+    vr::DevBuf<double> sfd_out;
+    // mixture queries (vr_query_*, kernels/vr_query.hip): their own workspaces, grown on demand; nothing of a
+    // frame (report, statistics, hints) is touched by a query
+    vr::DevBuf<std::byte> q_in, q_out2;  // host forms: the batch on the device (rays / points) and its second
+    vr::DevBuf<float> q_out;             // result (tau / active counts / events), its first result
+    vr::DevBuf<uint32_t> q_off, q_cnt;          // events: offsets (host form), counts,
+    vr::DevBuf<unsigned long long> q_keys, q_keys2;  // sort keys (in / out),
+    vr::DevBuf<std::byte> q_tmp;                // scan + sort scratch
+    vr::DevBuf<std::byte> q_ctl;      // words [0..2] ray counters of the three persistent walks, [4..5] the 64-bit event total
+    bool q_count_valid = false;       // the last vr_query_events_count_device of this scene: its n and total
+    uint64_t q_count_n = 0, q_count_total = 0;
+    int pcg_jump_n = -1;
+    uint64_t rec_hint = 0, ovf_hint = 0;  // record / overflow-pool capacities (0: not known yet)
+    uint64_t slow_hint = 0;               // exact slow-path queue: the most rays an earlier frame queued (+ 1/8)
+    uint64_t fix_hint = 0;                // band fix-up queue (secondary_fix_kernel): the same
+    uint64_t nee_hint = 0;                // deferred-NEE queue capacity from earlier free-flight frames (0: not known)
+    uint32_t last_nee_cap = 0, last_nee_bound = 0;  // the last free-flight frame's queue capacity and its bound
+    // A launch found the shadow-ray queue full at its VR_OPT_FF_NEE_QUEUE bound: the frame is reported
+    // (VR_ERR_RETRY) and this context's later frames trace every shadow ray inline — the queue's own walk and
+    // sums, so the same frame bit for bit as a queue with room — until the next upload or option change.
+    bool nee_inline = false;
+    bool report_ff = false;               // the last frame ran the free-flight pipeline (kRepNeeNeed)
+    // vr_set_option values (explicit per-context tuning; no environment variables are read)
+    int64_t opt_half_nodes = 1;        // VR_OPT_HALF_NODES
+    int64_t opt_secondary_budget = 1;  // VR_OPT_SECONDARY_BUDGET
+    int64_t opt_ff_window0 = 0;        // VR_OPT_FF_WINDOW0 (0: auto_window0)
+    int32_t auto_window0 = 8;          // first hit-window capacity derived from the uploaded scene
+    int32_t auto_nee_refill = 40;      // shadow-ray kernel refill threshold derived from the uploaded scene
+    int64_t opt_ff_kernel = 0;         // VR_OPT_FF_KERNEL (0: auto_ff_sm)
+    bool auto_ff_sm = false;           // the uploaded scene's free-flight paths take the phase-scheduled kernel
+    int64_t opt_ff_nee_queue = 6;      // VR_OPT_FF_NEE_QUEUE
+    int64_t opt_device_bvh = 0;        // VR_OPT_DEVICE_BVH
+    int64_t opt_march_binned = 0;      // VR_OPT_MARCH_BINNED
+    int64_t opt_ff_solver = 0;         // VR_OPT_FF_SOLVER
+    int64_t opt_start_subtree = 1;     // VR_OPT_START_SUBTREE
+    int64_t opt_sec_tight = 1;         // VR_OPT_SEC_TIGHT (next upload)
+    int64_t opt_march_wide_min = 2048;  // VR_OPT_MARCH_WIDE_MIN
+    vr_group* group = nullptr;         // vr_init_multi: the devices this context drives (host/vr_multi.cpp)
+};
+
+namespace vr {
+
+// Single-device entry points called on a multi-GPU context act on its first device.
+inline vr_ctx* first_device(vr_ctx* c) { return (c && c->group) ? group_rank(c->group, 0) : c; }
+
+// vr_frame.cpp
+vr_status collect(vr_ctx* c);           // waits for the last frame's report and grows the capacity hints from it
+bool frame_exceeded(const vr_ctx* c);   // that frame outgrew its buffers: render it again
+// A full frame into the context's frame buffer; slot 0/1 records RECORD_PIXEL_GAUSSIANS bitsets, -1 none.
+vr_status render_frame_device(vr_ctx* c, const vr_camera* cam, const vr_render_params* p, uint32_t W, uint32_t H, int32_t slot);
+
+}  // namespace vr
+#pragma GCC visibility pop

@@ -1,0 +1,48 @@
+// Kernel launchers the host files call (defined in kernels/*.hip; kernels/vr_lbvh.hip's is in ../vr_lbvh.h).
+#pragma once
+#include "vr_common.h"
+
+namespace vr {
+
+// kernels/vr_gauss.hip
+hipError_t gauss_march(const RenderArgs& A, hipStream_t stream, bool stats);
+hipError_t gauss_secondary(const RenderArgs& A, hipStream_t stream, bool stats);
+hipError_t gauss_accumulate(const RenderArgs& A, hipStream_t stream);
+hipError_t gauss_record_cut(const RenderArgs& A, float budget, hipStream_t stream);
+hipError_t gauss_whiten(const GaussianRecord* rec, WRecord* out, uint32_t n, uint32_t* bad, hipStream_t stream);
+hipError_t gauss_bin(const RenderArgs& A, bool emit, hipStream_t stream);
+hipError_t gauss_parents(const HNode4* nodes, uint32_t n, int32_t* parent, int32_t* prim_node, hipStream_t stream);
+hipError_t gauss_soa_nodes(const HNode4* src, HNode4* dst, uint32_t n, hipStream_t stream);
+hipError_t gauss_refit_secondary(const HNode4* src, HNode4* dst, HNode4* dst_t, uint32_t n, const GaussianRecord* rec, const int32_t* parent,
+                                 uint8_t* depth, float* nbox, uint32_t* maxd, const float hc[3], float hs, float diag,
+                                 hipStream_t stream);
+hipError_t gauss_bin_scan(const uint32_t* cnt, uint32_t* off, uint32_t n, void* tmp, size_t& tmp_bytes, hipStream_t stream);
+
+// kernels/vr_freeflight.hip
+hipError_t launch_free_flight(const RenderArgs& A, uint32_t chunk_tiles, hipStream_t stream, hipEvent_t* ev);
+uint32_t free_flight_threads(int cus);
+hipError_t launch_sfd_loss_diff(const uint32_t* bits0, const uint32_t* bits1, const float* lb, const float* lp, uint32_t npix,
+                                uint32_t n, double* out, hipStream_t stream);
+hipError_t launch_pixel_losses(const float* img, const float* ref, uint32_t npix, float* out, hipStream_t stream);
+
+// kernels/vr_query.hip
+hipError_t query_transmittance(const RenderArgs& A, const vr_ray* rays, uint32_t n, float* tr, float* tau, uint32_t* next,
+                               int refill, int cus, hipStream_t s);
+hipError_t query_sigma(const RenderArgs& A, const float* xyz, uint32_t n, float* out, uint32_t* n_active, hipStream_t s);
+hipError_t query_events_count(const RenderArgs& A, const vr_ray* rays, uint32_t n, uint32_t* counts, uint32_t* offsets,
+                              unsigned long long* total, uint32_t* next, int refill, int cus, void* tmp, size_t& tmp_bytes,
+                              hipStream_t s);
+hipError_t query_events_fill(const RenderArgs& A, const vr_ray* rays, uint32_t n, const uint32_t* offsets, uint32_t total,
+                             unsigned long long* keys, unsigned long long* keys2, float* t, uint32_t* ev, uint32_t* next,
+                             int refill, int cus, void* tmp, size_t& tmp_bytes, hipStream_t s);
+hipError_t query_pack_rays(const float* o, const float* d, const float* tmax, uint32_t tmax_stride, uint32_t n, vr_ray* rays,
+                           hipStream_t s);
+
+// kernels/vr_spheres.hip
+hipError_t launch_render(const RenderArgs& A, hipStream_t stream, int volume_type, int integrator);
+hipError_t launch_unshuffle(const float* slabs, uint32_t nslabs, uint32_t tiles_per_slab, uint32_t tiles_x, uint32_t W,
+                            uint32_t H, float* img, hipStream_t stream);
+hipError_t launch_unshuffle_part(const float* slabs, uint32_t first, uint32_t nslabs, uint32_t stride, uint32_t tiles_per_slab,
+                                 uint32_t tiles_x, uint32_t W, uint32_t H, float* img, hipStream_t stream);
+
+}  // namespace vr

@@ -25,14 +25,10 @@
 #include <thread>
 #include <vector>
 
-#include "vr_common.h"
+#include "vr_devmem.h"
+#include "vr_kernels.h"
 
 using namespace vr;
-
-namespace vr {
-hipError_t launch_unshuffle_part(const float* slabs, uint32_t first, uint32_t nslabs, uint32_t stride, uint32_t tiles_per_slab,
-                                 uint32_t tiles_x, uint32_t W, uint32_t H, float* img, hipStream_t stream);
-}
 
 namespace {
 
@@ -67,15 +63,14 @@ struct Rccl {  // the RCCL entry points the group uses (rccl.h)
 
 }  // namespace
 
-struct vr_group {
+struct __attribute__((visibility("hidden"))) vr_group {
     std::vector<int> devices;
     std::vector<vr_ctx*> ranks;         // one full device context per rank
-    std::vector<hipStream_t> streams;   // per rank, on its device
-    std::vector<float*> slab;           // per rank, on its device: its packed tiles
-    size_t slab_floats = 0;
-    float* d_recv = nullptr;            // root device: the n gathered slabs
-    float* d_frame = nullptr;           // root device: the row-major frame
-    size_t recv_floats = 0, frame_floats = 0;
+    // Every stream and buffer below is freed with its own device current (group_destroy).
+    std::vector<Stream> streams;        // per rank, on its device
+    std::vector<DevBuf<float>> slab;    // per rank, on its device: its packed tiles
+    DevBuf<float> d_recv;               // root device: the n gathered slabs
+    DevBuf<float> d_frame;              // root device: the row-major frame
     bool use_rccl = false;
     Rccl rccl;
     std::vector<ncclComm_t> comms;
@@ -83,13 +78,6 @@ struct vr_group {
 };
 
 namespace {
-
-vr_status hipf(hipError_t e, const char* what) { return fail(VR_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-#define GHIP(expr, what)                          \
-    do {                                          \
-        hipError_t e_ = (expr);                   \
-        if (e_ != hipSuccess) return hipf(e_, what); \
-    } while (0)
 
 vr_status ncclf(vr_group* g, ncclResult_t r, const char* what) {
     return fail(VR_ERR_HIP, std::string(what) + ": " + (g->rccl.error_string ? g->rccl.error_string(r) : "RCCL error"));
@@ -103,15 +91,11 @@ vr_status each_rank_parallel(vr_group* g, F fn) {
     });
 }
 
-vr_status grow_dev(int dev, float** p, size_t* cap, size_t floats, const char* what) {
-    if (*p && *cap >= floats) return VR_OK;
-    GHIP(hipSetDevice(dev), "hipSetDevice");
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    GHIP(hipMalloc(p, std::max<size_t>(floats, 1) * sizeof(float)), what);
-    *cap = floats;
-    return VR_OK;
+// Room for `floats` on device `dev`: exactly that much when it has to be allocated again.
+vr_status grow_dev(int dev, DevBuf<float>& b, size_t floats, const char* what) {
+    if (b && b.count() >= floats) return VR_OK;
+    HIP_TRY(hipSetDevice(dev), "hipSetDevice");
+    return b.alloc(std::max<size_t>(floats, 1), what);
 }
 
 // One frame: the root renders its own tiles straight into the row-major frame; every other rank renders
@@ -124,39 +108,33 @@ vr_status group_frame(vr_group* g, const vr_camera* cam, const vr_render_params*
     const uint32_t nt = vr_num_tiles(W, H);
     const uint32_t per = (nt + n - 1) / n;
     const size_t slab_floats = (size_t)per * 256 * 3;
-    vr_status st;
-    for (int r = 1; r < n; ++r) {  // every other rank's slab: sized for the largest share
-        size_t cap = g->slab_floats;
-        if ((st = grow_dev(g->devices[r], &g->slab[r], &cap, slab_floats, "hipMalloc(slab)")) != VR_OK) return st;
-    }
-    g->slab_floats = std::max(g->slab_floats, slab_floats);
-    if (n > 1 && (st = grow_dev(g->devices[0], &g->d_recv, &g->recv_floats, slab_floats * (n - 1), "hipMalloc(gathered slabs)")) != VR_OK)
-        return st;
-    if ((st = grow_dev(g->devices[0], &g->d_frame, &g->frame_floats, (size_t)W * H * 3, "hipMalloc(frame)")) != VR_OK) return st;
+    for (int r = 1; r < n; ++r)  // every other rank's slab: sized for the largest share
+        VR_TRY(grow_dev(g->devices[r], g->slab[r], slab_floats, "hipMalloc(slab)"));
+    if (n > 1) VR_TRY(grow_dev(g->devices[0], g->d_recv, slab_floats * (n - 1), "hipMalloc(gathered slabs)"));
+    VR_TRY(grow_dev(g->devices[0], g->d_frame, (size_t)W * H * 3, "hipMalloc(frame)"));
     // 1) every rank renders its interleaved share (asynchronous on its own stream), each rank's ~15
     // launches issued from a host thread of its own so the ranks start together; the root's tiles land
     // in the frame itself (no copy of the root's share, no self-send)
-    st = each_rank_parallel(g, [&](int r) -> vr_status {
+    VR_TRY(each_rank_parallel(g, [&](int r) -> vr_status {
         const uint32_t count = (uint32_t)r < nt ? (nt - 1 - (uint32_t)r) / (uint32_t)n + 1 : 0;
         if (count == 0) return VR_OK;
         return vr_render_tiles_device(g->ranks[r], cam, p, W, H, (uint32_t)r, (uint32_t)n, count, r == 0 ? 0 : 1,
-                                      r == 0 ? g->d_frame : g->slab[r], g->streams[r]);
-    });
-    if (st != VR_OK) return st;
+                                      r == 0 ? g->d_frame.get() : g->slab[r].get(), g->streams[r]);
+    }));
     // 2) gather the other ranks' slabs to the root: one group of sends / receives (the links run
     // concurrently; each rank's send starts as soon as its own render is done)
     if (n > 1 && g->use_rccl) {
         ncclResult_t e = g->rccl.group_start();
         if (e != ncclSuccess) return ncclf(g, e, "ncclGroupStart");
         for (int r = 1; r < n; ++r) {
-            GHIP(hipSetDevice(g->devices[r]), "hipSetDevice");
-            e = g->rccl.send(g->slab[r], slab_floats, ncclFloat32, 0, g->comms[r], g->streams[r]);
+            HIP_TRY(hipSetDevice(g->devices[r]), "hipSetDevice");
+            e = g->rccl.send(g->slab[r].get(), slab_floats, ncclFloat32, 0, g->comms[r], g->streams[r]);
             if (e != ncclSuccess) break;
         }
         if (e == ncclSuccess) {
-            GHIP(hipSetDevice(g->devices[0]), "hipSetDevice");
+            HIP_TRY(hipSetDevice(g->devices[0]), "hipSetDevice");
             for (int r = 1; r < n && e == ncclSuccess; ++r)
-                e = g->rccl.recv(g->d_recv + (size_t)(r - 1) * slab_floats, slab_floats, ncclFloat32, r, g->comms[0],
+                e = g->rccl.recv(g->d_recv.get() + (size_t)(r - 1) * slab_floats, slab_floats, ncclFloat32, r, g->comms[0],
                                  g->streams[0]);
         }
         ncclResult_t e2 = g->rccl.group_end();
@@ -164,31 +142,31 @@ vr_status group_frame(vr_group* g, const vr_camera* cam, const vr_render_params*
         if (e2 != ncclSuccess) return ncclf(g, e2, "ncclGroupEnd");
     } else if (n > 1) {  // ranks sharing a GPU: device copies once every share is done
         for (int r = 1; r < n; ++r) {
-            GHIP(hipSetDevice(g->devices[r]), "hipSetDevice");
-            GHIP(hipStreamSynchronize(g->streams[r]), "rank render");
+            HIP_TRY(hipSetDevice(g->devices[r]), "hipSetDevice");
+            HIP_TRY(hipStreamSynchronize(g->streams[r]), "rank render");
         }
-        GHIP(hipSetDevice(g->devices[0]), "hipSetDevice");
+        HIP_TRY(hipSetDevice(g->devices[0]), "hipSetDevice");
         for (int r = 1; r < n; ++r)
-            GHIP(hipMemcpyPeerAsync(g->d_recv + (size_t)(r - 1) * slab_floats, g->devices[0], g->slab[r], g->devices[r],
+            HIP_TRY(hipMemcpyPeerAsync(g->d_recv.get() + (size_t)(r - 1) * slab_floats, g->devices[0], g->slab[r].get(), g->devices[r],
                                     slab_floats * sizeof(float), g->streams[0]),
                  "hipMemcpyPeerAsync(slab)");
     }
     // 3) unshuffle the gathered slabs (ranks 1 .. n-1) into the frame on the root and copy it out
-    GHIP(hipSetDevice(g->devices[0]), "hipSetDevice");
+    HIP_TRY(hipSetDevice(g->devices[0]), "hipSetDevice");
     if (n > 1)
-        GHIP(launch_unshuffle_part(g->d_recv, 1, (uint32_t)(n - 1), (uint32_t)n, per, (W + kTile - 1) / kTile, W, H, g->d_frame,
+        HIP_TRY(launch_unshuffle_part(g->d_recv.get(), 1, (uint32_t)(n - 1), (uint32_t)n, per, (W + kTile - 1) / kTile, W, H, g->d_frame.get(),
                                    g->streams[0]),
              "unshuffle");
-    GHIP(hipMemcpyAsync(rgb, g->d_frame, (size_t)W * H * 3 * sizeof(float), hipMemcpyDeviceToHost, g->streams[0]),
+    HIP_TRY(hipMemcpyAsync(rgb, g->d_frame.get(), (size_t)W * H * 3 * sizeof(float), hipMemcpyDeviceToHost, g->streams[0]),
          "hipMemcpyAsync(frame)");
     for (int r = 0; r < n; ++r) {
-        GHIP(hipSetDevice(g->devices[r]), "hipSetDevice");
-        GHIP(hipStreamSynchronize(g->streams[r]), "frame");
+        HIP_TRY(hipSetDevice(g->devices[r]), "hipSetDevice");
+        HIP_TRY(hipStreamSynchronize(g->streams[r]), "frame");
     }
     // 4) every rank's outcome (vr_synchronize: capacity reports, per-ray capacity errors)
     *again = false;
     for (int r = 0; r < n; ++r) {
-        st = vr_synchronize(g->ranks[r]);
+        vr_status st = vr_synchronize(g->ranks[r]);
         if (st == VR_OK) continue;
         if (st == VR_ERR_RETRY) {
             *again = true;
@@ -218,8 +196,8 @@ vr_status group_create(int ndev, const int* devices, vr_group** out) {
     }
     g->use_rccl = std::set<int>(g->devices.begin(), g->devices.end()).size() == g->devices.size();
     g->ranks.assign(ndev, nullptr);
-    g->streams.assign(ndev, nullptr);
-    g->slab.assign(ndev, nullptr);
+    g->streams.resize(ndev);
+    g->slab.resize(ndev);
     auto bail = [&](vr_status st) {
         std::string m = vr_last_error();
         group_destroy(g);
@@ -228,7 +206,7 @@ vr_status group_create(int ndev, const int* devices, vr_group** out) {
     for (int r = 0; r < ndev; ++r) {
         vr_status st = vr_init(g->devices[r], &g->ranks[r]);
         if (st != VR_OK) return bail(st);
-        if (hipSetDevice(g->devices[r]) != hipSuccess || hipStreamCreateWithFlags(&g->streams[r], hipStreamNonBlocking) != hipSuccess) {
+        if (hipSetDevice(g->devices[r]) != hipSuccess || hipStreamCreateWithFlags(g->streams[r].put(), hipStreamNonBlocking) != hipSuccess) {
             fail(VR_ERR_HIP, "vr_init_multi: stream creation failed");
             return bail(VR_ERR_HIP);
         }
@@ -263,14 +241,14 @@ void group_destroy(vr_group* g) {
         if (c && g->rccl.destroy) g->rccl.destroy(c);
     for (size_t r = 0; r < g->ranks.size(); ++r) {
         (void)hipSetDevice(g->devices[r]);
-        if (g->slab[r]) (void)hipFree(g->slab[r]);
-        if (g->streams[r]) (void)hipStreamDestroy(g->streams[r]);
+        g->slab[r].reset();
+        g->streams[r].reset();
         if (g->ranks[r]) vr_destroy(g->ranks[r]);
     }
     if (!g->devices.empty()) {
         (void)hipSetDevice(g->devices[0]);
-        if (g->d_recv) (void)hipFree(g->d_recv);
-        if (g->d_frame) (void)hipFree(g->d_frame);
+        g->d_recv.reset();
+        g->d_frame.reset();
     }
     // the RCCL library stays loaded: its runtime may hold threads and device state until exit
     delete g;
@@ -288,8 +266,7 @@ vr_status group_render(vr_group* g, const vr_camera* cam, const vr_render_params
     if (W == 0 || H == 0 || W > 65535 || H > 65535) return fail(VR_ERR_INVALID, "width/height must be in [1, 65535]");
     for (int attempt = 1;; ++attempt) {  // the same schedule as one context's render_sync (kFrameAttempts)
         bool again = false;
-        vr_status st = group_frame(g, cam, p, W, H, rgb, &again);
-        if (st != VR_OK) return st;
+        VR_TRY(group_frame(g, cam, p, W, H, rgb, &again));
         if (!again) return VR_OK;
         if (attempt >= kFrameAttempts)
             return fail(VR_ERR_OVERFLOW, "scatter-record / shadow-ray queue capacity could not be sized");
@@ -298,8 +275,7 @@ vr_status group_render(vr_group* g, const vr_camera* cam, const vr_render_params
 
 vr_status group_set_option(vr_group* g, int32_t option, int64_t value) {
     for (vr_ctx* c : g->ranks) {
-        vr_status st = vr_set_option(c, option, value);
-        if (st != VR_OK) return st;
+        VR_TRY(vr_set_option(c, option, value));
     }
     return VR_OK;
 }
@@ -322,8 +298,7 @@ vr_status group_stats(vr_group* g, vr_render_stats* o) {
     std::memset(o, 0, sizeof(*o));
     for (vr_ctx* c : g->ranks) {
         vr_render_stats s{};
-        vr_status st = vr_get_stats(c, &s);
-        if (st != VR_OK) return st;
+        VR_TRY(vr_get_stats(c, &s));
         o->kernel_ms = std::max(o->kernel_ms, s.kernel_ms);
         for (size_t i = 0; i < std::size(o->stage_ms); ++i) o->stage_ms[i] = std::max(o->stage_ms[i], s.stage_ms[i]);
         o->pixels += s.pixels;

@@ -1,0 +1,210 @@
+// Mixture queries (vr_query_*, kernels/vr_query.hip): batched transmittance, ray events and sigma.
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+
+#include "vr_ctx.h"
+
+using namespace vr;
+
+namespace {
+
+// The scene part of the kernel arguments, after the checks every query shares. `n` entries of a batch.
+vr_status query_begin(vr_ctx* c, const char* what, size_t n, RenderArgs& A) {
+    if (!c) return fail(VR_ERR_INVALID, std::string(what) + ": NULL ctx");
+    if (!c->has_scene) return fail(VR_ERR_NOSCENE, "no scene uploaded (call vr_upload_scene first)");
+    if (c->type != VR_VOLUME_GAUSSIANS) return fail(VR_ERR_UNSUPPORTED, std::string(what) + ": mixture queries need a Gaussian scene");
+    if (n >= (1ull << 31)) return fail(VR_ERR_INVALID, std::string(what) + ": more than 2^31 - 1 entries in one call");
+    HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+    std::memset(&A, 0, sizeof(A));
+    const SceneDev& sd = c->scene;
+    A.gauss = sd.gauss.get();
+    A.nodes = sd.nodes.get();
+    A.hnodes = sd.hnodes.get();
+    // the 4-wide walks read the per-axis copy, which exists whenever the 4-wide tree does (upload_parents)
+    A.hnodes4 = sd.hnodes4w ? sd.hnodes4.get() : nullptr;
+    A.hnodes4w = sd.hnodes4w.get();
+    A.num_nodes4 = (uint32_t)sd.num_nodes4;
+    for (int k = 0; k < 3; ++k) A.hn_center[k] = sd.hn_center[k];
+    A.hn_scale = sd.hn_scale;
+    A.num_prims = c->num_prims;
+    A.bvh_depth = sd.bvh_depth;
+    A.gauss_order = sd.order.get();
+    return c->q_ctl.grow(32, "hipMalloc(query counters)");
+}
+int query_refill(const vr_ctx* c) { return std::clamp<int>(c->auto_nee_refill, 1, 64); }
+bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+vr_status vr_query_transmittance_device(vr_ctx* c, const vr_ray* d_rays, size_t n, float* d_tr, float* d_tau, void* stream) {
+    c = first_device(c);
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_transmittance", n, A));
+    if (n == 0) return VR_OK;
+    if (!d_rays || !d_tr) return fail(VR_ERR_INVALID, "vr_query_transmittance: NULL argument");
+    if (!aligned16(d_rays)) return fail(VR_ERR_INVALID, "vr_query_transmittance: the device ray array must be 16-byte aligned");
+    HIP_TRY(query_transmittance(A, d_rays, (uint32_t)n, d_tr, d_tau, (uint32_t*)c->q_ctl.get(), query_refill(c), c->cus,
+                                (hipStream_t)stream),
+            "query_transmittance_kernel");
+    return VR_OK;
+}
+
+vr_status vr_query_transmittance(vr_ctx* c, const vr_ray* rays, size_t n, float* tr, float* tau) {
+    c = first_device(c);
+    RenderArgs A;
+    vr_status st = query_begin(c, "vr_query_transmittance", n, A);
+    if (st != VR_OK || n == 0) return st;
+    if (!rays || !tr) return fail(VR_ERR_INVALID, "vr_query_transmittance: NULL argument");
+    VR_TRY(c->q_in.grow(n * sizeof(vr_ray), "hipMalloc(query rays)"));
+    VR_TRY(c->q_out.grow(n, "hipMalloc(query results)"));
+    if (tau) VR_TRY(c->q_out2.grow(n * sizeof(float), "hipMalloc(query results)"));
+    HIP_TRY(hipMemcpy(c->q_in.get(), rays, n * sizeof(vr_ray), hipMemcpyHostToDevice), "hipMemcpy(query rays)");
+    VR_TRY(vr_query_transmittance_device(c, (const vr_ray*)c->q_in.get(), n, c->q_out.get(), tau ? (float*)c->q_out2.get() : nullptr,
+                                       c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream), "query_transmittance_kernel");
+    HIP_TRY(hipMemcpy(tr, c->q_out.get(), n * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    if (tau) HIP_TRY(hipMemcpy(tau, c->q_out2.get(), n * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    return VR_OK;
+}
+
+vr_status vr_query_sigma_device(vr_ctx* c, const float* d_xyz, size_t n, float* d_sigma_as, uint32_t* d_n_active, void* stream) {
+    c = first_device(c);
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_sigma", n, A));
+    if (n == 0) return VR_OK;
+    if (!d_xyz || !d_sigma_as) return fail(VR_ERR_INVALID, "vr_query_sigma: NULL argument");
+    HIP_TRY(query_sigma(A, d_xyz, (uint32_t)n, d_sigma_as, d_n_active, (hipStream_t)stream), "query_sigma_kernel");
+    return VR_OK;
+}
+
+vr_status vr_query_sigma(vr_ctx* c, const float* xyz, size_t n, float* sigma_as, uint32_t* n_active) {
+    c = first_device(c);
+    RenderArgs A;
+    vr_status st = query_begin(c, "vr_query_sigma", n, A);
+    if (st != VR_OK || n == 0) return st;
+    if (!xyz || !sigma_as) return fail(VR_ERR_INVALID, "vr_query_sigma: NULL argument");
+    VR_TRY(c->q_in.grow(n * 3 * sizeof(float), "hipMalloc(query points)"));
+    VR_TRY(c->q_out.grow(n * 2, "hipMalloc(query results)"));
+    if (n_active) VR_TRY(c->q_out2.grow(n * sizeof(uint32_t), "hipMalloc(query results)"));
+    HIP_TRY(hipMemcpy(c->q_in.get(), xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(query points)");
+    VR_TRY(vr_query_sigma_device(c, (const float*)c->q_in.get(), n, c->q_out.get(), n_active ? (uint32_t*)c->q_out2.get() : nullptr,
+                               c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream), "query_sigma_kernel");
+    HIP_TRY(hipMemcpy(sigma_as, c->q_out.get(), n * 2 * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    if (n_active) HIP_TRY(hipMemcpy(n_active, c->q_out2.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    return VR_OK;
+}
+
+vr_status vr_query_events_count_device(vr_ctx* c, const vr_ray* d_rays, size_t n, uint32_t* d_offsets, uint64_t* total) {
+    c = first_device(c);
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_events", n, A));
+    if (!total) return fail(VR_ERR_INVALID, "vr_query_events: NULL total");
+    *total = 0;
+    if (n == 0) return VR_OK;
+    if (!d_rays || !d_offsets) return fail(VR_ERR_INVALID, "vr_query_events: NULL argument");
+    if (!aligned16(d_rays)) return fail(VR_ERR_INVALID, "vr_query_events: the device ray array must be 16-byte aligned");
+    c->q_count_valid = false;
+    HIP_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");  // d_rays may come from any stream
+    VR_TRY(c->q_cnt.grow(n + 1, "hipMalloc(event counts)"));
+    uint32_t* ctl = (uint32_t*)c->q_ctl.get();
+    unsigned long long* d_total = (unsigned long long*)(ctl + 4);
+    size_t tmp_bytes = 0;
+    auto count = [&](void* tmp) {  // tmp == nullptr: only the scratch size
+        return query_events_count(A, d_rays, (uint32_t)n, c->q_cnt.get(), d_offsets, d_total, ctl + 1, query_refill(c), c->cus, tmp,
+                                  tmp_bytes, c->stream);
+    };
+    HIP_TRY(count(nullptr), "event count scratch");
+    VR_TRY(c->q_tmp.grow(tmp_bytes + 16, "hipMalloc(event scan scratch)"));
+    HIP_TRY(count(c->q_tmp.get()), "query_events_count_kernel");
+    unsigned long long tot = 0;
+    HIP_TRY(hipMemcpyAsync(&tot, d_total, sizeof(tot), hipMemcpyDeviceToHost, c->stream), "hipMemcpy(event total)");
+    HIP_TRY(hipStreamSynchronize(c->stream), "query_events_count_kernel");
+    *total = tot;
+    if (tot > 0xffffffffull) return fail(VR_ERR_INVALID, "vr_query_events: more than 2^32 - 1 events in one call (split the batch)");
+    c->q_count_valid = true;
+    c->q_count_n = n;
+    c->q_count_total = tot;
+    return VR_OK;
+}
+
+vr_status vr_query_events_fill_device(vr_ctx* c, const vr_ray* d_rays, size_t n, const uint32_t* d_offsets, float* d_t,
+                                      uint32_t* d_ev, uint64_t cap, void* stream) {
+    c = first_device(c);
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_events", n, A));
+    if (n == 0) return VR_OK;
+    if (!d_rays || !d_offsets) return fail(VR_ERR_INVALID, "vr_query_events: NULL argument");
+    if (!aligned16(d_rays)) return fail(VR_ERR_INVALID, "vr_query_events: the device ray array must be 16-byte aligned");
+    if (!c->q_count_valid || c->q_count_n != n)
+        return fail(VR_ERR_INVALID, "vr_query_events_fill_device: no vr_query_events_count_device call for this many rays preceded it");
+    const uint64_t tot = c->q_count_total;
+    if (cap < tot)
+        return fail(VR_ERR_OVERFLOW, "vr_query_events: " + std::to_string(tot) + " events, room for " + std::to_string(cap));
+    if (tot == 0) return VR_OK;
+    if (!d_t || !d_ev) return fail(VR_ERR_INVALID, "vr_query_events: NULL argument");
+    VR_TRY(c->q_keys.grow(tot, "hipMalloc(event keys)"));
+    VR_TRY(c->q_keys2.grow(tot, "hipMalloc(event keys)"));
+    uint32_t* ctl = (uint32_t*)c->q_ctl.get();
+    size_t tmp_bytes = 0;
+    auto fill = [&](void* tmp) {  // tmp == nullptr: only the scratch size
+        return query_events_fill(A, d_rays, (uint32_t)n, d_offsets, (uint32_t)tot, c->q_keys.get(), c->q_keys2.get(), d_t, d_ev,
+                                 ctl + 2, query_refill(c), c->cus, tmp, tmp_bytes, (hipStream_t)stream);
+    };
+    HIP_TRY(fill(nullptr), "event sort scratch");
+    VR_TRY(c->q_tmp.grow(tmp_bytes + 16, "hipMalloc(event sort scratch)"));
+    HIP_TRY(fill(c->q_tmp.get()), "query_events_fill_kernel");
+    return VR_OK;
+}
+
+vr_status vr_query_events(vr_ctx* c, const vr_ray* rays, size_t n, uint32_t* offsets, float* t, uint32_t* ev, uint64_t cap,
+                          uint64_t* total) {
+    c = first_device(c);
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_events", n, A));
+    if (!total) return fail(VR_ERR_INVALID, "vr_query_events: NULL total");
+    *total = 0;
+    if (n == 0) {
+        if (offsets) offsets[0] = 0;
+        return VR_OK;
+    }
+    if (!rays || (cap > 0 && (!t || !ev)) || (cap == 0 && ((t == nullptr) != (ev == nullptr))))
+        return fail(VR_ERR_INVALID, "vr_query_events: NULL argument");
+    VR_TRY(c->q_in.grow(n * sizeof(vr_ray), "hipMalloc(query rays)"));
+    VR_TRY(c->q_off.grow(n + 1, "hipMalloc(event offsets)"));
+    HIP_TRY(hipMemcpy(c->q_in.get(), rays, n * sizeof(vr_ray), hipMemcpyHostToDevice), "hipMemcpy(query rays)");
+    VR_TRY(vr_query_events_count_device(c, (const vr_ray*)c->q_in.get(), n, c->q_off.get(), total));
+    if (offsets) HIP_TRY(hipMemcpy(offsets, c->q_off.get(), (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy(event offsets)");
+    if (cap == 0 && !t && !ev) return VR_OK;
+    const uint64_t tot = *total;
+    if (cap < tot) return fail(VR_ERR_OVERFLOW, "vr_query_events: " + std::to_string(tot) + " events, room for " + std::to_string(cap));
+    if (tot == 0) return VR_OK;
+    VR_TRY(c->q_out.grow(tot, "hipMalloc(query results)"));
+    VR_TRY(c->q_out2.grow(tot * sizeof(uint32_t), "hipMalloc(query results)"));
+    VR_TRY(vr_query_events_fill_device(c, (const vr_ray*)c->q_in.get(), n, c->q_off.get(), c->q_out.get(),
+                                     (uint32_t*)c->q_out2.get(), tot, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream), "query_events_fill_kernel");
+    HIP_TRY(hipMemcpy(t, c->q_out.get(), tot * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    HIP_TRY(hipMemcpy(ev, c->q_out2.get(), tot * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    return VR_OK;
+}
+
+vr_status vr_query_pack_rays_device(vr_ctx* c, const float* d_origins, const float* d_directions, const float* d_tmax,
+                                    uint32_t tmax_stride, size_t n, vr_ray* d_rays, void* stream) {
+    c = first_device(c);
+    if (!c) return fail(VR_ERR_INVALID, "vr_query_pack_rays_device: NULL ctx");
+    if (n == 0) return VR_OK;
+    if (!d_origins || !d_directions || !d_tmax || !d_rays || tmax_stride > 1 || n >= (1ull << 31) || !aligned16(d_rays))
+        return fail(VR_ERR_INVALID, "vr_query_pack_rays_device: bad argument");
+    HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+    HIP_TRY(query_pack_rays(d_origins, d_directions, d_tmax, tmax_stride, (uint32_t)n, d_rays, (hipStream_t)stream),
+            "query_pack_rays_kernel");
+    return VR_OK;
+}
+
+}  // extern "C"

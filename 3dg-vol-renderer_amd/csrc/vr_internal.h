@@ -152,7 +152,7 @@ struct RenderArgs {
     uint32_t bin_nb;
     float bin_dz;
     const BVHNode* nodes;
-    const HNode* hnodes;      // nullptr: the scene is not suited to half-precision boxes (see vr_device.cpp)
+    const HNode* hnodes;      // nullptr: the scene is not suited to half-precision boxes (see vr_upload.cpp)
     const HNode4* hnodes4;    // 4-wide collapse of the same tree (secondary rays); nullptr with hnodes
     const HNode4* hnodes4s;   // the secondary rays' copy with tight boxes (gauss_refit_secondary), else hnodes4
     const HNode4* hnodes4t;   // hnodes4s's nodes with the boxes laid out per axis (soa_nodes_kernel), or nullptr
@@ -171,7 +171,7 @@ struct RenderArgs {
     float step_size;
     int32_t env_samples;
     float t_eps;
-    float tau_cut;        // secondary rays: Tr := 0 once the optical depth reaches this (see vr_device.cpp)
+    float tau_cut;        // secondary rays: Tr := 0 once the optical depth reaches this (see vr_frame.cpp)
     int32_t pure;         // PureRayMarching: marched (point-sampled) transmittance, integrator.h:100-267
     const float* tsteps;  // iterated float step sequence t_k (test_integrators.h:184,289)
     int32_t num_tsteps;

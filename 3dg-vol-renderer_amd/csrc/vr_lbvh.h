@@ -1,5 +1,5 @@
 // Device BVH builder interface (kernels/vr_lbvh.hip), shared by its definition and its caller
-// (host/vr_device.cpp) so the result layout has exactly one definition.
+// (host/vr_upload.cpp) so the result layout has exactly one definition.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stddef.h>

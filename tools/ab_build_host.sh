@@ -1,9 +1,9 @@
 #!/bin/bash
 # A/B build of libvr_hip.so with host sources recompiled under extra -D flags:
-#   tools/ab_build_host.sh NAME "-DFOO=1 ..." [host files, default vr_device]  -> _ab/NAME/libvr_hip.so
+#   tools/ab_build_host.sh NAME "-DFOO=1 ..." [host files, default: the device context's four]  -> _ab/NAME/libvr_hip.so
 set -e
 cd "$(dirname "$0")/../3dg-vol-renderer_amd/csrc"
-name=$1; flags=$2; files=${3:-vr_device}
+name=$1; flags=$2; files=${3:-vr_device vr_upload vr_frame vr_query_host}
 mkdir -p ../../_ab/$name
 objs=$(ls ../build/*.o)
 new=""
