@@ -268,7 +268,7 @@ vr_status gauss_pipeline(vr_ctx* c, RenderArgs& A, hipStream_t s, bool stats) {
     }
 
     // Everything below is sized by the capacity; the kernels read the live record count on the device.
-    // Tr slots: whole record chunks (<= 64 records; hand-out order, vr_gauss.hip)
+    // Tr slots: whole record chunks (<= 64 records; hand-out order, vr_gauss_common.h rays_per_chunk)
     VR_TRY(c->tr.grow(std::max<uint64_t>((cap + 63) / 64 * 64 * S, 1), "hipMalloc(secondary)", A.tr));
     VR_TRY(c->rec_rad.grow(std::max<uint64_t>(cap, 1), "hipMalloc(record radiance)", A.rec_rad));
     // exact slow path: light rays (stopping event / missed member), the rare rays with a member at its 3-sigma
@@ -715,7 +715,7 @@ vr_status vr_debug_pixel_records(vr_ctx* c, uint32_t x, uint32_t y, float* out, 
             float* o = out + k * row;
             const float v[9] = {(float)meta.y, pos.x, pos.y, pos.z, pos.w, rad.x, rad.y, rad.z, (float)(meta.w & 0x7fffffffu)};
             std::copy(v, v + 9, o);
-            // Tr slots: hand-out order within the record's chunk (vr_gauss.hip ray_slot / tr_slot)
+            // Tr slots: hand-out order within the record's chunk (vr_gauss_common.h ray_slot / rays_per_chunk)
             const uint32_t chunk = r / cr, rl = r % cr;
             const size_t base = (size_t)chunk * cr * S;
             if (ne > 0 && c->env_order)

@@ -4,7 +4,8 @@
 
 namespace vr {
 
-// kernels/vr_gauss.hip
+// kernels/vr_gauss_*.hip, a unit per pipeline stage (kernels/vr_gauss_common.h): march (gauss_march, gauss_bin,
+// gauss_bin_scan), secondary (gauss_secondary), shade (gauss_accumulate, gauss_record_cut), tree (the others)
 hipError_t gauss_march(const RenderArgs& A, hipStream_t stream, bool stats);
 hipError_t gauss_secondary(const RenderArgs& A, hipStream_t stream, bool stats);
 hipError_t gauss_accumulate(const RenderArgs& A, hipStream_t stream);

@@ -231,7 +231,7 @@ vr_status upload_device_bvh(vr_ctx* c, const HostScene& hs, const std::vector<fl
 }
 
 // The secondary rays' 4-wide tree: the shared tree's nodes refit with the records' tight boxes on the
-// device (vr_gauss.hip, refit_kernel; whitened scenes only: the M forms keep the padded boxes).
+// device (vr_gauss_tree.hip, refit_kernel; whitened scenes only: the M forms keep the padded boxes).
 vr_status upload_secondary_tree(vr_ctx* c) {
     SceneDev& s = c->scene;
     s.hnodes4s.reset();
@@ -263,7 +263,7 @@ vr_status upload_secondary_tree(vr_ctx* c) {
 
 // Parent of every 4-wide node (built on the device from the children refs): a secondary ray starts its
 // tree walk in the subtree holding its origin and climbs to the parents once that subtree is done
-// (vr_gauss.hip, record_start_kernel / sec_node4v).
+// (vr_gauss_secondary.hip, record_start_kernel / sec_node4v).
 vr_status upload_parents(vr_ctx* c) {
     SceneDev& s = c->scene;
     s.parent4.reset();

@@ -1,4 +1,4 @@
-"""GPU: the binned primary march (VR_OPT_MARCH_BINNED, kernels/vr_gauss.hip march_binned_kernel) against
+"""GPU: the binned primary march (VR_OPT_MARCH_BINNED, kernels/vr_gauss_march.hip march_binned_kernel) against
 the BVH window-query march (march_kernel).
 
 Both marches decide every entry with the same exact intersect and evaluate every step with the same

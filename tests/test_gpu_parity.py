@@ -186,9 +186,7 @@ def _both(mean, cov, dens, alb, lpos, lint, W, H, pos=CAM_POS, vd=None, env_samp
     return img.pixels, ref, integ.last_stats
 
 
-def test_light_inside_gaussian_and_camera_inside_gaussian():
-    """Straddling Gaussians (light inside) need the 'first event past the light' stop; camera inside
-    a Gaussian starts the march with an active set at t = 0."""
+def _light_inside_scene():
     mean, cov, dens, alb = _synthetic(12, 3)
     mean = np.vstack([mean, [[0.0, 3.0, 0.0], [0.0, 1.0, 5.0]]]).astype(np.float32)
     cov = np.vstack([cov, [[0.5, 0, 0, 0.5, 0, 0.5], [0.3, 0.0, 0.0, 0.3, 0.0, 0.6]]]).astype(np.float32)
@@ -196,9 +194,36 @@ def test_light_inside_gaussian_and_camera_inside_gaussian():
     alb = np.append(alb, [0.7, 0.9]).astype(np.float32)
     lpos = np.array([[0.0, 3.1, 0.1], [2.0, 2.0, 2.0]], np.float32)
     lint = np.array([[40, 40, 40], [10, 20, 30]], np.float32)
-    got, ref, st = _both(mean, cov, dens, alb, lpos, lint, 48, 48)
+    return mean, cov, dens, alb, lpos, lint
+
+
+def test_light_inside_gaussian_and_camera_inside_gaussian():
+    """Straddling Gaussians (light inside) need the 'first event past the light' stop; camera inside
+    a Gaussian starts the march with an active set at t = 0."""
+    got, ref, st = _both(*_light_inside_scene(), 48, 48)
     err, nm = _linf(got, ref)
     assert nm == 0 and err < TOL, err
+
+
+def test_light_inside_gaussian_on_both_slow_kernels(device_options):
+    """The same scene sends every ray towards its first light to the exact slow path (the light lies inside a
+    Gaussian's 3-sigma ellipsoid). With the 4-wide half-precision tree (half_nodes 1) the queue is served by
+    secondary_slow_coop_kernel, without it (half_nodes 0) by secondary_slow_kernel (vr_gauss_exact.hip): both
+    decode the queued ray from its result slot and must match the oracle."""
+    mean, cov, dens, alb, lpos, lint = _light_inside_scene()
+    orc = O.OracleScene.from_gaussians(mean, cov, dens, alb, lpos, lint)
+    ref = O.render(orc, O.PINHOLE, CAM_POS, main_view_dir(), FOV, 48, 48, O.RAYMARCH_GAUSSIANS, 0.01, 8)
+    for half_nodes in (1, 0):
+        device_options("half_nodes", half_nodes)  # applies at the next upload: a new scene per render
+        scene = vr.Scene.from_gaussians(mean, cov, dens, alb, [vr.Light(p, i) for p, i in zip(lpos, lint)])
+        img = vr.Image(48, 48)
+        integ = vr.RayMarchingGaussians(vr.Pinhole_Camera(CAM_POS, main_view_dir(), FOV), env_samples=8)
+        integ.render(scene, img)
+        got, st = img.pixels, integ.last_stats
+        print(f"half_nodes {half_nodes}: slow_rays {st['slow_rays']}")
+        assert st["slow_rays"] > 0, half_nodes
+        err, nm = _linf(got, ref)
+        assert nm == 0 and err < TOL, (half_nodes, err)
 
 
 def test_dense_overlap_uses_fallback_path_and_still_matches():
@@ -448,11 +473,11 @@ def _tile_stratified(W, H, per_tile_stride, seed):
 # Fixed regression pixels of the C4 frame (4096^2, 1 M), from the oracle sweeps of its fallback pixels at t_eps = 0
 # (profiles/r04_c4_exact_fallback_sweep.txt, r05_c4_exact_fallback_sweep.txt): (2224, 3653) was 2.3e-3 dark until
 # round 5 (a non-member Gaussian the record position lies just outside of was summed from 0 by the secondary rays'
-# credit scheme, vr_gauss.hip wtest); (470, 3144) was 2.6e-2 bright (a member whose 3-sigma surface passes through
+# credit scheme, vr_gauss_secondary.hip wtest); (470, 3144) was 2.6e-2 bright (a member whose 3-sigma surface passes through
 # the record position: the reference's f32 test misses it, so it stays active to the last event; now the exact
 # slow path); (598, 3212) is a grazing-chord pixel (the reference's f32 quadratic collapses a chord seen from far
 # away: since round 6 the device sends a ray with a chord in that error band to the exact slow path, which collapses
-# it as the reference does, vr_gauss.hip kChordBand); the others were tangent-tie pixels on the oracle's tree before
+# it as the reference does, vr_gauss_common.h kChordBand); the others were tangent-tie pixels on the oracle's tree before
 # round 6 (held to the stable order where the reference's own tree's std::sort differs from it).
 C4_REGRESSION = [(2224, 3653), (470, 3144), (598, 3212), (3900, 202), (3702, 3557), (3700, 3551), (1551, 3645),
                  (3322, 641), (2198, 1218), (194, 490), (1241, 712), (2363, 3017)]

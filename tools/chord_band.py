@@ -1,5 +1,5 @@
 """Error band of the reference's f32 ray/3-sigma-ellipsoid discriminant (gaussian.h:137-151) in whitened units, which
-sizes the secondary rays' chord band (vr_gauss.hip kChordBand). Gaussians of the make_random distribution
+sizes the secondary rays' chord band (vr_gauss_common.h kChordBand). Gaussians of the make_random distribution
 (diameters U(0.01, 0.035), Haar rotations), origins 0.01-3 units away, rays aimed to graze: the f32 discriminant
 B*B - 4*A*C (Eigen's evaluation order) divided by 4A against the exact D = 9 - e2 (double, same f32 M, p, d), in
 units of eps * c (eps = 2^-23, c = p.M.p). CPU only: python3 tools/chord_band.py"""

@@ -1,6 +1,6 @@
 """C4 ray-march diagnostics for A/B builds: frame / stage times of the product schedule plus the
 instrumented counters of one frame (VR_LIB_PATH picks the library; diagnostic builds reuse the
-secondary counter slots, see VR_DIAG_CYCLES / VR_DIAG_WAVE_UTIL in kernels/vr_gauss.hip).
+secondary counter slots, see VR_DIAG_CYCLES / VR_DIAG_WAVE_UTIL in kernels/vr_gauss_secondary.hip).
 
   python3 tools/diag_c4.py [--size 4096] [--frames 3] [--counts 1]
 Prints one JSON line."""

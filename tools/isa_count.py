@@ -1,7 +1,7 @@
 """Static ISA census of one kernel: instructions per source function, by class (VALU / SALU /
 VMEM / SMEM / LDS / branch), from the disassembly of a device code object built with line tables.
 
-  hipcc ... -gline-tables-only --cuda-device-only -c kernels/vr_gauss.hip -o x.co
+  hipcc ... -gline-tables-only --cuda-device-only -c kernels/vr_gauss_secondary.hip -o x.co
   clang-offload-bundler --unbundle --type=o --input=x.co --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --output=x.o
   llvm-objdump -d x.o > x.s
   python3 tools/isa_count.py x.o x.s secondary_ww_kernelILi256ELi18ELb0ELb0ELi6ELi9ELb1ELb1E [--top 30]

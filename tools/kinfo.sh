@@ -1,6 +1,6 @@
 #!/bin/bash
 # Register / spill / LDS census of the device kernels of one source under extra -D flags:
-#   tools/kinfo.sh vr_gauss "-DFOO=1" [kernel-name-regex]
+#   tools/kinfo.sh vr_gauss_secondary "-DFOO=1" [kernel-name-regex]
 set -e
 cd "$(dirname "$0")/../3dg-vol-renderer_amd/csrc"
 k=$1; flags=$2; pat=${3:-secondary_ww_kernel}

@@ -1,6 +1,6 @@
 """Per-Gaussian breakdown of one secondary ray of the C4 frame (t_eps 0): the oracle's segment loop
 (orc_debug_secondary_ray: what each Gaussian contributes over the reference's segments) against a numpy model
-of the device's whitened per-Gaussian intervals (vr_gauss.hip wtest / sec_finish), to find the Gaussian
+of the device's whitened per-Gaussian intervals (vr_gauss_secondary.hip wtest / sec_finish), to find the Gaussian
 whose treatment differs.  python3 tools/ray_breakdown.py x y k sample"""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
