@@ -110,7 +110,7 @@ struct vr_ctx {
     vr::DevBuf<uint64_t> env_base;
     vr::DevBuf<std::byte> deep;  // march_deep_kernel: pixel queue + global active lists (vr_gauss_march.hip)
     vr::DevBuf<uint32_t> bin_cnt, bin_off, bin_ent;  // tile bins of the binned march (VR_OPT_MARCH_BINNED)
-    vr::DevBuf<std::byte> ff_scratch;                // free-flight integrators (vr_freeflight.hip)
+    vr::DevBuf<std::byte> ff_scratch;                // free-flight integrators (vr_freeflight.hip, vr_ff_bounce.h)
     vr::DevBuf<float4> ff_tail, ff_nee;
     vr::DevBuf<float> ff_sum;
     vr::DevBuf<std::byte> ff_fb;      // ff_fallback_kernel: path queue + kFFBigCap rows

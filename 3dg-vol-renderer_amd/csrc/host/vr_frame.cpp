@@ -331,7 +331,7 @@ vr_status gauss_pipeline(vr_ctx* c, RenderArgs& A, hipStream_t s, bool stats) {
 // Free-flight integrators: one persistent launch per chunk of tiles x batch of samples (at most
 // kFFMaxPaths paths) on a grid of resident waves that claim 64-path groups from a counter, the
 // launch's queued shadow rays (deferred NEE), then the paths' radiance is added to the pixels in
-// sample order (vr_freeflight.hip).
+// sample order (vr_freeflight.hip; the bounce itself is vr_ff_bounce.h).
 constexpr uint64_t kFFMaxPaths = 1ull << 23;
 vr_status free_flight_pipeline(vr_ctx* c, RenderArgs& A, hipStream_t s) {
     const uint32_t spp = (uint32_t)A.ff_samples;

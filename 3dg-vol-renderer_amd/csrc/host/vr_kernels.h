@@ -19,9 +19,11 @@ hipError_t gauss_refit_secondary(const HNode4* src, HNode4* dst, HNode4* dst_t, 
                                  hipStream_t stream);
 hipError_t gauss_bin_scan(const uint32_t* cnt, uint32_t* off, uint32_t n, void* tmp, size_t& tmp_bytes, hipStream_t stream);
 
-// kernels/vr_freeflight.hip
+// kernels/vr_freeflight.hip (per-path helpers and ff_bounce: kernels/vr_ff_bounce.h)
 hipError_t launch_free_flight(const RenderArgs& A, uint32_t chunk_tiles, hipStream_t stream, hipEvent_t* ev);
 uint32_t free_flight_threads(int cus);
+
+// kernels/vr_loss.hip
 hipError_t launch_sfd_loss_diff(const uint32_t* bits0, const uint32_t* bits1, const float* lb, const float* lp, uint32_t npix,
                                 uint32_t n, double* out, hipStream_t stream);
 hipError_t launch_pixel_losses(const float* img, const float* ref, uint32_t npix, float* out, hipStream_t stream);

@@ -214,7 +214,7 @@ struct RenderArgs {
     uint32_t chunk_shift;           // log2(chunk_rec)
     float* rec_cut;                 // per record: optical-depth cut-off of its secondary rays (nullptr: tau_cut)
     int32_t* rec_start;             // per record: the HNode4 subtree its secondary rays walk first (nullptr: the root)
-    // ---- free-flight integrators (vr_freeflight.hip): one (tile chunk, sample batch) step ----
+    // ---- free-flight integrators (vr_freeflight.hip, vr_ff_bounce.h): one (tile chunk, sample batch) step ----
     int32_t ff_multi;        // 0 FreeFlightGaussians, 1 MultiScatterGaussians
     int32_t ff_samples;      // samples per pixel (integrator num_samples)
     int32_t ff_n;            // int(sqrt(num_samples)): strata per axis (integrator.h:564)
@@ -239,8 +239,8 @@ struct RenderArgs {
     uint32_t ff_fbq_cap;
     float4* ff_big;          // the fallback's scratch rows: hit, act0, act1, each [kFFBigCap][kFFBigThreads]
     // Deferred next-event estimation: the path kernel queues a bounce's shadow ray instead of tracing
-    // it; ff_nee_kernel traces the queue and writes each contribution into its path's slot; the
-    // accumulation adds a path's slots in bounce order (see vr_freeflight.hip).
+    // it (nee_queue, vr_ff_bounce.h); ff_nee_kernel traces the queue and writes each contribution into its
+    // path's slot; ff_path_radiance_kernel adds a path's slots in bounce order (vr_freeflight.hip).
     float4* ff_nee;          // queue, 3 float4 per ray: {o, tmax}, {d, next ray of the path (bits)},
                              // {m0 m1 m2, light bits (-1: env)}; ff_nee_kernel overwrites m with m * Li
     uint32_t* ff_nee_n;      // [0] rays queued in the launch (may pass ff_nee_cap: those rays went inline)

@@ -225,15 +225,18 @@ def test_reference_driver_default_render_matches_oracle():
     _check(g, r)
 
 
-@pytest.mark.parametrize("multi", [False, True])
-def test_deferred_shadow_rays_equal_inline(multi, device_options):
+@pytest.mark.parametrize("multi,kernel", [(False, 0), (True, 0), (False, 2), (True, 2)],
+                         ids=["False", "True", "False-phase", "True-phase"])
+def test_deferred_shadow_rays_equal_inline(multi, kernel, device_options):
     """VR_OPT_FF_NEE_QUEUE: the path kernel queues each bounce's shadow ray for ff_nee_kernel (the same
     walk and double sum as an inline transmittance_up_to), linked per path, and the accumulation adds a
     path's contributions in bounce order, so frames equal inline NEE bit for bit while the queue has
     room. A queue of 1 ray per path fills in every launch (its paths would switch to inline NEE mid-path
     and add those contributions as one partial sum): the frame is rendered again with every shadow ray
-    inline, so it is the same frame bit for bit too (round 5; until then float association only)."""
+    inline, so it is the same frame bit for bit too (round 5; until then float association only).
+    kernel: VR_OPT_FF_KERNEL, the scene's default kernel (0) and the phase-scheduled kernel forced (2)."""
     scene = vr.Scene.load_GMM(scene_path("50_random.txt"))
+    device_options("ff_kernel", kernel)
     frames = {}
     for q in (0, 16, 1):
         device_options("ff_nee_queue", q)
@@ -299,6 +302,64 @@ def test_phase_scheduled_kernel_equals_bounce_kernel(name, multi, tree):
         a, _ = _fresh_render(scene, integ, 90, 70, ff_kernel=1, **opts)
         b, _ = _fresh_render(scene, integ, 90, 70, ff_kernel=2, **opts)
         assert np.array_equal(a, b, equal_nan=True), f"window0 {w0}: max|d| {np.nanmax(np.abs(a - b)):.2e}"
+
+
+@pytest.mark.parametrize("multi", [False, True])
+def test_phase_scheduled_kernel_equals_bounce_kernel_through_the_fallback(multi):
+    """200 coincident Gaussians exceed the 128-entry rows on every path that hits them: both kernels hand
+    those paths to ff_fallback_kernel, and the frames are equal bit for bit."""
+    scene, _ = _coincident_scene(200)
+    cam = vr.Pinhole_Camera(CAM_POS, main_view_dir(), FOV)
+    integ = vr.MultiScatterGaussians(cam, 4, 5) if multi else vr.FreeFlightGaussians(cam, 4)
+    frames = {}
+    for k in (1, 2):
+        frames[k], dev = _fresh_render(scene, integ, 16, 16, ff_kernel=k)
+        st = dev.stats()
+        print(f"kernel {k}: {st}")
+        assert st["fallback_pixels"] > 0 and st["error_pixels"] == 0
+    assert np.array_equal(frames[1], frames[2], equal_nan=True)
+
+
+def test_phase_scheduled_kernel_fails_loudly_beyond_every_capacity(device_options):
+    # test_overlap_beyond_every_capacity_fails_loudly with the phase-scheduled kernel forced
+    scene, _ = _coincident_scene(1100)
+    device_options("ff_kernel", 2)
+    with pytest.raises(vr.VRError):
+        _gpu(scene, 8, 8, True, 1)
+
+
+@pytest.mark.parametrize("solver", ["bisection", "uniform"])
+def test_phase_scheduled_kernel_equals_bounce_kernel_with_other_solvers(solver, device_options):
+    """The solvers that read the cached F rows (bisection: od_to / ph) and the path's seed (uniform:
+    ff_path_seed) give the same frame under both kernels, bit for bit."""
+    scene = vr.Scene.load_GMM(scene_path("250_random.txt"))
+    cam = vr.Pinhole_Camera(CAM_POS, main_view_dir(), FOV)
+    frames = {}
+    try:
+        for k in (1, 2):
+            device_options("ff_kernel", k)
+            img = vr.Image(32, 32)
+            vr.MultiScatterGaussians(cam, 4, 5, solver=solver).render(scene, img)
+            frames[k] = img.pixels.copy()
+    finally:
+        vr.Device.get(0).set_option("ff_solver", 0)
+    assert np.array_equal(frames[1], frames[2], equal_nan=True), f"max|d| {np.nanmax(np.abs(frames[1] - frames[2])):.2e}"
+
+
+def test_phase_scheduled_kernel_records_what_the_bounce_kernel_records(device_options):
+    """RECORD_PIXEL_GAUSSIANS under both kernels: the same per-pixel Gaussian sets and the same image."""
+    scene = vr.Scene.load_GMM(scene_path("50_random.txt"))
+    integ = vr.MultiScatterGaussians(vr.Pinhole_Camera(CAM_POS, main_view_dir(), FOV), 4)
+    bits, imgs = {}, {}
+    for k in (1, 2):
+        device_options("ff_kernel", k)
+        img = vr.Image(32, 32)
+        integ.record(scene, img, slot=0)
+        bits[k] = integ.pixel_gaussian_bits(0)
+        imgs[k] = img.pixels.copy()
+    assert bits[1].any()
+    assert np.array_equal(bits[1], bits[2])
+    assert np.array_equal(imgs[1], imgs[2], equal_nan=True)
 
 
 @pytest.mark.parametrize("queue", [1, 2])

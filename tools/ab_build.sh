@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B build of libvr_hip.so with one kernel object recompiled under extra -D flags:
 #   tools/ab_build.sh NAME KERNEL(a unit of csrc/kernels: vr_gauss_march, vr_gauss_secondary, vr_gauss_exact, vr_gauss_tree,
-#   vr_gauss_shade, vr_freeflight, vr_query, vr_spheres, vr_lbvh) "-DFOO=1 ..."  -> _ab/NAME/libvr_hip.so
+#   vr_gauss_shade, vr_freeflight, vr_loss, vr_query, vr_spheres, vr_lbvh) "-DFOO=1 ..."  -> _ab/NAME/libvr_hip.so
 set -e
 cd "$(dirname "$0")/../3dg-vol-renderer_amd/csrc"
 name=$1; k=$2; flags=$3
