@@ -443,4 +443,61 @@ vr_status vr_upload_scene(vr_ctx* c, const vr_scene* sc) {
     return VR_OK;
 }
 
+vr_status vr_tree_limits(int32_t* leaf_max, int32_t* max_depth, int32_t* wide_stack_max) {
+    if (leaf_max) *leaf_max = kLeafMax;
+    if (max_depth) *max_depth = kMaxDepth;
+    if (wide_stack_max) *wide_stack_max = kWideStackMax;
+    return VR_OK;
+}
+
+vr_status vr_debug_tree(vr_ctx* c, int32_t array, void* out, size_t cap, size_t* n, size_t* elem_bytes, vr_tree_info* info) {
+    if (!c || !n || (cap > 0 && !out)) return fail(VR_ERR_INVALID, "vr_debug_tree: bad argument");
+    if (c->group) return fail(VR_ERR_INVALID, "vr_debug_tree: a multi-device context holds one scene per device");
+    if (!c->has_scene) return fail(VR_ERR_INVALID, "vr_debug_tree: no scene uploaded");
+    if (c->type != VR_VOLUME_GAUSSIANS) return fail(VR_ERR_INVALID, "vr_debug_tree: a sphere scene has no tree");
+    const SceneDev& s = c->scene;
+    const size_t np = (size_t)c->num_prims, n4 = s.hnodes4 ? s.num_nodes4 : 0;
+    const void* src = nullptr;
+    size_t count = 0, elem = 0;
+    switch (array) {
+        case VR_TREE_ORDER: src = s.order.get(), count = np, elem = sizeof(uint32_t); break;
+        case VR_TREE_RECORDS: src = s.gauss.get(), count = np, elem = sizeof(GaussianRecord); break;
+        case VR_TREE_NODES: src = s.nodes.get(), count = s.num_nodes, elem = sizeof(BVHNode); break;
+        case VR_TREE_HNODES: src = s.hnodes.get(), count = s.num_nodes, elem = sizeof(HNode); break;
+        case VR_TREE_HNODES4: src = s.hnodes4.get(), count = n4, elem = sizeof(HNode4); break;
+        case VR_TREE_HNODES4S: src = s.hnodes4s.get(), count = n4, elem = sizeof(HNode4); break;
+        case VR_TREE_HNODES4W: src = s.hnodes4w.get(), count = n4, elem = sizeof(HNode4); break;
+        case VR_TREE_HNODES4T:  // the second half of the tight tree's allocation (upload_secondary_tree)
+            src = (VR_SEC_SOA && s.hnodes4s) ? s.hnodes4s.get() + n4 : nullptr, count = n4, elem = sizeof(HNode4);
+            break;
+        case VR_TREE_PARENT4: src = s.parent4.get(), count = n4, elem = sizeof(int32_t); break;
+        case VR_TREE_PRIM_NODE4: src = s.prim_node4.get(), count = np, elem = sizeof(int32_t); break;
+        default: return fail(VR_ERR_INVALID, "vr_debug_tree: unknown array");
+    }
+    if (!src) count = 0;
+    HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+    HIP_TRY(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+    *n = count;
+    if (elem_bytes) *elem_bytes = elem;
+    if (info) {
+        *info = vr_tree_info{};
+        info->num_prims = c->num_prims;
+        info->num_nodes = (int64_t)s.num_nodes;
+        info->num_nodes4 = (int64_t)n4;
+        info->bvh_depth = s.bvh_depth;
+        info->built_on_device = s.last_upload_device_bvh ? 1 : 0;
+        info->wrec_pd = s.wrec_pd ? 1 : 0;
+        vr_tree_limits(&info->leaf_max, &info->max_depth, &info->wide_stack_max);
+        for (int k = 0; k < 3; ++k) {
+            info->hn_center[k] = s.hn_center[k];
+            info->bounds_min[k] = s.bmin[k];
+            info->bounds_max[k] = s.bmax[k];
+        }
+        info->hn_scale = s.hn_scale;
+    }
+    const size_t m = std::min(count, cap);
+    if (m > 0) HIP_TRY(hipMemcpy(out, src, m * elem, hipMemcpyDeviceToHost), "hipMemcpy(tree)");
+    return VR_OK;
+}
+
 }  // extern "C"

@@ -394,6 +394,35 @@ class Device:
         check(lib().vr_debug_pixel_records(self._h, int(x), int(y), fptr(out), n.value, row.value, ctypes.byref(n), None))
         return out[:n.value]
 
+    def debug_tree(self, arrays=None):
+        """vr_debug_tree: the uploaded Gaussian scene's trees as they lie on the device, a dict of numpy arrays
+        (L.TREE_ARRAYS: order, records, the structured nodes / hnodes / hnodes4 / hnodes4s, the per-axis word
+        copies hnodes4w / hnodes4t, parent4, prim_node4; an array the scene does not have is empty) plus
+        "info", a dict of the vr_tree_info fields. `arrays` limits the read-back to the names given."""
+        info = L.vr_tree_info()
+        out = {}
+        for name in (L.TREE_ARRAYS if arrays is None else arrays):
+            sel, dt = L.TREE_ARRAYS[name]
+            n, elem = ctypes.c_size_t(), ctypes.c_size_t()
+            check(lib().vr_debug_tree(self._h, sel, None, 0, ctypes.byref(n), ctypes.byref(elem), ctypes.byref(info)))
+            a = np.zeros(n.value, np.dtype(dt))
+            if np.dtype(dt).itemsize != elem.value:
+                raise ValueError(f"{name}: elements of {elem.value} bytes, the table has {np.dtype(dt).itemsize}")
+            if n.value:
+                check(lib().vr_debug_tree(self._h, sel, a.ctypes.data, n.value, ctypes.byref(n), None, None))
+            out[name] = a
+        if not out:
+            n = ctypes.c_size_t()
+            check(lib().vr_debug_tree(self._h, 0, None, 0, ctypes.byref(n), None, ctypes.byref(info)))
+        d = {k: getattr(info, k) for k, _ in L.vr_tree_info._fields_}
+        for k in ("hn_center", "bounds_min", "bounds_max"):
+            d[k] = np.array(list(d[k]), np.float32)
+        d["hn_scale"] = np.float32(d["hn_scale"])
+        for k in ("built_on_device", "wrec_pd"):
+            d[k] = bool(d[k])
+        out["info"] = d
+        return out
+
     OPTIONS = {"half_nodes": L.VR_OPT_HALF_NODES, "secondary_budget": L.VR_OPT_SECONDARY_BUDGET,
                "ff_window0": L.VR_OPT_FF_WINDOW0, "record_capacity": L.VR_OPT_RECORD_CAPACITY,
                "device_bvh": L.VR_OPT_DEVICE_BVH, "ff_nee_queue": L.VR_OPT_FF_NEE_QUEUE,

@@ -85,6 +85,28 @@ class vr_ray(ctypes.Structure):
     _fields_ = [("origin", f3), ("tmax", ctypes.c_float), ("direction", f3), ("unit", ctypes.c_float)]
 
 
+class vr_tree_info(ctypes.Structure):
+    _fields_ = [("num_prims", ctypes.c_int64), ("num_nodes", ctypes.c_int64), ("num_nodes4", ctypes.c_int64),
+                ("bvh_depth", ctypes.c_int32), ("built_on_device", ctypes.c_int32), ("wrec_pd", ctypes.c_int32),
+                ("leaf_max", ctypes.c_int32), ("max_depth", ctypes.c_int32), ("wide_stack_max", ctypes.c_int32),
+                ("hn_center", f3), ("hn_scale", ctypes.c_float), ("bounds_min", f3), ("bounds_max", f3)]
+
+
+# vr_tree_array (include/vr_hip.h): name -> (selector, numpy dtype of one element as stored on the device)
+TREE_ARRAYS = {
+    "order": (0, "<u4"),
+    "records": (1, ("<f4", (12,))),
+    "nodes": (2, [("f", "<f4", (12,)), ("c", "<i4", (4,))]),
+    "hnodes": (3, [("h", "<u2", (12,)), ("c", "<i4", (2,))]),
+    "hnodes4": (4, [("h", "<u2", (4, 6)), ("c", "<i4", (4,))]),
+    "hnodes4s": (5, [("h", "<u2", (4, 6)), ("c", "<i4", (4,))]),
+    "hnodes4w": (6, ("<u4", (16,))),
+    "hnodes4t": (7, ("<u4", (16,))),
+    "parent4": (8, "<i4"),
+    "prim_node4": (9, "<i4"),
+}
+
+
 # name -> (restype, argtypes). Every symbol declared in include/vr_hip.h.
 P = ctypes.c_void_p
 PP = ctypes.POINTER(ctypes.c_void_p)
@@ -167,6 +189,9 @@ SIGNATURES = {
     "vr_query_pack_rays_device": (ST, [P, P, P, P, ctypes.c_uint32, ctypes.c_size_t, P, P]),
     "vr_debug_pixel_records": (ST, [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_float), ctypes.c_size_t,
                                     ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
+    "vr_debug_tree": (ST, [P, ctypes.c_int32, P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+                           ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(vr_tree_info)]),
+    "vr_tree_limits": (ST, [ctypes.POINTER(ctypes.c_int32)] * 3),
 }
 
 _lib = None

@@ -422,6 +422,52 @@ vr_status vr_get_fallback_pixels(vr_ctx* ctx, uint32_t* xy, size_t cap, size_t* 
 vr_status vr_debug_pixel_records(vr_ctx* ctx, uint32_t x, uint32_t y, float* out, size_t cap, size_t row, size_t* n,
                                  size_t* row_out);
 
+/* Diagnostics: the trees of the uploaded Gaussian scene as they lie on the device (read-only: no state of the
+ * context changes and nothing is allocated past the call; the context's stream is synchronised first).
+ * `array` selects one of the scene's arrays; elements are copied as stored (csrc/vr_internal.h):
+ *   ORDER       uint32          record (tree order) -> scene index
+ *   RECORDS     12 x float      mean xyz, density, M 00 01 02 11 12 22, norm, albedo, in tree order
+ *   NODES       64 B BVHNode    child-pair tree: float f[12] (left box min xyz max xyz, right box), int32 c[4]
+ *   HNODES      32 B HNode      its half-precision copy: uint16 h[12], int32 c[2]
+ *   HNODES4     64 B HNode4     the 4-wide collapse: uint16 h[4][6], int32 c[4]
+ *   HNODES4S    64 B HNode4     the secondary rays' tight refit of it
+ *   HNODES4W    16 x uint32     HNODES4 laid out per axis (words 4a .. 4a+3: axis a's bounds as f16 pairs {min of
+ *   HNODES4T    16 x uint32     children 0, 1}, {min 2, 3}, {max 0, 1}, {max 2, 3}; words 12-15 the refs); of HNODES4S
+ *   PARENT4     int32           parent of every 4-wide node | (its slot + 1) << 28, root -1
+ *   PRIM_NODE4  int32           the 4-wide node holding each record's leaf
+ * Two calls, as vr_debug_pixel_records: with cap = 0 the element count goes into *n and the element size into
+ * *elem_bytes (if not NULL); with cap > 0, up to cap elements are written to out. An array the scene does not have
+ * (no half-precision trees, no tight refit) has count 0. `info`, if not NULL, is filled by every successful call.
+ * VR_ERR_INVALID: no scene, a sphere scene, a vr_init_multi context, or an unknown array. */
+typedef enum vr_tree_array {
+    VR_TREE_ORDER = 0,
+    VR_TREE_RECORDS = 1,
+    VR_TREE_NODES = 2,
+    VR_TREE_HNODES = 3,
+    VR_TREE_HNODES4 = 4,
+    VR_TREE_HNODES4S = 5,
+    VR_TREE_HNODES4W = 6,
+    VR_TREE_HNODES4T = 7,
+    VR_TREE_PARENT4 = 8,
+    VR_TREE_PRIM_NODE4 = 9
+} vr_tree_array;
+typedef struct vr_tree_info {
+    int64_t num_prims, num_nodes, num_nodes4;
+    int32_t bvh_depth;       /* levels of the child-pair tree, leaves included (root = 1): picks the traversal stack */
+    int32_t built_on_device; /* 1: the device builder made this tree, 0: the host builder (also as its fallback) */
+    int32_t wrec_pd;         /* 1: every record's M is positive definite (whitened secondary rays) */
+    int32_t leaf_max;        /* build constants: primitives per leaf, */
+    int32_t max_depth;       /*   the builders' depth bound (bvh_depth <= max_depth + 1), */
+    int32_t wide_stack_max;  /*   per-lane stack entries of a 4-wide walk */
+    float hn_center[3];      /* half-precision normalisation: u = (x - hn_center) * hn_scale */
+    float hn_scale;
+    float bounds_min[3], bounds_max[3]; /* the scene box */
+} vr_tree_info;
+vr_status vr_debug_tree(vr_ctx* ctx, int32_t array, void* out, size_t cap, size_t* n, size_t* elem_bytes,
+                        vr_tree_info* info);
+/* The build constants of vr_tree_info alone (no context needed); any pointer may be NULL. */
+vr_status vr_tree_limits(int32_t* leaf_max, int32_t* max_depth, int32_t* wide_stack_max);
+
 /* ---------------- mixture queries (gmm.h) ---------------- */
 /* The three questions GaussianMixtureModel answers about the mixture itself, for a batch of the caller's
  * rays or points against the uploaded Gaussian scene (sphere scenes: VR_ERR_UNSUPPORTED). Every Gaussian is

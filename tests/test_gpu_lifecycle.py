@@ -47,10 +47,11 @@ def generation(g):
     import vr_amd as vr
     cam = vr.Pinhole_Camera(CAM_POS, main_view_dir(), FOV)
     dev = vr.Device(0)
-    dev.set_option("device_bvh", g & 1)  # 1000_random has >= 256 primitives: the device builder when enabled
+    dev.set_option("device_bvh", g & 1)
     dev.set_option("half_nodes", 0 if g == 2 else 1)
     big = vr.Scene.load_GMM(scene_path("1000_random.txt"))
     dev.upload(big)
+    assert dev.debug_tree(arrays=())["info"]["built_on_device"] == bool(g & 1)
     out = {}
     out["march"] = render(dev, vr.RayMarchingGaussians(cam, env_samples=4), 64, 64)
     out["march_eps"] = render(dev, vr.RayMarchingGaussians(cam, env_samples=4, t_eps=1e-3), 64, 64)  # rec_cut
