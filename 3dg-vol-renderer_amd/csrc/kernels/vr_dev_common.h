@@ -13,7 +13,8 @@ constexpr float kTPad = 1e-5f;
 
 enum { kOK = 0, kOverflow = 1, kError = 2 };
 
-// Sorted list of Gaussian (leaf-order) ids with a 64-bit bloom mask for membership tests.
+// List of Gaussian (leaf-order) ids, kept in scene-index order by the march (RenderArgs::gauss_order), with a
+// 64-bit bloom mask for membership tests.
 // Element i lives at act[i * stride] (LDS with a per-thread stride, or a global array, stride 1).
 struct ActList {
     int* act;

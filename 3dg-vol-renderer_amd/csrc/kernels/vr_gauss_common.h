@@ -18,8 +18,8 @@
 // No per-ray event list is ever built or sorted:
 //   * the step sequence t_k is the reference's own iterated float sum (host table), so empty
 //     stretches are skipped by index;
-//   * the active set at step k is {i : a_i <= t_k < b_i}; it is kept as a short sorted list of
-//     Gaussian ids in LDS, extended by BVH queries restricted to the window (t_{k-1}, t_k] or by a
+//   * the active set at step k is {i : a_i <= t_k < b_i}; it is kept as a short list of
+//     Gaussian ids in LDS, sorted by scene index (the order the reference sums a step's densities in), extended by BVH queries restricted to the window (t_{k-1}, t_k] or by a
 //     closest-entry query when it runs empty;
 //   * a secondary ray's transmittance telescopes the reference's segment loop into one sum of
 //     per-Gaussian optical depths over each Gaussian's active interval on that ray, reproducing the

@@ -384,8 +384,11 @@ __device__ int march(const RenderArgs& A, uint32_t p, int px, int py, int* act_b
                             ovf = true;
                             continue;
                         }
-                        int i = act.n;  // sorted insert
-                        while (i > 0 && act.get(i - 1) > (int)j) {
+                        // sorted insert by scene index (gmm.h:98-126 sums in that order): a step's sums do not
+                        // depend on how the tree's builder ordered the records
+                        const uint32_t key = A.gauss_order[j];
+                        int i = act.n;
+                        while (i > 0 && A.gauss_order[act.get(i - 1)] > key) {
                             act.set(i, act.get(i - 1));
                             --i;
                         }
@@ -755,8 +758,9 @@ __global__ __launch_bounds__(64) void march_binned_kernel(RenderArgs A) {
                     done = true;
                     return;
                 }
-                int i = act.n;  // sorted insert (index order, gmm.h:98-126)
-                while (i > 0 && act.get(i - 1) > j) {
+                const uint32_t key = A.gauss_order[j];  // sorted insert (scene-index order, gmm.h:98-126)
+                int i = act.n;
+                while (i > 0 && A.gauss_order[act.get(i - 1)] > key) {
                     act.set(i, act.get(i - 1));
                     --i;
                 }

@@ -95,6 +95,23 @@ def debug_pixel_records(scene, pos, view_dir, fov, x, y, W, H, step_size=0.01, e
     return out[:min(n, out.shape[0])]
 
 
+def debug_record_active(scene, pos, view_dir, fov, x, y, W, H, k, step_size=0.01, env_samples=20):
+    """orc_debug_record_active: the scene indices active at scattering step k of pixel (x, y) (see
+    debug_pixel_records), or None if the pixel has no such step. Test tooling only."""
+    pos, pp = _f(pos)
+    vd, pv = _f(view_dir)
+    L = lib()
+    L.orc_debug_record_active.restype = ctypes.c_int64
+    L.orc_debug_record_active.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                          ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
+                                          ctypes.c_int64]
+    out = np.zeros(4096, np.int64)
+    n = L.orc_debug_record_active(scene.h, pp, pv, float(fov), int(x), int(y), int(W), int(H), float(step_size),
+                                  int(env_samples), int(k), out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), out.shape[0])
+    return None if n < 0 else out[:min(n, out.shape[0])].tolist()
+
+
 def primary_depths(scene, cam_type, pos, view_dir, fov, W, H, step_size=0.01, t_eps=1e-6, nthreads=0):
     """(H, W) termination distance of every primary ray (-1: no events); see orc_primary_depths."""
     pos, pp = _f(pos)
