@@ -1,6 +1,6 @@
 // The device context (vr_ctx) and what its host files share: vr_device.cpp (init / destroy, options,
 // vr_synchronize, the SFD helpers), vr_upload.cpp (vr_upload_scene), vr_frame.cpp (the frame pipelines,
-// their report and the render entry points) and vr_query_host.cpp (vr_query_*).
+// their report and the render entry points), vr_rays.cpp (vr_render_rays) and vr_query_host.cpp (vr_query_*).
 #pragma once
 #include <map>
 
@@ -127,6 +127,10 @@ struct vr_ctx {
     vr::DevBuf<unsigned long long> q_keys, q_keys2;  // sort keys (in / out),
     vr::DevBuf<std::byte> q_tmp;                // scan + sort scratch
     vr::DevBuf<std::byte> q_ctl;      // words [0..2] ray counters of the three persistent walks, [4..5] the 64-bit event total
+    // ray grids (vr_render_rays, vr_rays.cpp)
+    vr::DevBuf<vr_ray> ray_in;        // host form: the grid on the device,
+    vr::DevBuf<float> ray_tr;         //   and its transmittance output
+    vr::DevBuf<uint32_t> ray_ext;     // device form: the extent reduction's result (ray_extent_kernel)
     bool q_count_valid = false;       // the last vr_query_events_count_device of this scene: its n and total
     uint64_t q_count_n = 0, q_count_total = 0;
     int pcg_jump_n = -1;
@@ -168,6 +172,18 @@ vr_status collect(vr_ctx* c);           // waits for the last frame's report and
 bool frame_exceeded(const vr_ctx* c);   // that frame outgrew its buffers: render it again
 // A full frame into the context's frame buffer; slot 0/1 records RECORD_PIXEL_GAUSSIANS bitsets, -1 none.
 vr_status render_frame_device(vr_ctx* c, const vr_camera* cam, const vr_render_params* p, uint32_t W, uint32_t H, int32_t slot);
+// Kernel arguments of a frame apart from its rays' source (a camera: vr_frame.cpp, a ray grid: vr_rays.cpp)
+vr_status fill_scene_args(vr_ctx* c, const vr_render_params* p, uint32_t W, uint32_t H, vr::RenderArgs& A);
+bool needs_table(const vr_render_params* p);      // the integrator marches the step table
+float table_tmax(const vr_ctx* c, float extent);  // the table's reach for primary rays that travel `extent` at most
+// (max_entries > 0: VR_ERR_OVERFLOW, before anything is allocated, for a table of more entries)
+vr_status fill_table(vr_ctx* c, const vr_render_params* p, float tmax, uint32_t max_entries, vr::RenderArgs& A);
+// One frame's kernels and report on stream s (asynchronous), and the synchronous form on the context's stream,
+// which renders a frame that outgrew its record buffers again
+// (grid: a ray grid's rays and transmittance output; nullptr: a camera frame)
+vr_status launch(vr_ctx* c, vr::RenderArgs& A, const vr_render_params* p, hipStream_t s, bool stats = false,
+                 const vr::GridSrc* grid = nullptr);
+vr_status render_sync(vr_ctx* c, vr::RenderArgs& A, const vr_render_params* p, const vr::GridSrc* grid = nullptr);
 
 }  // namespace vr
 #pragma GCC visibility pop

@@ -31,21 +31,22 @@ float scene_tmax(const vr_ctx* c, const vr_camera* cam) {
                         best = std::max(best, (float)std::sqrt(d));
                     }
         }
-    // secondary rays start inside the scene box: a Gaussian interval on them ends within one
-    // box diagonal (PureRayMarching marches them over the same step table)
-    double diag = 0.0;
-    for (int k = 0; k < 3; ++k) diag += (double)(bmax[k] - bmin[k]) * (bmax[k] - bmin[k]);
-    best = std::max(best, (float)std::sqrt(diag));
-    return best * 1.01f + 1.0f;
+    return table_tmax(c, best);
 }
 
-vr_status get_table(vr_ctx* c, float step, float tmax, const float** d, int* n) {
+// max_entries > 0 (ray grids, whose extent is the caller's): a table of more entries is refused before anything is
+// allocated, and the doubling of a cached table stops there.
+vr_status get_table(vr_ctx* c, float step, float tmax, const float** d, int* n, uint32_t max_entries = 0) {
     if (!(step > 0.0f) || !std::isfinite(step)) return fail(VR_ERR_INVALID, "step_size must be a positive finite float");
+    if (max_entries > 0 && !((double)tmax / (double)step < (double)max_entries))
+        return fail(VR_ERR_OVERFLOW, "the rays' extent over step_size needs a step table of more than " + std::to_string(max_entries) +
+                                         " entries (move the ray origins closer to the scene, or enlarge step_size)");
     uint32_t key;
     std::memcpy(&key, &step, 4);
     auto it = c->tables.find(key);
     if (it == c->tables.end() || it->second.tmax < tmax) {
         float want = it == c->tables.end() ? tmax : std::max(tmax, 2.0f * it->second.tmax);
+        if (max_entries > 0 && !((double)want / (double)step < (double)max_entries)) want = tmax;
         std::vector<float> t = step_table(step, want);
         if (t.back() <= tmax) return fail(VR_ERR_OVERFLOW, "step_size too small for the scene extent (float step sequence stalls)");
         vr_ctx::Table tb;
@@ -71,11 +72,15 @@ vr_status ensure_queue(vr_ctx* c, uint64_t pixels) {
     return VR_OK;
 }
 
-vr_status fill_args(vr_ctx* c, const vr_camera* cam, const vr_render_params* p, uint32_t W, uint32_t H, RenderArgs& A) {
+}  // namespace
+
+// Kernel arguments, in the three parts a frame is made of. fill_scene_args: the checks of the request and everything
+// that does not depend on where the rays come from; the rays are a camera's (fill_args below) or a caller's grid
+// (vr_rays.cpp), and either sizes the step table by its own extent (fill_table).
+vr_status vr::fill_scene_args(vr_ctx* c, const vr_render_params* p, uint32_t W, uint32_t H, RenderArgs& A) {
     if (!c->has_scene) return fail(VR_ERR_NOSCENE, "no scene uploaded (call vr_upload_scene first)");
-    if (!cam || !p) return fail(VR_ERR_INVALID, "NULL camera or params");
+    if (!p) return fail(VR_ERR_INVALID, "NULL camera or params");
     if (W == 0 || H == 0 || W > 65535 || H > 65535) return fail(VR_ERR_INVALID, "width/height must be in [1, 65535]");
-    if (cam->type != VR_CAMERA_PINHOLE && cam->type != VR_CAMERA_ORTHOGRAPHIC) return fail(VR_ERR_INVALID, "unknown camera type");
     if (p->flags != 0) return fail(VR_ERR_INVALID, "vr_render_params.flags must be 0");
     if ((p->integrator == VR_RAYMARCH_GAUSSIANS || p->integrator == VR_PURE_RAYMARCH) && c->type != VR_VOLUME_GAUSSIANS)
         return fail(VR_ERR_INVALID, "RayMarchingGaussians needs a Gaussian scene");
@@ -92,14 +97,6 @@ vr_status fill_args(vr_ctx* c, const vr_camera* cam, const vr_render_params* p, 
     if (!ff && p->integrator != VR_TEST_HITMASK && p->env_samples < 0) return fail(VR_ERR_INVALID, "env_samples must be >= 0");
     if (!(p->t_eps >= 0.0f) || p->t_eps >= 1.0f) return fail(VR_ERR_INVALID, "t_eps must be in [0, 1)");
     std::memset(&A, 0, sizeof(A));
-    A.cam_type = cam->type;
-    for (int k = 0; k < 3; ++k) {
-        A.cam_pos[k] = cam->position[k];
-        A.cam_view[k] = cam->view_dir[k];
-        A.cam_right[k] = cam->right[k];
-        A.cam_up[k] = cam->up[k];
-        A.cam_pinhole[k] = cam->pinhole[k];
-    }
     A.width = W;
     A.height = H;
     A.tiles_x = (W + kTile - 1) / kTile;
@@ -142,21 +139,59 @@ vr_status fill_args(vr_ctx* c, const vr_camera* cam, const vr_render_params* p, 
         A.ff_max_bounces = 1 << 16;
         A.ff_solver = (int32_t)c->opt_ff_solver;
         A.ff_sm = c->opt_ff_kernel == 2 || (c->opt_ff_kernel == 0 && c->auto_ff_sm) ? 1 : 0;
-    } else if (p->integrator != VR_TEST_HITMASK) {
-        const float* d;
-        int n;
-        VR_TRY(get_table(c, p->step_size, scene_tmax(c, cam), &d, &n));
-        A.tsteps = d;
-        A.num_tsteps = n;
     }
     A.counters = c->counters.get();
     A.gauss_order = sd.order.get();
     return VR_OK;
 }
 
+bool vr::needs_table(const vr_render_params* p) {
+    return p->integrator == VR_RAYMARCH_GAUSSIANS || p->integrator == VR_PURE_RAYMARCH || p->integrator == VR_RAYMARCH_SPHERES;
+}
+
+// The step table of a ray-march frame whose rays travel at most tmax.
+vr_status vr::fill_table(vr_ctx* c, const vr_render_params* p, float tmax, uint32_t max_entries, RenderArgs& A) {
+    const float* d;
+    int n;
+    VR_TRY(get_table(c, p->step_size, tmax, &d, &n, max_entries));
+    A.tsteps = d;
+    A.num_tsteps = n;
+    return VR_OK;
+}
+
+// Farthest a ray starting within `extent` of every corner of the scene box, or a secondary ray, travels in it.
+float vr::table_tmax(const vr_ctx* c, float extent) {
+    const float *bmin = c->scene.bmin, *bmax = c->scene.bmax;
+    // secondary rays start inside the scene box: a Gaussian interval on them ends within one
+    // box diagonal (PureRayMarching marches them over the same step table)
+    double diag = 0.0;
+    for (int k = 0; k < 3; ++k) diag += (double)(bmax[k] - bmin[k]) * (bmax[k] - bmin[k]);
+    return std::max(extent, (float)std::sqrt(diag)) * 1.01f + 1.0f;
+}
+
+namespace {
+
+vr_status fill_args(vr_ctx* c, const vr_camera* cam, const vr_render_params* p, uint32_t W, uint32_t H, RenderArgs& A) {
+    if (!c->has_scene) return fail(VR_ERR_NOSCENE, "no scene uploaded (call vr_upload_scene first)");
+    if (!cam || !p) return fail(VR_ERR_INVALID, "NULL camera or params");
+    if (W == 0 || H == 0 || W > 65535 || H > 65535) return fail(VR_ERR_INVALID, "width/height must be in [1, 65535]");
+    if (cam->type != VR_CAMERA_PINHOLE && cam->type != VR_CAMERA_ORTHOGRAPHIC) return fail(VR_ERR_INVALID, "unknown camera type");
+    VR_TRY(fill_scene_args(c, p, W, H, A));
+    A.cam_type = cam->type;
+    for (int k = 0; k < 3; ++k) {
+        A.cam_pos[k] = cam->position[k];
+        A.cam_view[k] = cam->view_dir[k];
+        A.cam_right[k] = cam->right[k];
+        A.cam_up[k] = cam->up[k];
+        A.cam_pinhole[k] = cam->pinhole[k];
+    }
+    if (needs_table(p)) VR_TRY(fill_table(c, p, scene_tmax(c, cam), 0, A));
+    return VR_OK;
+}
+
 
 // RayMarchingGaussians: march (records) -> sizing / cut-offs -> secondary rays -> accumulate.
-vr_status gauss_pipeline(vr_ctx* c, RenderArgs& A, hipStream_t s, bool stats) {
+vr_status gauss_pipeline(vr_ctx* c, RenderArgs& A, hipStream_t s, bool stats, const GridSrc* grid) {
     const uint32_t npix = A.num_tiles * 256u;
     VR_TRY(c->px_first.grow(npix, "hipMalloc(px_first)", A.px_first));
     VR_TRY(c->px_T.grow(npix, "hipMalloc(px_T)", A.px_T));
@@ -189,7 +224,7 @@ vr_status gauss_pipeline(vr_ctx* c, RenderArgs& A, hipStream_t s, bool stats) {
     // Tile bins of the binned march: count, scan, then (with one host sync for the entry count) emit.
     A.bin_off = A.bin_ent = nullptr;
     A.bin_cnt = A.bin_out = nullptr;
-    if (c->opt_march_binned && A.num_prims > 0) {
+    if (c->opt_march_binned && A.num_prims > 0 && grid == nullptr) {  // (a ray grid has no tile frusta to bin by)
 #ifndef VR_BIN_BUCKETS
 #define VR_BIN_BUCKETS 256  // depth buckets per tile (a bucket's hits wait in a 16-entry per-lane list)
 #endif
@@ -252,7 +287,7 @@ vr_status gauss_pipeline(vr_ctx* c, RenderArgs& A, hipStream_t s, bool stats) {
         HIP_TRY(hipMemsetAsync(A.rec_alloc, 0, 16, s), "hipMemsetAsync(rec_alloc)");
         HIP_TRY(hipMemsetAsync(c->queue.get(), 0, sizeof(uint32_t), s), "hipMemsetAsync(queue)");
         HIP_TRY(hipMemsetAsync(A.deepq, 0, sizeof(uint32_t), s), "hipMemsetAsync(deep queue)");
-        HIP_TRY(gauss_march(A, s, stats), "march");
+        HIP_TRY(gauss_march(A, s, stats, grid), "march");
         if (attempt == 0) HIP_TRY(hipEventRecord(c->ev_stage[0], s), "hipEventRecord");
         if (sized) break;
         HIP_TRY(hipMemcpyAsync(c->h_sizing.get(), A.rec_alloc, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "rec_alloc D2H");
@@ -320,7 +355,7 @@ vr_status gauss_pipeline(vr_ctx* c, RenderArgs& A, hipStream_t s, bool stats) {
     }
     HIP_TRY(gauss_secondary(A, s, stats), "secondary rays");
     HIP_TRY(hipEventRecord(c->ev_stage[2], s), "hipEventRecord");
-    HIP_TRY(gauss_accumulate(A, s), "accumulate");
+    HIP_TRY(gauss_accumulate(A, s, grid ? grid->out_tr : nullptr), "accumulate");
     c->staged = true;
     c->report_gauss = true;
     c->report_pixels = (uint64_t)A.num_tiles * 256u;
@@ -444,9 +479,7 @@ bool frame_exceeded(const vr_ctx* c) {
 
 }  // namespace vr
 
-namespace {
-
-vr_status launch(vr_ctx* c, RenderArgs& A, const vr_render_params* p, hipStream_t s, bool stats = false) {
+vr_status vr::launch(vr_ctx* c, RenderArgs& A, const vr_render_params* p, hipStream_t s, bool stats, const GridSrc* grid) {
     VR_TRY(ensure_queue(c, (uint64_t)A.num_tiles * 256u));
     A.queue = c->queue.get();
     A.queue_cap = c->queue_cap;
@@ -460,12 +493,12 @@ vr_status launch(vr_ctx* c, RenderArgs& A, const vr_render_params* p, hipStream_
     c->report_ff = false;
     c->ff_launches = 0;
     if (c->type == VR_VOLUME_GAUSSIANS && (p->integrator == VR_RAYMARCH_GAUSSIANS || p->integrator == VR_PURE_RAYMARCH)) {
-        VR_TRY(gauss_pipeline(c, A, s, stats));
+        VR_TRY(gauss_pipeline(c, A, s, stats, grid));
     } else if (p->integrator == VR_FREE_FLIGHT || p->integrator == VR_MULTI_SCATTER) {
         VR_TRY(free_flight_pipeline(c, A, s));
         c->report_ff = true;
     } else {
-        HIP_TRY(launch_render(A, s, c->type, p->integrator), "kernel launch");
+        HIP_TRY(launch_render(A, s, c->type, p->integrator, grid), "kernel launch");
     }
     HIP_TRY(hipEventRecord(c->ev_stop, s), "hipEventRecord");
     auto report = [&](Report first, const uint32_t* src, size_t words) {
@@ -494,13 +527,13 @@ vr_status launch(vr_ctx* c, RenderArgs& A, const vr_render_params* p, hipStream_
 // Synchronous frame into the context's device frame buffer (render_frame_device): a frame that outgrew
 // the record buffers sized from earlier frames is rendered again with grown ones; pixels / paths over
 // every per-ray capacity fail the call.
-vr_status render_sync(vr_ctx* c, RenderArgs& A, const vr_render_params* p) {
+vr_status vr::render_sync(vr_ctx* c, RenderArgs& A, const vr_render_params* p, const GridSrc* grid) {
     struct Reported {  // every exit reports this frame's outcome itself: vr_synchronize must not report it again
         vr_ctx* c;
         ~Reported() { c->sync_pending = false; }
     } reported{c};
     for (int attempt = 1;; ++attempt) {
-        VR_TRY(launch(c, A, p, c->stream));
+        VR_TRY(launch(c, A, p, c->stream, false, grid));
         VR_TRY(collect(c));
         if (!frame_exceeded(c)) break;
         if (attempt >= kFrameAttempts)
@@ -510,6 +543,8 @@ vr_status render_sync(vr_ctx* c, RenderArgs& A, const vr_render_params* p) {
         return fail(VR_ERR_OVERFLOW, std::to_string(c->h_report[kRepErrors]) + " pixels / paths exceeded a per-ray capacity (NaN)");
     return VR_OK;
 }
+
+namespace {
 
 // The tiles first_tile, first_tile + tile_stride, ... (num_tiles >= 1 of them) lie in the W x H frame.
 bool tiles_in_frame(uint32_t W, uint32_t H, uint32_t first_tile, uint32_t tile_stride, uint32_t num_tiles) {

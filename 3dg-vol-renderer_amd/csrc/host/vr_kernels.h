@@ -6,9 +6,10 @@ namespace vr {
 
 // kernels/vr_gauss_*.hip, a unit per pipeline stage (kernels/vr_gauss_common.h): march (gauss_march, gauss_bin,
 // gauss_bin_scan), secondary (gauss_secondary), shade (gauss_accumulate, gauss_record_cut), tree (the others)
-hipError_t gauss_march(const RenderArgs& A, hipStream_t stream, bool stats);
+// (grid: a ray grid's rays and transmittance output, vr_render_rays; nullptr: a camera frame)
+hipError_t gauss_march(const RenderArgs& A, hipStream_t stream, bool stats, const GridSrc* grid = nullptr);
 hipError_t gauss_secondary(const RenderArgs& A, hipStream_t stream, bool stats);
-hipError_t gauss_accumulate(const RenderArgs& A, hipStream_t stream);
+hipError_t gauss_accumulate(const RenderArgs& A, hipStream_t stream, float* out_tr = nullptr);
 hipError_t gauss_record_cut(const RenderArgs& A, float budget, hipStream_t stream);
 hipError_t gauss_whiten(const GaussianRecord* rec, WRecord* out, uint32_t n, uint32_t* bad, hipStream_t stream);
 hipError_t gauss_bin(const RenderArgs& A, bool emit, hipStream_t stream);
@@ -41,8 +42,12 @@ hipError_t query_events_fill(const RenderArgs& A, const vr_ray* rays, uint32_t n
 hipError_t query_pack_rays(const float* o, const float* d, const float* tmax, uint32_t tmax_stride, uint32_t n, vr_ray* rays,
                            hipStream_t s);
 
+// kernels/vr_ray_extent.hip: *out = the bits of the largest distance from a ray's origin to the farthest corner of
+// the box, over the valid rays that hit the box (0: none does)
+hipError_t ray_extent(const vr_ray* rays, uint32_t n, const float bmin[3], const float bmax[3], uint32_t* out, hipStream_t s);
+
 // kernels/vr_spheres.hip
-hipError_t launch_render(const RenderArgs& A, hipStream_t stream, int volume_type, int integrator);
+hipError_t launch_render(const RenderArgs& A, hipStream_t stream, int volume_type, int integrator, const GridSrc* grid = nullptr);
 hipError_t launch_unshuffle(const float* slabs, uint32_t nslabs, uint32_t tiles_per_slab, uint32_t tiles_x, uint32_t W,
                             uint32_t H, float* img, hipStream_t stream);
 hipError_t launch_unshuffle_part(const float* slabs, uint32_t first, uint32_t nslabs, uint32_t stride, uint32_t tiles_per_slab,

@@ -288,11 +288,23 @@ __device__ __forceinline__ void union_walk_simt(uint32_t steps, Ctr& c) {
 // (Measured and not kept, DESIGN.md §3: window queries starting in the subtree holding the window and climbing,
 // a fast-form pre-test of the candidates, look-ahead windows over 2-4 steps, a closest-entry query merged with
 // the following entrant query, a sorting network in the entrant walk; all bit-identical, all slower at C4.)
-template <int ACT, bool S, bool H, bool W = false, int CAP = kStackSize, bool COOP = false, int DEEP = 0>
-__device__ int march(const RenderArgs& A, uint32_t p, int px, int py, int* act_base, int* stack, int stride, Ctr& c,
+// RAYS: the pixel marches its row of the caller's ray grid (GridArgs) instead of the camera's ray; everything after the
+// ray is the frame's. An invalid row (grid_ray) ends the pixel at once: NaN transmittance, no records, no error count.
+template <int ACT, bool S, bool H, bool W = false, int CAP = kStackSize, bool COOP = false, int DEEP = 0, bool RAYS = false>
+__device__ int march(const FrameArgs<RAYS>& A, uint32_t p, int px, int py, int* act_base, int* stack, int stride, Ctr& c,
                      int act_stride = -1) {
     const bool writer = !COOP || __lane_id() == 0u;  // COOP: lane 0 writes the pixel's records
-    const Ray ray = primary_ray(A, px, py);
+    bool ray_ok = true;
+    const Ray ray = pixel_ray<RAYS>(A, px, py, ray_ok);
+    if constexpr (RAYS) {
+        if (!ray_ok) {
+            if (writer) {
+                A.px_first[p] = kNoRecord;
+                A.px_T[p] = __builtin_nanf("");
+            }
+            return kOK;
+        }
+    }
     const GaussianRecord* __restrict__ G = A.gauss;
     const float* __restrict__ ts = A.tsteps;
     const int nts = A.num_tsteps;
@@ -424,8 +436,8 @@ __device__ __forceinline__ void orphan_records(const RenderArgs& A, uint32_t p) 
         reinterpret_cast<float*>(A.rec_pos + r)[3] = kOrphanWeight;
 }
 
-template <int ACT, int BLOCK, bool S, int STACK, bool H, bool W = false>
-__global__ __launch_bounds__(BLOCK) void march_kernel(RenderArgs A) {
+template <int ACT, int BLOCK, bool S, int STACK, bool H, bool W = false, bool RAYS = false>
+__global__ __launch_bounds__(BLOCK) void march_kernel(FrameArgs<RAYS> A) {
     __shared__ int s_act[ACT * BLOCK];
     __shared__ int s_stack[STACK * BLOCK];
     // A workgroup is one 16x16 tile (BLOCK 256) or one of its 8x8 quarters (BLOCK 64: four times as
@@ -440,7 +452,7 @@ __global__ __launch_bounds__(BLOCK) void march_kernel(RenderArgs A) {
     Ctr c{};
     int st = kOK;
     if (x < (int)A.width && y < (int)A.height) {
-        st = march<ACT, S, H, W, STACK, false, W ? VR_MARCH_DEEP : 0>(A, p, x, y, s_act + threadIdx.x, s_stack + threadIdx.x, BLOCK, c);
+        st = march<ACT, S, H, W, STACK, false, W ? VR_MARCH_DEEP : 0, RAYS>(A, p, x, y, s_act + threadIdx.x, s_stack + threadIdx.x, BLOCK, c);
     } else {
         A.px_first[p] = kNoRecord;
         A.px_T[p] = 0.0f;
@@ -459,8 +471,8 @@ __global__ __launch_bounds__(BLOCK) void march_kernel(RenderArgs A) {
 // The fallback passes march one pixel per wave (march<COOP>): a pixel lands here because its active
 // set is large, and its serial march was the tail of the whole march stage (~1 ms at C4, also for a
 // 1/8 multi-GPU share). BLOCK = one wave.
-template <int ACT, int BLOCK, bool S, bool H, bool W = false>
-__global__ __launch_bounds__(BLOCK) void march_fallback_kernel(RenderArgs A) {
+template <int ACT, int BLOCK, bool S, bool H, bool W = false, bool RAYS = false>
+__global__ __launch_bounds__(BLOCK) void march_fallback_kernel(FrameArgs<RAYS> A) {
     static_assert(BLOCK == 64, "one pixel per wave");
     __shared__ int s_act[ACT * BLOCK];
     __shared__ int s_stack[kStackSize * BLOCK];
@@ -474,7 +486,7 @@ __global__ __launch_bounds__(BLOCK) void march_fallback_kernel(RenderArgs A) {
         Ctr c{};
         // (W: the 4-wide walks — half the dependent node fetches of the pair tree on a single pixel's
         // serial queries; a walk past the kStackSize stack goes to the deep pass)
-        int st = march<ACT, S, H, W, kStackSize, true>(A, p, x, y, s_act + tid, s_stack + tid, BLOCK, c);  // re-links px_first
+        int st = march<ACT, S, H, W, kStackSize, true, 0, RAYS>(A, p, x, y, s_act + tid, s_stack + tid, BLOCK, c);  // re-links px_first
         if (tid != 0) continue;
         if constexpr (S)
             for (int i = 0; i < kNumCtr; ++i) atomicAdd(A.work + i, (unsigned long long)c.v[i]);
@@ -496,8 +508,8 @@ __global__ __launch_bounds__(BLOCK) void march_fallback_kernel(RenderArgs A) {
 // queues shorter than A.wide_min (C4: 833 pixels). Same march<> operations as every other pass, so
 // a pixel's records do not depend on which pass marched it. Overflow (more than kActWide active, or a
 // 4-wide walk past its stack): the deep pass.
-template <bool S, bool H, bool W>
-__global__ __launch_bounds__(kWideBlock) void march_wide_kernel(RenderArgs A) {
+template <bool S, bool H, bool W, bool RAYS = false>
+__global__ __launch_bounds__(kWideBlock) void march_wide_kernel(FrameArgs<RAYS> A) {
     __shared__ int s_stack[kStackSize * kWideBlock];
     const int tid = threadIdx.x;
     const uint32_t gt = blockIdx.x * kWideBlock + tid, nthreads = gridDim.x * kWideBlock;
@@ -508,7 +520,7 @@ __global__ __launch_bounds__(kWideBlock) void march_wide_kernel(RenderArgs A) {
         const uint32_t p = A.queue[1 + q];
         int lx, ly, x, y;
         tile_pixel(A, p >> 8, (int)(p & 255u), lx, ly, x, y);
-        const int st = march<kActWide, S, H, W, kStackSize>(A, p, x, y, A.wide_act + gt, s_stack + tid, kWideBlock, c, (int)nthreads);
+        const int st = march<kActWide, S, H, W, kStackSize, false, 0, RAYS>(A, p, x, y, A.wide_act + gt, s_stack + tid, kWideBlock, c, (int)nthreads);
         if (st == kOverflow) {
             orphan_records(A, p);
             const uint32_t slot = atomicAdd(A.deepq, 1u);
@@ -524,8 +536,8 @@ __global__ __launch_bounds__(kWideBlock) void march_wide_kernel(RenderArgs A) {
 // Pixels whose active set outgrew the fallback's 64 LDS slots: the same march with the active list in
 // global memory (kActDeep slots per lane, [slot][thread] rows, one pixel per wave).
 // Only an active set past kActDeep, Gaussians overlapping one point, fails (NaN, VR_ERR_OVERFLOW).
-template <bool S, bool H>
-__global__ __launch_bounds__(kDeepBlock) void march_deep_kernel(RenderArgs A) {
+template <bool S, bool H, bool RAYS = false>
+__global__ __launch_bounds__(kDeepBlock) void march_deep_kernel(FrameArgs<RAYS> A) {
     static_assert(kDeepBlock == 64, "one pixel per wave");
     __shared__ int s_stack[kStackSize * kDeepBlock];
     const int tid = threadIdx.x;
@@ -537,7 +549,7 @@ __global__ __launch_bounds__(kDeepBlock) void march_deep_kernel(RenderArgs A) {
         tile_pixel(A, p >> 8, (int)(p & 255u), lx, ly, x, y);
         Ctr c{};
         const int st =
-            march<kActDeep, S, H, false, kStackSize, true>(A, p, x, y, A.deep_act + gt, s_stack + tid, kDeepBlock, c, (int)nthreads);
+            march<kActDeep, S, H, false, kStackSize, true, 0, RAYS>(A, p, x, y, A.deep_act + gt, s_stack + tid, kDeepBlock, c, (int)nthreads);
         if (tid != 0) continue;
         if constexpr (S)
             for (int i = 0; i < kNumCtr; ++i) atomicAdd(A.work + i, (unsigned long long)c.v[i]);
@@ -849,46 +861,52 @@ hipError_t gauss_bin_scan(const uint32_t* cnt, uint32_t* off, uint32_t n, void* 
     return hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, cnt, off, (int)n, stream);
 }
 
-template <bool S, bool H>
-static hipError_t march_pass(const RenderArgs& A, hipStream_t stream) {
+// RAYS: a ray grid (never binned: the bins are built from the camera's tile frusta).
+template <bool S, bool H, bool RAYS = false>
+static hipError_t march_pass(const FrameArgs<RAYS>& A, hipStream_t stream) {
     // LDS per 256-lane workgroup = (active-list slots + stack entries) * 1 KiB. Shallow trees use a
     // 24-entry stack; the 16-slot active list overflows to the 64-slot fallback kernel. H: the
     // half-precision node copy (boxes only propose candidates; every decision is the exact quadratic).
     const bool shallow = A.bvh_depth <= kShallowStack + 1;
-    if (A.bin_ent != nullptr)  // binned march (its overflowing pixels re-run in the BVH fallback below)
-        hipLaunchKernelGGL((dev::march_binned_kernel<S>), dim3(A.num_tiles * 4), dim3(64), 0, stream, A);
+    if (!RAYS && A.bin_ent != nullptr)  // binned march (its overflowing pixels re-run in the BVH fallback below)
+        hipLaunchKernelGGL((dev::march_binned_kernel<S>), dim3(A.num_tiles * 4), dim3(64), 0, stream, static_cast<const RenderArgs&>(A));
     else if (H && A.hnodes4 != nullptr && A.march_big)  // translucent, densely overlapping scenes (C2): fewer
         // pixels overflow, and their records come from coherent quarter tiles instead of the fallback queue
-        hipLaunchKernelGGL((dev::march_kernel<kActBig, kBlockFast, S, VR_MARCH_STACK4, true, true>), dim3(A.num_tiles * (256 / kBlockFast)),
+        hipLaunchKernelGGL((dev::march_kernel<kActBig, kBlockFast, S, VR_MARCH_STACK4, true, true, RAYS>), dim3(A.num_tiles * (256 / kBlockFast)),
                            dim3(kBlockFast), 0, stream, A);
     else if (H && A.hnodes4 != nullptr)  // 4-wide tree; a query that could overflow the stack goes to the fallback
-        hipLaunchKernelGGL((dev::march_kernel<kActFast, kBlockFast, S, VR_MARCH_STACK4, true, true>), dim3(A.num_tiles * (256 / kBlockFast)),
+        hipLaunchKernelGGL((dev::march_kernel<kActFast, kBlockFast, S, VR_MARCH_STACK4, true, true, RAYS>), dim3(A.num_tiles * (256 / kBlockFast)),
                            dim3(kBlockFast), 0, stream, A);
     else if (shallow)
-        hipLaunchKernelGGL((dev::march_kernel<kActFast, kBlockFast, S, kShallowStack, H>), dim3(A.num_tiles * (256 / kBlockFast)),
+        hipLaunchKernelGGL((dev::march_kernel<kActFast, kBlockFast, S, kShallowStack, H, false, RAYS>), dim3(A.num_tiles * (256 / kBlockFast)),
                            dim3(kBlockFast), 0, stream, A);
     else
-        hipLaunchKernelGGL((dev::march_kernel<kActFast, kBlockFast, S, kStackSize, H>), dim3(A.num_tiles * (256 / kBlockFast)),
+        hipLaunchKernelGGL((dev::march_kernel<kActFast, kBlockFast, S, kStackSize, H, false, RAYS>), dim3(A.num_tiles * (256 / kBlockFast)),
                            dim3(kBlockFast), 0, stream, A);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (H && A.hnodes4 != nullptr)  // the one-pixel-per-wave fallback march walks the 4-wide tree
-        hipLaunchKernelGGL((dev::march_fallback_kernel<kActFallback, kBlockFallback, S, H, true>), dim3(1024), dim3(kBlockFallback), 0,
+        hipLaunchKernelGGL((dev::march_fallback_kernel<kActFallback, kBlockFallback, S, H, true, RAYS>), dim3(1024), dim3(kBlockFallback), 0,
                            stream, A);
     else
-        hipLaunchKernelGGL((dev::march_fallback_kernel<kActFallback, kBlockFallback, S, H>), dim3(1024), dim3(kBlockFallback), 0,
+        hipLaunchKernelGGL((dev::march_fallback_kernel<kActFallback, kBlockFallback, S, H, false, RAYS>), dim3(1024), dim3(kBlockFallback), 0,
                            stream, A);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (H && A.hnodes4 != nullptr)  // (exactly one of the two passes takes the queue, by its length)
-        hipLaunchKernelGGL((dev::march_wide_kernel<S, H, true>), dim3(kWideThreads / kWideBlock), dim3(kWideBlock), 0, stream, A);
+        hipLaunchKernelGGL((dev::march_wide_kernel<S, H, true, RAYS>), dim3(kWideThreads / kWideBlock), dim3(kWideBlock), 0, stream, A);
     else
-        hipLaunchKernelGGL((dev::march_wide_kernel<S, H, false>), dim3(kWideThreads / kWideBlock), dim3(kWideBlock), 0, stream, A);
+        hipLaunchKernelGGL((dev::march_wide_kernel<S, H, false, RAYS>), dim3(kWideThreads / kWideBlock), dim3(kWideBlock), 0, stream, A);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL((dev::march_deep_kernel<S, H>), dim3(kDeepThreads / kDeepBlock), dim3(kDeepBlock), 0, stream, A);
+    hipLaunchKernelGGL((dev::march_deep_kernel<S, H, RAYS>), dim3(kDeepThreads / kDeepBlock), dim3(kDeepBlock), 0, stream, A);
     return hipGetLastError();
 }
 
-hipError_t gauss_march(const RenderArgs& A, hipStream_t stream, bool stats) {
+hipError_t gauss_march(const RenderArgs& A, hipStream_t stream, bool stats, const GridSrc* grid) {
+    if (grid != nullptr) {  // a ray grid (no instrumented build: vr_count_work takes a camera)
+        if (stats) return hipErrorInvalidValue;
+        const GridArgs G{A, *grid};
+        return A.hnodes != nullptr ? march_pass<false, true, true>(G, stream) : march_pass<false, false, true>(G, stream);
+    }
     if (A.hnodes != nullptr) return stats ? march_pass<true, true>(A, stream) : march_pass<false, true>(A, stream);
     return stats ? march_pass<true, false>(A, stream) : march_pass<false, false>(A, stream);
 }

@@ -119,7 +119,9 @@ __global__ __launch_bounds__(kRadBlock) void record_radiance_kernel(RenderArgs A
     }
 }
 
-__global__ __launch_bounds__(256) void accumulate_kernel(RenderArgs A) {
+// TR: a ray grid that asked for the transmittance left at the end of its primary march (out_tr, W x H row-major).
+template <bool TR>
+__device__ __forceinline__ void accumulate(const RenderArgs& A, [[maybe_unused]] float* __restrict__ out_tr) {
     const uint32_t tile_local = blockIdx.x;
     const int tid = threadIdx.x;
     const uint32_t p = tile_local * 256u + (uint32_t)tid;
@@ -140,7 +142,11 @@ __global__ __launch_bounds__(256) void accumulate_kernel(RenderArgs A) {
     }
     const float T = A.px_T[p];
     store_px(A, tile_local, lx, ly, x, y, L0 + T * A.env[0], L1 + T * A.env[1], L2 + T * A.env[2]);
+    if constexpr (TR) out_tr[(size_t)y * A.width + (size_t)x] = T;
 }
+
+__global__ __launch_bounds__(256) void accumulate_kernel(RenderArgs A) { accumulate<false>(A, nullptr); }
+__global__ __launch_bounds__(256) void accumulate_tr_kernel(RenderArgs A, float* __restrict__ out_tr) { accumulate<true>(A, out_tr); }
 
 }  // namespace dev
 
@@ -153,7 +159,7 @@ hipError_t gauss_record_cut(const RenderArgs& A, float budget, hipStream_t strea
     return hipGetLastError();
 }
 
-hipError_t gauss_accumulate(const RenderArgs& A, hipStream_t stream) {
+hipError_t gauss_accumulate(const RenderArgs& A, hipStream_t stream, float* out_tr) {
     {  // (also with no secondary rays: Le = 0 / 0 reproduces the reference's NaN for env_samples = 0)
         const dim3 grid(record_grid(A, A.chunk_rec, 65536));
         if (A.env_order != nullptr)  // <= 64 KB of LDS: env_samples <= kEnvOrderMax, lights <= kMaxLights
@@ -164,7 +170,8 @@ hipError_t gauss_accumulate(const RenderArgs& A, hipStream_t stream) {
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(dev::accumulate_kernel, dim3(A.num_tiles), dim3(256), 0, stream, A);
+    if (out_tr != nullptr) hipLaunchKernelGGL(dev::accumulate_tr_kernel, dim3(A.num_tiles), dim3(256), 0, stream, A, out_tr);
+    else hipLaunchKernelGGL(dev::accumulate_kernel, dim3(A.num_tiles), dim3(256), 0, stream, A);
     return hipGetLastError();
 }
 

@@ -87,14 +87,25 @@ __device__ float sphere_transmittance(const RenderArgs& A, const Ray& r, uint32_
     return T;
 }
 
-__device__ void march_spheres(const RenderArgs& A, int px, int py, float& R0, float& R1, float& R2) {
-    const Ray ray = primary_ray(A, px, py);
+// RAYS: the pixel's row of the caller's ray grid instead of the camera's ray (pixel_ray); an invalid row gives NaN.
+// Tend: the transmittance left at the end of the march (what multiplies the environment colour).
+template <bool RAYS>
+__device__ void march_spheres(const FrameArgs<RAYS>& A, int px, int py, float& R0, float& R1, float& R2, float& Tend) {
+    bool ray_ok = true;
+    const Ray ray = pixel_ray<RAYS>(A, px, py, ray_ok);
+    if constexpr (RAYS) {
+        if (!ray_ok) {
+            R0 = R1 = R2 = Tend = __builtin_nanf("");
+            return;
+        }
+    }
     SEvt ev[2 * kMaxSpheresDev];
     int n = sphere_events(A, ray, ev);
     if (n == 0) {
         R0 = A.env[0];
         R1 = A.env[1];
         R2 = A.env[2];
+        Tend = 1.0f;
         return;
     }
     const float* __restrict__ ts = A.tsteps;
@@ -163,29 +174,51 @@ __device__ void march_spheres(const RenderArgs& A, int px, int py, float& R0, fl
     R0 = L0 + T * A.env[0];
     R1 = L1 + T * A.env[1];
     R2 = L2 + T * A.env[2];
+    Tend = T;
+}
+
+// The ray grid's transmittance output (W x H row-major; grids are never packed), if it was asked for.
+__device__ __forceinline__ void store_tr(const GridArgs& A, int x, int y, float T) {
+    if (A.grid.out_tr != nullptr && x < (int)A.width && y < (int)A.height) A.grid.out_tr[(size_t)y * A.width + (size_t)x] = T;
 }
 
 __global__ __launch_bounds__(256) void rm_spheres_kernel(RenderArgs A) {
     const uint32_t tile_local = xcd_tile(blockIdx.x, gridDim.x);
     int lx, ly, x, y;
     tile_pixel(A, tile_local, threadIdx.x, lx, ly, x, y);
-    float r = 0.0f, g = 0.0f, b = 0.0f;
-    if (x < (int)A.width && y < (int)A.height) march_spheres(A, x, y, r, g, b);
+    float r = 0.0f, g = 0.0f, b = 0.0f, T = 0.0f;
+    if (x < (int)A.width && y < (int)A.height) march_spheres<false>(A, x, y, r, g, b, T);
     store_px(A, tile_local, lx, ly, x, y, r, g, b);
 }
 
+// rm_spheres_kernel for a ray grid (vr_render_rays): the same march along the caller's rays, and its final T if asked.
+__global__ __launch_bounds__(256) void rm_spheres_rays_kernel(GridArgs A) {
+    const uint32_t tile_local = xcd_tile(blockIdx.x, gridDim.x);
+    int lx, ly, x, y;
+    tile_pixel(A, tile_local, threadIdx.x, lx, ly, x, y);
+    float r = 0.0f, g = 0.0f, b = 0.0f, T = 0.0f;
+    if (x < (int)A.width && y < (int)A.height) march_spheres<true>(A, x, y, r, g, b, T);
+    store_px(A, tile_local, lx, ly, x, y, r, g, b);
+    store_tr(A, x, y, T);
+}
+
 // TestIntegrator: magenta where the primary ray has any event, env colour elsewhere.
-template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void hitmask_kernel(RenderArgs A, int spheres) {
+// RAYS: a ray grid; its transmittance output is 0 where the ray has an event and 1 where it has none (the
+// environment colour shows), NaN with the colour for an invalid row.
+template <int BLOCK, bool RAYS = false>
+__global__ __launch_bounds__(BLOCK) void hitmask_kernel(FrameArgs<RAYS> A, int spheres) {
     __shared__ int s_stack[kStackSize * BLOCK];
     const uint32_t tile_local = xcd_tile(blockIdx.x, gridDim.x);
     int lx, ly, x, y;
     tile_pixel(A, tile_local, threadIdx.x, lx, ly, x, y);
     float r = 0.0f, g = 0.0f, b = 0.0f;
+    [[maybe_unused]] float T = 0.0f;
     if (x < (int)A.width && y < (int)A.height) {
-        const Ray ray = primary_ray(A, x, y);
+        bool ray_ok = true;
+        const Ray ray = pixel_ray<RAYS>(A, x, y, ray_ok);
         bool any = false;
-        if (spheres) {
+        if (RAYS && !ray_ok) {
+        } else if (spheres) {
             for (int i = 0; i < A.num_prims && !any; ++i) {
                 float te, tx;
                 any = sphere_hit(A.spheres[i], ray, te, tx);
@@ -203,8 +236,13 @@ __global__ __launch_bounds__(BLOCK) void hitmask_kernel(RenderArgs A, int sphere
         }
         if (any) { r = 1.0f; g = 0.0f; b = 1.0f; }
         else { r = A.env[0]; g = A.env[1]; b = A.env[2]; }
+        if constexpr (RAYS) {
+            T = any ? 0.0f : 1.0f;
+            if (!ray_ok) r = g = b = T = __builtin_nanf("");
+        }
     }
     store_px(A, tile_local, lx, ly, x, y, r, g, b);
+    if constexpr (RAYS) store_tr(A, x, y, T);
 }
 
 // Slabs (rank r holds tiles r, r + nslabs, ...) -> row-major frame.
@@ -232,13 +270,18 @@ __global__ void unshuffle_kernel(const float* __restrict__ slabs, uint32_t first
 
 }  // namespace dev
 
-hipError_t launch_render(const RenderArgs& A, hipStream_t stream, int volume_type, int integrator) {
+hipError_t launch_render(const RenderArgs& A, hipStream_t stream, int volume_type, int integrator, const GridSrc* grid_src) {
     dim3 grid(A.num_tiles);
+    GridArgs G{A, {nullptr, nullptr}};  // a ray grid (vr_render_rays): its own instantiations
+    if (grid_src != nullptr) G.grid = *grid_src;
     if (integrator == VR_TEST_HITMASK) {
-        hipLaunchKernelGGL((dev::hitmask_kernel<256>), grid, dim3(256), 0, stream, A, volume_type == VR_VOLUME_SPHERES ? 1 : 0);
+        const int spheres = volume_type == VR_VOLUME_SPHERES ? 1 : 0;
+        if (grid_src != nullptr) hipLaunchKernelGGL((dev::hitmask_kernel<256, true>), grid, dim3(256), 0, stream, G, spheres);
+        else hipLaunchKernelGGL((dev::hitmask_kernel<256>), grid, dim3(256), 0, stream, A, spheres);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(dev::rm_spheres_kernel, grid, dim3(256), 0, stream, A);
+    if (grid_src != nullptr) hipLaunchKernelGGL(dev::rm_spheres_rays_kernel, grid, dim3(256), 0, stream, G);
+    else hipLaunchKernelGGL(dev::rm_spheres_kernel, grid, dim3(256), 0, stream, A);
     return hipGetLastError();
 }
 

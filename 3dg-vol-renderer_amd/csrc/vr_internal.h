@@ -5,6 +5,8 @@
 #include <hip/hip_vector_types.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace vr {
 
 // ------------------------------------------------------------------------------------------
@@ -253,5 +255,18 @@ struct RenderArgs {
     uint32_t rec_npix;       // W * H
     const unsigned long long* pcg_jump;  // [2k] = A^k, [2k+1] = inc (A^(k-1) + ... + 1): PCG32 state after k draws
 };
+
+// A ray grid's own arguments (vr_render_rays). They travel beside RenderArgs, to the grid instantiations of the
+// kernels only (GridArgs): the camera kernels' argument block, and what they keep of it in registers or scratch,
+// is unchanged by them.
+struct GridSrc {
+    const float4* rays;  // W x H vr_ray rows, row-major: pixel (x, y) marches rows 2 (y W + x), + 1 in place of the camera's ray
+    float* out_tr;       // W x H: the transmittance left at the end of the primary march (nullptr: not asked for)
+};
+struct GridArgs : RenderArgs {
+    GridSrc grid;
+};
+template <bool RAYS>
+using FrameArgs = std::conditional_t<RAYS, GridArgs, RenderArgs>;  // the argument block of a kernel's RAYS instantiation
 
 }  // namespace vr

@@ -54,6 +54,30 @@ public:
         apply_solver(ctx);
         vr_cpp::check(vr_render(ctx, &camera->state(), &params_, image.get_width(), image.get_height(), image.data()));
     }
+    // Radiance along the caller's own rays (vr_render_rays, include/vr_hip.h): `rays` is a W x H grid in row-major
+    // order, rendered by the ray-march integrators exactly as a frame is, pixel (x, y) marching rays[y * W + x]
+    // in place of the camera's ray (the integrator's camera is not read). A Ray's direction was normalised by its
+    // constructor (ray.h:11-12): it goes to the device as it stands (unit = 1), as MixtureQuery passes its rays.
+    // *transmittance (if given) receives the W * H transmittances left at the end of the primary marches. The
+    // free-flight integrators throw (VR_ERR_UNSUPPORTED). Runs on the context's first device.
+    void render_rays(const Scene& scene, const std::vector<Ray>& rays, uint32_t W, uint32_t H, Image& out,
+                     std::vector<float>* transmittance = nullptr) {
+        if (rays.size() != (size_t)W * H) throw std::runtime_error("render_rays: W * H rays expected");
+        if (out.get_width() != W || out.get_height() != H) throw std::runtime_error("render_rays: the image is not W x H");
+        std::vector<vr_ray> r(rays.size());
+        for (size_t i = 0; i < rays.size(); ++i) {
+            for (int k = 0; k < 3; ++k) {
+                r[i].origin[k] = rays[i].origin[k];
+                r[i].direction[k] = rays[i].direction[k];
+            }
+            r[i].tmax = 0.0f;
+            r[i].unit = 1.0f;
+        }
+        vr_ctx* ctx = context();
+        upload(ctx, scene);
+        if (transmittance) transmittance->assign(rays.size(), 0.0f);
+        vr_cpp::check(vr_render_rays(ctx, r.data(), W, H, &params_, out.data(), transmittance ? transmittance->data() : nullptr));
+    }
     // re-upload when the scene (or the scene object) changed since the last upload to this context
     static void upload(vr_ctx* ctx, const Scene& scene) {
         vr_scene* ns = scene.native();

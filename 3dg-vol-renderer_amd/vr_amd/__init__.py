@@ -24,7 +24,7 @@ __all__ = [
     "Integrator", "RayMarchingGaussians", "PureRayMarching", "RayMarchingSpheres", "FreeFlightGaussians",
     "MultiScatterGaussians", "bits_to_lists", "TestIntegrator", "Device",
     "load_xml",
-    "num_tiles",
+    "num_tiles", "RAY_BATCH_WIDTH",
 ]
 
 
@@ -656,6 +656,58 @@ def _query_point_args(points):
     return _query_f32(points, "points", (3,))
 
 
+# ---- ray grids (vr_render_rays, include/vr_hip.h): Integrator.render_rays ----
+RAY_BATCH_WIDTH = 256  # a flat (n, 3) batch is rendered as a grid of this width: ray i sits at (i % 256, i // 256)
+_MAX_GRID_EDGE = 65535  # vr_render_rays: width and height lie in [1, 65535]
+
+
+def _ray_grid_layout(origins, directions):
+    """Checks the ray arguments of render_rays before anything reaches the library. Returns (torch input?,
+    grid width, grid height, number of rays, leading shape of the results): an (H, W, 3) pair is a W x H grid; an
+    (n, 3) pair a flat batch laid out RAY_BATCH_WIDTH wide and ceil(n / RAY_BATCH_WIDTH) high, whose last row
+    is padded. ValueError otherwise."""
+    kinds = []
+    for x, name in ((origins, "origins"), (directions, "directions")):
+        if _is_torch(x):
+            import torch
+            ok_dtype = x.dtype == torch.float32
+        elif isinstance(x, np.ndarray):
+            ok_dtype = x.dtype == np.float32
+        else:
+            raise ValueError(f"{name} must be a numpy array or a torch tensor, not {type(x).__name__}")
+        if not ok_dtype:
+            raise ValueError(f"{name} must be float32, not {x.dtype}")
+        if len(x.shape) not in (2, 3) or x.shape[-1] != 3:
+            raise ValueError(f"{name} must have shape (H, W, 3) or (n, 3), not {tuple(x.shape)}")
+        kinds.append(_is_torch(x))
+    if kinds[0] != kinds[1]:
+        raise ValueError("origins and directions must both be numpy arrays or both torch tensors")
+    if tuple(origins.shape) != tuple(directions.shape):
+        raise ValueError(f"origins have shape {tuple(origins.shape)} but directions {tuple(directions.shape)}")
+    lead = tuple(int(k) for k in origins.shape[:-1])
+    if len(lead) == 2:
+        H, W = lead
+        n = W * H
+    else:
+        n = lead[0]
+        if n > RAY_BATCH_WIDTH * _MAX_GRID_EDGE:
+            raise ValueError(f"{n} rays in one flat batch: at most {RAY_BATCH_WIDTH * _MAX_GRID_EDGE} (split it)")
+        W, H = RAY_BATCH_WIDTH, -(-n // RAY_BATCH_WIDTH)
+    if not (1 <= W <= _MAX_GRID_EDGE and 1 <= H <= _MAX_GRID_EDGE):
+        raise ValueError(f"a ray grid's width and height must be in [1, {_MAX_GRID_EDGE}], not {W} x {H}")
+    return kinds[0], W, H, n, lead
+
+
+def _pack_ray_grid_numpy(origins, directions, unit, W, H, n):
+    """The W x H vr_ray rows of n rays (W * H >= n): origin, tmax (unread), direction, unit. Rows past the
+    n-th, the pad of a flat batch's last grid row, have a zero direction (invalid: NaN results, dropped)."""
+    rays = np.zeros((W * H, 8), np.float32)
+    rays[:n, 0:3] = origins.reshape(n, 3)
+    rays[:n, 4:7] = directions.reshape(n, 3)
+    rays[:n, 7] = 1.0 if unit else 0.0
+    return rays
+
+
 def num_tiles(width, height):
     return int(lib().vr_num_tiles(width, height))
 
@@ -696,6 +748,56 @@ class Integrator:
         image.pixels[...] = out
         self.last_stats = dev.stats()
         return image
+
+    def render_rays(self, scene, origins, directions, unit=False, return_transmittance=False):
+        """Radiance along the caller's own rays (vr_render_rays, include/vr_hip.h): the ray-march integrators
+        render a grid of rays exactly as they render a frame, pixel (x, y) marching its own ray in place of the
+        camera's (the integrator's camera is not read). origins, directions: float32, (H, W, 3) for a W x H grid
+        or (n, 3) for a flat batch (laid out RAY_BATCH_WIDTH wide; the environment samples of ray i are keyed by
+        its grid position (i % 256, i // 256)). unit: the directions are normalised already and are used as
+        they stand (a Ray object's; otherwise they get the Ray constructor's one normalisation).
+        numpy arrays go through the host entry point; torch tensors on this integrator's GPU through the device
+        one on torch's current stream, with no host copy (the call waits for that stream). Returns rgb with
+        the inputs' leading shape + (3,), of the inputs' kind; with return_transmittance, (rgb, tr), tr being the
+        transmittance left at the end of each primary march (rgb - tr * env + tr * background composites over
+        another background). A ray with a non-finite origin or a zero / non-finite direction gives NaN."""
+        if self.integrator_id in (L.VR_FREE_FLIGHT, L.VR_MULTI_SCATTER):
+            raise VRError(L.VR_ERR_UNSUPPORTED, f"{type(self).__name__}.render_rays: the free-flight integrators jitter "
+                          "the sensor position of every sample, which a fixed ray does not have (ray-march integrators only)")
+        torch_in, W, H, n, lead = _ray_grid_layout(origins, directions)
+        dev = self._device(scene)
+        if torch_in:
+            import torch
+            dev._check_torch(origins, directions)
+            rays = torch.zeros((W * H, 8), dtype=torch.float32, device=origins.device)  # (pad rows: zero direction)
+            zero = torch.zeros(1, dtype=torch.float32, device=origins.device)
+            stream = torch.cuda.current_stream(origins.device).cuda_stream
+            check(lib().vr_query_pack_rays_device(dev._h, origins.reshape(n, 3).contiguous().data_ptr(),
+                                                  directions.reshape(n, 3).contiguous().data_ptr(), zero.data_ptr(), 0, n,
+                                                  rays.data_ptr(), stream))
+            if unit:
+                rays[:n, 7] = 1.0
+            rgb = torch.empty((W * H, 3), dtype=torch.float32, device=origins.device)
+            tr = torch.empty(W * H, dtype=torch.float32, device=origins.device) if return_transmittance else None
+            for attempt in range(3):  # a grid that outgrew the record buffers of earlier frames is rendered again
+                check(lib().vr_render_rays_device(dev._h, rays.data_ptr(), W, H, ctypes.byref(self.params), rgb.data_ptr(),
+                                                  tr.data_ptr() if return_transmittance else None, stream))
+                try:
+                    dev.synchronize()
+                    break
+                except VRError as e:
+                    if attempt == 2 or e.status != L.VR_ERR_RETRY:
+                        raise
+        else:
+            rays = _pack_ray_grid_numpy(origins, directions, unit, W, H, n)
+            rgb = np.empty((W * H, 3), np.float32)
+            tr = np.empty(W * H, np.float32) if return_transmittance else None
+            check(lib().vr_render_rays(dev._h, rays.ctypes.data, W, H, ctypes.byref(self.params), fptr(rgb),
+                                       fptr(tr) if return_transmittance else None))
+        # (a multi-GPU context renders a grid on its first device: that rank's statistics)
+        self.last_stats = dev.rank_stats(0) if isinstance(dev.device, tuple) else dev.stats()
+        rgb = rgb[:n].reshape(lead + (3,))
+        return (rgb, tr[:n].reshape(lead)) if return_transmittance else rgb
 
 
 class RayMarchingGaussians(Integrator):

@@ -10,7 +10,7 @@ _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("VR_LIB_PATH") or os.path.join(_PKG_ROOT, "libvr_hip.so")  # override: A/B builds
 
 VR_OK = 0
-VR_ERR_OVERFLOW, VR_ERR_RETRY = 6, 8
+VR_ERR_INVALID, VR_ERR_OVERFLOW, VR_ERR_UNSUPPORTED, VR_ERR_RETRY = 1, 6, 7, 8
 STATUS_NAMES = {
     0: "VR_OK", 1: "VR_ERR_INVALID", 2: "VR_ERR_IO", 3: "VR_ERR_PARSE", 4: "VR_ERR_HIP",
     5: "VR_ERR_NOSCENE", 6: "VR_ERR_OVERFLOW", 7: "VR_ERR_UNSUPPORTED", 8: "VR_ERR_RETRY",
@@ -187,6 +187,9 @@ SIGNATURES = {
     "vr_query_events_fill_device": (ST, [P, P, ctypes.c_size_t, P, P, P, ctypes.c_uint64, P]),
     "vr_query_events": (ST, [P, P, ctypes.c_size_t, U32P, FP, U32P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     "vr_query_pack_rays_device": (ST, [P, P, P, P, ctypes.c_uint32, ctypes.c_size_t, P, P]),
+    "vr_render_rays": (ST, [P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(vr_render_params), FP, FP]),
+    "vr_render_rays_device": (ST, [P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(vr_render_params), P, P, P]),
+    "vr_ray_grid_extent": (ST, [P, ctypes.c_size_t, FP, FP, FP]),
     "vr_debug_pixel_records": (ST, [P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_float), ctypes.c_size_t,
                                     ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
     "vr_debug_tree": (ST, [P, ctypes.c_int32, P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),

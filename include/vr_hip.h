@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define VR_ABI_VERSION 8
+#define VR_ABI_VERSION 9
 
 typedef enum vr_status {
     VR_OK = 0,
@@ -539,6 +539,50 @@ vr_status vr_query_events(vr_ctx* ctx, const vr_ray* rays, size_t n, uint32_t* o
 vr_status vr_query_pack_rays_device(vr_ctx* ctx, const float* d_origins, const float* d_directions, const float* d_tmax,
                                     uint32_t tmax_stride, size_t n, vr_ray* d_rays, void* stream);
 
+/* ---------------- ray grids: radiance along the caller's own rays ---------------- */
+/* A ray grid is a W x H image of rays, row-major: pixel (x, y) marches rays[y * W + x] (a vr_ray row; tmax is not
+ * read) in place of the camera's ray. Everything else is the frame's, bit for bit: the step sequence t_k,
+ * activation, scatter records, light and environment rays, the environment-sample key derive_path_seed(x, y, k)
+ * of the pixel coordinates, the fallback / wide / deep passes, the exact slow path and band fix-ups, t_eps,
+ * accumulation L + T env, the statistics and the retry of a frame that outgrew its record buffers. A grid filled
+ * with a camera's own rays (vr_camera_sample_ray at ((x + 0.5f) / W, (y + 0.5f) / H) in f32, unit = 1) is that
+ * camera's frame. The caller builds the rays: light probes inside the cloud, fisheye / equirectangular /
+ * aspect-correct / distorted cameras, stereo pairs, a ray bundle a torch pipeline already holds on the device.
+ * Integrators: VR_RAYMARCH_GAUSSIANS, VR_PURE_RAYMARCH, VR_RAYMARCH_SPHERES, VR_TEST_HITMASK. VR_FREE_FLIGHT and
+ * VR_MULTI_SCATTER return VR_ERR_UNSUPPORTED: their samples jitter the sensor position inside the pixel, which a
+ * fixed ray does not have, and no reference defines what a sample of a fixed ray would be.
+ * rgb: 3 * W * H floats laid out as the full-frame render writes them. tr (may be NULL): W * H floats, the
+ * transmittance left at the end of the primary march, the factor that multiplies the environment colour, so that
+ * rgb - tr * env + tr * background composites over another background; asking for it changes no bit of rgb.
+ * For VR_RAYMARCH_SPHERES it is the march's final T; for VR_TEST_HITMASK it is 0 where the ray hits a primitive
+ * and 1 where it hits none. A ray that misses every primitive gets the environment colour exactly and tr = 1.
+ * `unit` is honoured as the queries honour it: 0, the direction gets the Ray constructor's one normalisation;
+ * non-zero, it is used as it stands and must be of unit length (the step table is sized in distances: a shorter
+ * direction runs off its end, and those pixels are reported as error pixels). A ray with a non-finite origin, or a direction whose squared norm is 0, NaN or
+ * infinite in f32, gets NaN in rgb and tr, spawns nothing and is counted nowhere (not in error_pixels: it is the
+ * caller's input, not a capacity failure); the call still returns VR_OK.
+ * The step table is sized from the rays, not from a camera: over the valid rays whose slab test hits the scene
+ * bounds, the largest distance from a ray's origin to the farthest corner of the bounds, then the larger of that
+ * and the bounds' diagonal, times 1.01 plus 1. VR_ERR_OVERFLOW, before anything is allocated, if that reach over
+ * step_size exceeds 2^24 table entries (64 MB): a ray that starts 10^7 scene units away and hits the bounds.
+ * VR_ERR_INVALID: a NULL pointer (tr excepted), width or height outside [1, 65535], a device ray array that is not
+ * 16-byte aligned; otherwise the errors of a frame. VR_OPT_MARCH_BINNED is ignored (the bins are built from a
+ * camera's tile frusta: grids always take the BVH march). On a vr_init_multi context the call runs on the first
+ * device, as the queries do.
+ * Host form: synchronous, copies in and out. Device form: d_rays, d_rgb, d_tr are device memory; the kernels
+ * are queued on `stream` (a hipStream_t, NULL: the default stream) and the frame's outcome is reported by
+ * vr_synchronize / vr_get_stats as for the tile entry point, but the call itself waits for `stream` once,
+ * before the march is queued: the extent of the rays is reduced on the device and read back (4 bytes) to size
+ * the step table, as the event count of the queries is. VR_TEST_HITMASK marches no table and does not wait. */
+vr_status vr_render_rays(vr_ctx* ctx, const vr_ray* rays, uint32_t width, uint32_t height, const vr_render_params* p,
+                         float* rgb_host, float* tr_host);
+vr_status vr_render_rays_device(vr_ctx* ctx, const vr_ray* d_rays, uint32_t width, uint32_t height,
+                                const vr_render_params* p, float* d_rgb, float* d_tr, void* stream);
+/* Diagnostics (host only, no context): the extent the step table of a ray grid is sized from, for n rays and the
+ * scene bounds [bounds_min, bounds_max] (vr_scene_info): the largest origin-to-farthest-corner distance over the
+ * valid rays whose slab test hits the bounds; 0 if none does. */
+vr_status vr_ray_grid_extent(const vr_ray* rays, size_t n, const float bounds_min[3], const float bounds_max[3],
+                             float* extent);
 
 #ifdef __cplusplus
 } /* extern "C" */
