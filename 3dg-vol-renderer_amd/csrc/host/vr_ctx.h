@@ -118,7 +118,7 @@ struct vr_ctx {
     uint32_t rec_npix[2] = {0, 0}, rec_n[2] = {0, 0};
     vr::DevBuf<std::byte> sfd_tmp;     // vr_sfd_loss_diff: losses + output
     vr::DevBuf<float> sfd_ref, sfd_loss[2];  // device inverse loop (vr_sfd_optimize): I_ref, base / perturbed losses
-    vr::DevBuf<double> sfd_out;
+    vr::DevBuf<double> sfd_out, sfd_part;  // the union statistic and its per-chunk partial sums
     // mixture queries (vr_query_*, kernels/vr_query.hip): their own workspaces, grown on demand; nothing of a
     // frame (report, statistics, hints) is touched by a query
     vr::DevBuf<std::byte> q_in, q_out2;  // host forms: the batch on the device (rays / points) and its second

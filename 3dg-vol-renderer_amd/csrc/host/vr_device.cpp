@@ -88,9 +88,11 @@ void vr_destroy(vr_ctx* c) {
 
 // out[g] (host) = d_out[g] = sum over the union of the pixels recorded for g in slots 0 and 1 of lp - lb (device losses).
 static vr_status loss_diff(vr_ctx* c, const float* lb, const float* lp, uint32_t npix, size_t n, double* d_out, double* out) {
+    VR_TRY(c->sfd_part.grow(std::max<size_t>(sfd_partial_count(npix, (uint32_t)n), 1), "hipMalloc(sfd partial sums)"));
     HIP_TRY(hipMemsetAsync(d_out, 0, n * 8, c->stream), "hipMemsetAsync");
     if (n > 0)
-        HIP_TRY(launch_sfd_loss_diff(c->rec_bits[0].get(), c->rec_bits[1].get(), lb, lp, npix, (uint32_t)n, d_out, c->stream),
+        HIP_TRY(launch_sfd_loss_diff(c->rec_bits[0].get(), c->rec_bits[1].get(), lb, lp, npix, (uint32_t)n, c->sfd_part.get(), d_out,
+                                     c->stream),
                 "sfd launch");
     HIP_TRY(hipMemcpyAsync(out, d_out, n * 8, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync");
     HIP_TRY(hipStreamSynchronize(c->stream), "sfd");

@@ -25,8 +25,10 @@ hipError_t launch_free_flight(const RenderArgs& A, uint32_t chunk_tiles, hipStre
 uint32_t free_flight_threads(int cus);
 
 // kernels/vr_loss.hip
+// (partial: sfd_partial_count(npix, n) doubles of scratch, the per-chunk sums)
+size_t sfd_partial_count(uint32_t npix, uint32_t n);
 hipError_t launch_sfd_loss_diff(const uint32_t* bits0, const uint32_t* bits1, const float* lb, const float* lp, uint32_t npix,
-                                uint32_t n, double* out, hipStream_t stream);
+                                uint32_t n, double* partial, double* out, hipStream_t stream);
 hipError_t launch_pixel_losses(const float* img, const float* ref, uint32_t npix, float* out, hipStream_t stream);
 
 // kernels/vr_query.hip

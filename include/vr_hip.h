@@ -303,7 +303,11 @@ vr_status vr_gmm_default_eps(float* eps, size_t n_params);
 vr_status vr_adam_step(float* params, const float* grads, float* m, float* v, size_t n, int32_t t, float lr, float beta1,
                        float beta2, float eps);
 /* Sign vector k of vr_sfd_optimize's run with `seed` (+1 / -1 per parameter): the deterministic
- * stand-in for the reference's coin(mt19937(random_device)) (inverse_integrator.h:101-103, 139-141). */
+ * stand-in for the reference's coin(mt19937(random_device)) (inverse_integrator.h:101-103, 139-141).
+ * The stream is the textbook PCG32 (XSH-RR 64/32) after pcg32_srandom(initstate = splitmix64(seed),
+ * initseq = splitmix64(k)), splitmix64 being the usual finaliser of x + 0x9e3779b97f4a7c15; entry i is +1
+ * where the i-th output's 24-bit uniform (output >> 8) / 2^24 is below 0.5, else -1. vr_sfd_optimize draws
+ * vector it * num_stoch_samples + j for sample j of iteration it. */
 vr_status vr_sfd_sign_vector(uint64_t seed, uint64_t k, float* signs, size_t n);
 
 /* SFDDConfig (inverse_integrator.h:52-57) + run options. */
