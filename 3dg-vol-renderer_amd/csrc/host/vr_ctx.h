@@ -104,7 +104,8 @@ struct vr_ctx {
     vr::DevBuf<float> px_T, tr, rec_cut;
     vr::DevBuf<float4> rec_pos, rec_rad;
     vr::DevBuf<uint4> rec_meta;
-    vr::DevBuf<int32_t> rec_act, stack_ovf, rec_start;
+    vr::DevBuf<int32_t> rec_act, stack_ovf;
+    vr::DevBuf<vr::RecStart> rec_start;
     vr::DevBuf<unsigned long long> rec_bloom, pcg_jump, ray_next;
     vr::DevBuf<uint16_t> env_order;
     vr::DevBuf<uint64_t> env_base;

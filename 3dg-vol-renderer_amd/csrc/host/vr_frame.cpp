@@ -336,7 +336,7 @@ vr_status gauss_pipeline(vr_ctx* c, RenderArgs& A, hipStream_t s, bool stats, co
         }
     }
     HIP_TRY(hipEventRecord(c->ev_stage[1], s), "hipEventRecord");
-    A.rec_start = nullptr;  // per record: the 4-wide subtree its secondary rays walk first (record_start_kernel)
+    A.rec_start = nullptr;  // per record: the 4-wide subtree its secondary rays walk first and its parent entry (record_start_kernel)
     if (A.hnodes4 != nullptr && A.hn4_parent != nullptr && c->opt_start_subtree) {
         VR_TRY(c->rec_start.grow(cap, "hipMalloc(record start nodes)", A.rec_start));
     }

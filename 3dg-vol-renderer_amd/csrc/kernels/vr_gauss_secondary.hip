@@ -42,6 +42,14 @@
 #ifndef VR_WW_QCAP
 #define VR_WW_QCAP 9  // leaf queue of the persistent kernel: the head entry + an LDS ring of QCAP - 1 (1 + 2^k)
 #endif
+// The ray's dependent load chain: loads whose address is known long before their data is needed are
+// issued early into registers that are dead at that time (A/B at C4, round 7: secondary stage 75.9 -> 74.8 ms with both).
+#ifndef VR_SEC_START_ENTRY
+#define VR_SEC_START_ENTRY 1  // a ray's start node and its first climb from one 8-B gather (RecStart), next to the record's words
+#endif
+#ifndef VR_SEC_UP_AHEAD
+#define VR_SEC_UP_AHEAD 1  // the climb's parent entry is loaded one level ahead (SecRay::up)
+#endif
 
 namespace vr {
 namespace dev {
@@ -89,7 +97,10 @@ struct SecRay {
     bool light, needs_stop;
     bool bnd;          // the record has a member at its 3-sigma surface (kRecBoundary): the list phase tests the band
     uint32_t nsteps;  // instrumented build only: node steps taken by this ray
-    int32_t from;     // 4-wide walk: root of the subtree the ray walks / has finished (climbs from the record's start subtree)
+    // 4-wide walk: the parent entry of the subtree the ray walks (hn4_parent's form: the subtree's child slot + 1 in
+    // bits 28-30), -1 at the root: the node of the next climb, loaded one climb ahead (sec_node4v).
+    // (VR_SEC_UP_AHEAD = 0: the root of that subtree, whose parent entry the climb loads.)
+    int32_t up;
 #ifdef VR_DIAG_LEVELS  // diagnostic builds only: this ray's node steps per tree depth (2 levels per bucket)
     uint32_t lv[8];
 #endif
@@ -223,9 +234,11 @@ __global__ __launch_bounds__(BLOCK) void env_order_kernel(RenderArgs A) {
 
 // Start ray `rem` of record chunk `chunk`. Returns false if the ray is already complete (Tr
 // written) or a padding id. norm: slab-test terms in the half nodes' scene-normalised
-// coordinates (HNode).
+// coordinates (HNode). start: the node the tree walk starts at (wide: the 4-wide walk, in the record's start subtree;
+// otherwise the root); the record's start entry is gathered here, next to its other words, so that it is no link
+// of the ray's load chain.
 __device__ __forceinline__ bool sec_init(const RenderArgs& A, uint32_t nrec, uint32_t chunk, uint32_t rem, SecRay& R,
-                                         bool norm = false) {
+                                         int32_t& start, bool norm = false, bool wide = false) {
     uint32_t s, r;
     if (!ray_slot(A, chunk, rem, nrec, s, r)) return false;  // padding id
     R.slot = chunk * rays_per_chunk(A) + rem;
@@ -238,6 +251,16 @@ __device__ __forceinline__ bool sec_init(const RenderArgs& A, uint32_t nrec, uin
         return false;
     }
     const uint4 meta = A.rec_meta[r];
+    RecStart st{0, -1};  // (the root)
+    if (wide && A.rec_start != nullptr) {
+#if VR_SEC_START_ENTRY
+        st = A.rec_start[r];
+#else
+        st.node = A.rec_start[r].node;
+        if (VR_SEC_UP_AHEAD) st.up = A.hn4_parent[st.node];
+#endif
+    }
+    start = st.node;
     R.rec = r;
     R.cut = A.tau_cut;  // (a select of the two addresses would make this one flat load)
     if (A.rec_cut != nullptr) R.cut = __builtin_nontemporal_load(A.rec_cut + r);
@@ -249,7 +272,7 @@ __device__ __forceinline__ bool sec_init(const RenderArgs& A, uint32_t nrec, uin
     R.credit = 0.0f;
     R.hitmask = 0;
     R.nsteps = 0;
-    R.from = 0;
+    R.up = VR_SEC_UP_AHEAD ? st.up : st.node;
 #ifdef VR_DIAG_LEVELS
     for (int b = 0; b < 8; ++b) R.lv[b] = 0;
 #endif
@@ -669,15 +692,24 @@ __device__ __forceinline__ void sec_node4v(const RenderArgs& A, SecRay& R, LdsIn
     } else if (sp > 0) {
         --sp;
         node = sp < STACK ? stack[sp * BLOCK] : A.stack_ovf[ovf_slot<BLOCK, STACK>(A, sp)];
-    } else if (R.from > 0) {
-        // the subtree rooted at R.from is done: its parent next, without that child (every node is still
-        // visited at most once: the walk from the record's start subtree up to the root covers the tree).
-        // The parent entry carries the child's slot in bits 28-30 (slot + 1), which the next step skips.
-        const int32_t up = A.hn4_parent[R.from];
-        R.from = up & kNodeIndexMask;
-        node = up;  // (-1: the root's subtree is done)
     } else {
-        node = -1;
+        // the subtree is done: its parent next, without that child (every node is still visited at most once: the
+        // walk from the record's start subtree up to the root covers the tree). The parent entry carries the
+        // child's slot in bits 28-30 (slot + 1), which the next step skips.
+#if VR_SEC_UP_AHEAD
+        // R.up is that entry, loaded when the ray entered the subtree (-1: the root's subtree is done); the
+        // parent's own entry is issued now and read at the next climb, many node steps later
+        node = R.up;
+        if (R.up >= 0) R.up = A.hn4_parent[R.up & kNodeIndexMask];
+#else
+        if (R.up > 0) {
+            const int32_t up = A.hn4_parent[R.up];
+            R.up = up & kNodeIndexMask;
+            node = up;  // (-1: the root's subtree is done)
+        } else {
+            node = -1;
+        }
+#endif
     }
 }
 
@@ -736,27 +768,28 @@ __device__ __forceinline__ void sec_node(const RenderArgs& A, SecRay& R, LdsInt*
 // Gaussians active at the record's step: they contain the record position, so they carry the
 // largest optical depths from it and most rays become opaque right there, without touching the
 // tree); the tree walk that follows skips exactly these members (act_find). The phase lives in
-// `node`: kNodeList (-2) walks the active list [Q.j, Q.end), node >= 0 is the tree walk, -1 the end.
+// `node`: node <= kNodeList (-2) walks the active list [Q.j, Q.end) and carries the tree walk's start node X as
+// kNodeList - X (no register of its own: SecRay::up holds X's parent entry), node >= 0 is the tree walk, -1 the end.
 // (Until round 3 the phase walked a per-record neighbour list {j : q_j(pos) <= 9.5} built by a BVH
 // point query per record; the active list is a subset the march already holds: no list stage
 // (-6.1 ms at C4) and a 2.4 % faster secondary stage)
 constexpr int kNodeList = -2;
 
 
-// Start ray R's list phase (or go straight to the tree).
-__device__ __forceinline__ void list_begin(SecRay& R, LeafQueue& Q, int& node) {
+// Start ray R's list phase (or go straight to the tree, at node `start`).
+__device__ __forceinline__ void list_begin(SecRay& R, LeafQueue& Q, int& node, int32_t start) {
     Q.n = 0;
     Q.q1 = 0;  // ring head (ring queues): valid whenever the tree walk starts here
     Q.j = R.act_off;
     Q.end = R.act_off + R.act_n;
-    node = R.act_n > 0u ? kNodeList : R.from;
+    node = R.act_n > 0u ? kNodeList - start : start;
 }
 
 // After a list slot was consumed: move to the tree (its start subtree) once the list is done.
-__device__ __forceinline__ void list_advance(LeafQueue& Q, int& node, int start) {
-    if (node != kNodeList || Q.j < Q.end) return;
+__device__ __forceinline__ void list_advance(LeafQueue& Q, int& node) {
+    if (node > kNodeList || Q.j < Q.end) return;
     Q.j = Q.end = 0;
-    node = start;
+    node = kNodeList - node;
 }
 
 constexpr int kRefillMin = VR_WW_REFILL, kNodeSteps = VR_WW_NODE_STEPS, kPrimSteps = VR_WW_PRIM_STEPS;
@@ -871,7 +904,8 @@ __global__ __launch_bounds__(BLOCK, WAVES) void secondary_ww_kernel(RenderArgs A
             if (!live && pool + rank < pool_end) {
                 t = pool + rank;
                 if constexpr (S) c.v[kCtrSecRays]++;
-                live = sec_init(A, nrec, chunk, t, R, H);  // false: padding id, or complete already (Tr written)
+                int32_t start;
+                live = sec_init(A, nrec, chunk, t, R, start, H, W);  // false: padding id, or complete already (Tr written)
 #ifdef VR_DIAG_DRAIN
                 dr_ray0 = wall_clock64();
                 dr_late = counter_done;
@@ -880,11 +914,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void secondary_ww_kernel(RenderArgs A
                 node = -1;
                 Q.n = 0;
                 Q.j = Q.end = 0;
-                if (live) {
-                    if constexpr (W)  // the tree walk starts in the record's start subtree
-                        if (A.rec_start != nullptr) R.from = A.rec_start[R.rec];
-                    list_begin(R, Q, node);
-                }
+                if (live) list_begin(R, Q, node, start);
             }
             rf_lap(2, true);
             const uint32_t handed = (uint32_t)__popcll(idle);
@@ -913,10 +943,10 @@ __global__ __launch_bounds__(BLOCK, WAVES) void secondary_ww_kernel(RenderArgs A
             LdsInt* ext = stack + STACK * BLOCK;
             // next primitive of the lane: a list member (ls = its slot) or a queued leaf's (ls = -1)
             auto fetch = [&](uint32_t& j, int& ls) {
-                if (node == kNodeList) {
+                if (node <= kNodeList) {
                     ls = (int)(Q.j - R.act_off);
                     j = (uint32_t)A.rec_act[Q.j++];
-                    list_advance(Q, node, R.from);
+                    list_advance(Q, node);
                 } else {
                     ls = -1;
                     j = Q.next<QCAP, BLOCK>(ext);
@@ -1151,7 +1181,8 @@ __global__ __launch_bounds__(256) void record_start_kernel(RenderArgs A) {
         if (A.prim_node4 != nullptr) {
             const uint4 meta = A.rec_meta[r];
             if ((meta.w & ~kRecBoundary) > 0u) {
-                A.rec_start[r] = A.prim_node4[A.rec_act[meta.z]];
+                const int32_t x = A.prim_node4[A.rec_act[meta.z]];
+                A.rec_start[r] = RecStart{x, A.hn4_parent[x]};
                 continue;
             }
         }
@@ -1184,7 +1215,7 @@ __global__ __launch_bounds__(256) void record_start_kernel(RenderArgs A) {
             if (next < 0) break;
             node = next;
         }
-        A.rec_start[r] = node;
+        A.rec_start[r] = RecStart{node, A.hn4_parent[node]};  // (start entries exist with a parent table only: gauss_pipeline)
     }
 }
 

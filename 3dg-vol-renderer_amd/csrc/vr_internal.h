@@ -72,6 +72,14 @@ static_assert(sizeof(HNode4) == 64, "4-wide half node must be 64 B");
 #define VR_SEC_SOA 1  // the secondary rays' node step reads a per-axis copy of their tree (sign-selected slabs; A/B)
 #endif
 
+// Where a record's secondary rays start (record_start_kernel): one 8-B gather at the ray's start instead of two
+// dependent loads (the start node, then its parent entry).
+struct alignas(8) RecStart {
+    int32_t node;  // the HNode4 subtree the record's secondary rays walk first
+    int32_t up;    // hn4_parent[node]: the first climb's node (the skip slot in bits 28-30), -1 at the root
+};
+static_assert(sizeof(RecStart) == 8, "record start entries are one 8-B load");
+
 #ifndef VR_LEAF_MAX
 #define VR_LEAF_MAX 2  // A/B (round 3, every line): 2 beats 3 by 0.8-2.8 % (C4 +1.7 %), 1 and 4 lose
 #endif
@@ -215,7 +223,7 @@ struct RenderArgs {
     uint32_t chunk_rec;             // records per secondary-ray chunk (power of 2; 64 without env_order)
     uint32_t chunk_shift;           // log2(chunk_rec)
     float* rec_cut;                 // per record: optical-depth cut-off of its secondary rays (nullptr: tau_cut)
-    int32_t* rec_start;             // per record: the HNode4 subtree its secondary rays walk first (nullptr: the root)
+    RecStart* rec_start;            // per record: where its secondary rays start (nullptr: at the root)
     // ---- free-flight integrators (vr_freeflight.hip, vr_ff_bounce.h): one (tile chunk, sample batch) step ----
     int32_t ff_multi;        // 0 FreeFlightGaussians, 1 MultiScatterGaussians
     int32_t ff_samples;      // samples per pixel (integrator num_samples)
