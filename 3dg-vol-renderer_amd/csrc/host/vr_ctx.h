@@ -22,6 +22,7 @@ enum Report {
     kRepNeeNeed,       // counter 3: free-flight, the most shadow rays one launch tried to queue
     kRepSlow,          // exact slow-path queue length
     kRepFix,           // band fix-up queue length
+    kRepFiltered,      // rec_alloc[3]: environment rays cut on their record's active list before the walk
     kReportWords
 };
 
@@ -29,11 +30,6 @@ enum Report {
 // capacity a path can exceed is kFFHitCap Gaussians overlapping one point; such a path re-runs in
 // ff_fallback_kernel with kFFBigCap-entry rows (only beyond that: error path, NaN).
 constexpr int32_t kFFHitCap = 128, kFFActCap = kFFHitCap;
-
-// 32-record chunks of the environment-ray order (A/B at C4: 8/16/32/64/128 -> 156.1/150.4/149.1/152.9/161.9 ms)
-#ifndef VR_CHUNK_SHIFT
-#define VR_CHUNK_SHIFT 5
-#endif
 
 // The uploaded scene on the device. A fresh value frees all of it (free_scene).
 struct SceneDev {
@@ -99,6 +95,13 @@ struct vr_ctx {
     int64_t last_pixels = 0;
     uint32_t last_first_tile = 0, last_tile_stride = 1, last_tiles_x = 1, last_w = 0, last_h = 0;  // tile map of the last frame
     uint32_t last_secondary_per_record = 0;
+    // The environment rays' list filter pays from about a third of the rays filtered (kFilterMinShare, vr_frame.cpp). A
+    // frame that ran it and filtered less switches it off for this context's later frames (a hint, as rec_hint: frames
+    // are identical either way); every kFilterProbe-th such frame runs it again, an upload or VR_OPT_SEC_FILTER resets it.
+    bool filter_ran = false;      // the last ray-march frame ran the filter (with last_env_samples per record)
+    bool filter_low = false;      // ... and the last one that did filtered less than the break-even share
+    uint32_t filter_skipped = 0;  // frames rendered without it since
+    uint32_t last_env_samples = 0;
     // wavefront pipeline buffers (grown on demand, never shrunk)
     vr::DevBuf<uint32_t> px_first, rec_next, rec_alloc, slowq, fixq;
     vr::DevBuf<float> px_T, tr, rec_cut;
@@ -109,6 +112,7 @@ struct vr_ctx {
     vr::DevBuf<unsigned long long> rec_bloom, pcg_jump, ray_next;
     vr::DevBuf<uint16_t> env_order;
     vr::DevBuf<uint64_t> env_base;
+    vr::DevBuf<uint32_t> env_count;
     vr::DevBuf<std::byte> deep;  // march_deep_kernel: pixel queue + global active lists (vr_gauss_march.hip)
     vr::DevBuf<uint32_t> bin_cnt, bin_off, bin_ent;  // tile bins of the binned march (VR_OPT_MARCH_BINNED)
     vr::DevBuf<std::byte> ff_scratch;                // free-flight integrators (vr_freeflight.hip, vr_ff_bounce.h)
@@ -160,6 +164,7 @@ struct vr_ctx {
     int64_t opt_start_subtree = 1;     // VR_OPT_START_SUBTREE
     int64_t opt_sec_tight = 1;         // VR_OPT_SEC_TIGHT (next upload)
     int64_t opt_march_wide_min = 2048;  // VR_OPT_MARCH_WIDE_MIN
+    int64_t opt_sec_filter = 1;        // VR_OPT_SEC_FILTER
     vr_group* group = nullptr;         // vr_init_multi: the devices this context drives (host/vr_multi.cpp)
 };
 

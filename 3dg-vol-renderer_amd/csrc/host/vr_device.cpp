@@ -181,6 +181,7 @@ const Option kOptions[] = {
     VR_OPTION(VR_OPT_FF_KERNEL, 0, 2, "in [0, 2]", &vr_ctx::opt_ff_kernel),
     VR_OPTION(VR_OPT_SEC_TIGHT, 0, 1, "0 or 1", &vr_ctx::opt_sec_tight),
     VR_OPTION(VR_OPT_MARCH_WIDE_MIN, 0, 0xffffffffll, "in [0, 2^32)", &vr_ctx::opt_march_wide_min),
+    VR_OPTION(VR_OPT_SEC_FILTER, 0, 1, "0 or 1", &vr_ctx::opt_sec_filter),
     VR_OPTION(VR_OPT_RECORD_CAPACITY, 0, 0x3fffffff, "0 or in [4096, 2^30)", nullptr),
 };
 #undef VR_OPTION
@@ -204,6 +205,10 @@ vr_status vr_set_option(vr_ctx* c, int32_t option, int64_t value) {
     if (o->value) c->*o->value = value;
     else c->rec_hint = c->ovf_hint = (uint64_t)value;
     if (option == VR_OPT_FF_NEE_QUEUE) c->nee_inline = false;
+    if (option == VR_OPT_SEC_FILTER) {  // (setting it also forgets what earlier frames said about the filter's share)
+        c->filter_low = false;
+        c->filter_skipped = 0;
+    }
     return VR_OK;
 }
 

@@ -190,6 +190,15 @@ vr_status fill_args(vr_ctx* c, const vr_camera* cam, const vr_render_params* p, 
 }
 
 
+// The environment rays' list filter (env_order_kernel, VR_OPT_SEC_FILTER) costs a pass over every environment ray's
+// list and saves the persistent kernel the rays it filters. Measured on an MI355X against the parent commit
+// (profiles/r08_c4_sec_filter_ab.json, kernel times of rocprofv3 --kernel-trace): per environment ray the pass costs
+// 9 ps at C4, 18 ps at C2 (longer lists) and 6 ps at C3; per filtered ray the persistent kernel saves 32, 100 and
+// 27 ps. The break-even share of filtered rays is their ratio: 0.29, 0.18, 0.23. C4 (share 0.53) and C3 (0.49) gain
+// 4.5 and 0.6 ms a frame, C2 (0.065) lost 5.8 ms. Below a third, above the largest break-even, the filter is left out.
+constexpr double kFilterMinShare = 1.0 / 3.0;
+constexpr uint32_t kFilterProbe = 64;  // a context that leaves it out runs it again every so many frames (C2: + 0.1 ms a frame)
+
 // RayMarchingGaussians: march (records) -> sizing / cut-offs -> secondary rays -> accumulate.
 vr_status gauss_pipeline(vr_ctx* c, RenderArgs& A, hipStream_t s, bool stats, const GridSrc* grid) {
     const uint32_t npix = A.num_tiles * 256u;
@@ -351,7 +360,18 @@ vr_status gauss_pipeline(vr_ctx* c, RenderArgs& A, hipStream_t s, bool stats, co
             const uint64_t nch = (cap + cr - 1) / cr;
             VR_TRY(c->env_order.grow(nch * cr * (uint64_t)A.env_samples, "hipMalloc(environment-ray order)", A.env_order));
             VR_TRY(c->env_base.grow(nch * cr, "hipMalloc(environment generator states)", A.env_base));
+            VR_TRY(c->env_count.grow(nch, "hipMalloc(environment-ray counts)", A.env_count));
+            // the list filter runs the whitened list phase: RayMarchingGaussians on a scene with whitened records;
+            // not on a context whose last filtered frame was below the break-even share, but for a probe now and then
+            bool run = c->opt_sec_filter && A.wrec != nullptr && !A.pure;
+            if (run && c->filter_low) {
+                run = ++c->filter_skipped >= kFilterProbe;
+                if (run) c->filter_skipped = 0;
+            }
+            A.sec_filter = run ? 1 : 0;
         }
+        c->filter_ran = A.sec_filter != 0;
+        c->last_env_samples = (uint32_t)A.env_samples;
     }
     HIP_TRY(gauss_secondary(A, s, stats), "secondary rays");
     HIP_TRY(hipEventRecord(c->ev_stage[2], s), "hipEventRecord");
@@ -456,6 +476,10 @@ vr_status collect(vr_ctx* c) {
         // >= 5 % of the pixels re-marched: the scene's active sets outgrow 16 slots; later frames march with
         // kActBig (same operations, so the frames are identical; kept until the next upload)
         if ((uint64_t)c->h_report[kRepFallback] * 20ull >= c->report_pixels && c->report_pixels > 0) c->march_big = true;
+        if (c->filter_ran && c->h_report[kRepExceeded] == 0) {  // the list filter's share of the frame's environment rays
+            const uint64_t env = nrec * c->last_env_samples;
+            c->filter_low = (double)c->h_report[kRepFiltered] < kFilterMinShare * (double)env;
+        }
     }
     if (c->report_ff && c->last_nee_bound > 0) {
         // a launch that found the queue full counted its paths' first refused claim only (they then
@@ -511,6 +535,7 @@ vr_status vr::launch(vr_ctx* c, RenderArgs& A, const vr_render_params* p, hipStr
         HIP_TRY(report(kRepDeep, A.deepq, 1), "hipMemcpyAsync(report)");
         HIP_TRY(report(kRepSlow, A.slowq, 1), "hipMemcpyAsync(report)");
         HIP_TRY(report(kRepFix, A.fixq, 1), "hipMemcpyAsync(report)");
+        HIP_TRY(report(kRepFiltered, A.rec_alloc + 3, 1), "hipMemcpyAsync(report)");
     }
     HIP_TRY(report(kRepFFFallback, c->counters.get() + 2, 2), "hipMemcpyAsync(report)");  // and kRepNeeNeed
     HIP_TRY(hipEventRecord(c->ev_report, s), "hipEventRecord");
@@ -808,6 +833,7 @@ vr_status vr_get_stats(vr_ctx* c, vr_render_stats* o) {
     o->deep_pixels = c->report_gauss ? (int64_t)std::min(c->h_report[kRepDeep], kDeepQueue) : 0;
     o->slow_rays = c->report_gauss ? (int64_t)c->h_report[kRepSlow] : 0;
     o->band_rays = c->report_gauss ? (int64_t)c->h_report[kRepFix] : 0;
+    o->filtered_rays = c->report_gauss ? (int64_t)c->h_report[kRepFiltered] : 0;
     return VR_OK;
 }
 

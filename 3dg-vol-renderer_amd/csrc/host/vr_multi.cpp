@@ -310,6 +310,7 @@ vr_status group_stats(vr_group* g, vr_render_stats* o) {
         o->deep_pixels += s.deep_pixels;
         o->slow_rays += s.slow_rays;
         o->band_rays += s.band_rays;
+        o->filtered_rays += s.filtered_rays;
     }
     return VR_OK;
 }

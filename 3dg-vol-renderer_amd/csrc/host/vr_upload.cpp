@@ -360,6 +360,8 @@ vr_status vr_upload_scene(vr_ctx* c, const vr_scene* sc) {
     c->has_scene = false;
     c->q_count_valid = false;
     c->march_big = false;
+    c->filter_low = false;
+    c->filter_skipped = 0;
     c->nee_inline = false;  // (nee_hint is kept: the inverse loop re-uploads every iteration and renders alike)
     c->type = s.type;
     c->lights.clear();

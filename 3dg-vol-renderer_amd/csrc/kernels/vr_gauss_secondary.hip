@@ -142,23 +142,70 @@ __device__ __forceinline__ int act_find(const RenderArgs& A, const SecRay& R, in
 // octahedral map of the evaluated direction, round 3: 3.3 ms slower at C4).
 constexpr int kEnvBits = 4, kEnvSide = 1 << kEnvBits, kEnvCells = kEnvSide * kEnvSide;
 
+// The environment rays' list filter (VR_OPT_SEC_FILTER; DESIGN.md §3, pipeline step 2): the list phase of one
+// environment ray, as secondary_ww_kernel's wtest runs it for a list member (ls >= 0) of a ray that is no light ray —
+// the member's chord [max(t0, 0), t1] goes to `credit`, a stretch [0, t0] ahead of the origin to `tau`. The band and
+// boundary tests of wtest only raise needs_stop, which sec_finish reads after the cut-off, so a ray that reaches its
+// cut-off here stores Tr = 0 there whatever they say. A second definition rather than a shared one: the persistent
+// kernel sits at its register limit (72 VGPRs) and its test is left as it compiles; the operations
+// are the same ones in the same order (explicit fmaf, no contraction), so the decision is the kernel's bit for bit
+// (tests/test_gpu_sec_filter.py: frames and per-ray rows with the filter on and off).
+__device__ __forceinline__ bool list_member_depth(const WRec& g, const Ray& ray, float& tau, float& credit) {
+    const WQuad q = wquad(g, ray);
+    float t0, t1, sd;
+    if (!wintersect(q, t0, t1, sd)) return false;
+    const bool inside = q.hr > -sd;  // t0 < 0: the origin lies in the 3-sigma sphere
+    constexpr float kRs2 = 0.70710678118654752f;
+    const float F1 = erf_chord(sd * kRs2), F0 = erf_chord(q.hr * kRs2);  // a member is summed from 0
+    const float pf = (g.dn * q.r) * __expf(-0.5f * q.e2);
+    const float od = pf * fmaxf(F1 - F0, 0.0f);
+    const float chord = inside ? od : pf * (F1 + F1);
+    credit += chord;
+    tau += od - chord;
+    return true;
+}
+#ifndef VR_SEC_FILTER_MAX
+#define VR_SEC_FILTER_MAX 16  // longest active list the filter tests; the rays of longer ones are handed out
+#endif
+constexpr uint32_t kFilterMax = VR_SEC_FILTER_MAX;
+
 // One sorting group per record chunk: counting sort of the chunk's environment rays by direction key
 // (order inside a key is arbitrary: every ray's result is independent of when it is traced). A group
 // is one wave: BLOCK/64 chunks in flight per workgroup, wave-local LDS and no workgroup barriers; the
 // chunk's chain of dependent loads is the cost, not its arithmetic (C4: 1.56 ms; a workgroup per chunk 1.91).
-template <int BLOCK>
+// One more bucket follows the direction cells: the rays the persistent kernel need not trace — those of padding
+// records, of records without a ray to trace (weight <= 0, sec_init) and, with A.sec_filter, those that reach
+// their optical-depth cut-off on their record's active list (list_member_depth). The order still lists every
+// ray of the chunk, so a ray's Tr slot is its position in it as before; the rays of that bucket get their
+// Tr = 0 here, and A.env_count tells the persistent kernel how many rays come before them.
+// S: the instrumented build (vr_count_work) counts the filter's list tests and the rays it keeps back where the
+// persistent kernel counts its own.
+template <int BLOCK, bool S>
 __global__ __launch_bounds__(BLOCK) void env_order_kernel(RenderArgs A) {
     constexpr int G = 64, kGroups = BLOCK / G;
     constexpr uint32_t kKeyCap = 8192 / kGroups;  // keys kept in LDS per group; larger chunks recompute them
-    using KeyT = typename std::conditional<(kEnvCells <= 256), uint8_t, uint16_t>::type;
+    constexpr uint32_t kRecMax = 1u << VR_CHUNK_SHIFT;  // records per chunk (A.chunk_rec)
+    constexpr uint32_t kTail = kEnvCells;         // the bucket behind every direction cell
+    static_assert(kEnvCells <= 256, "direction keys are kept in 8 bits");
     constexpr int kPer = kEnvCells / 64;  // counts per lane of the scan
-    __shared__ uint32_t hist_s[kGroups][kEnvCells];
-    __shared__ KeyT keys_s[kGroups][kKeyCap];
-    __shared__ uint64_t base_s[kGroups][256];  // the chunk's generator states (record-in-chunk fits 8 bits)
+    __shared__ uint32_t hist_s[kGroups][kEnvCells + 1];
+    __shared__ uint8_t keys_s[kGroups][kKeyCap];
+    __shared__ uint64_t tail_s[kGroups][kKeyCap / 64];  // with the keys: the rays of the last bucket, a bit each
+    __shared__ uint64_t base_s[kGroups][kRecMax];  // the chunk's generator states
+    // the chunk's records: position and weight, active list (offset, count; count 0: not tested), cut-off
+    __shared__ float4 pos_s[kGroups][kRecMax];
+    __shared__ uint2 act_s[kGroups][kRecMax];
+    __shared__ float cut_s[kGroups][kRecMax];
+    __shared__ int32_t ids_s[kGroups][kRecMax * kFilterMax];  // the tested lists' members (shared by a record's rays)
     const uint32_t grp = threadIdx.x / G, tid = threadIdx.x % G;
     uint32_t* hist = hist_s[grp];
-    KeyT* keys = keys_s[grp];
+    uint8_t* keys = keys_s[grp];
+    uint64_t* tailm = tail_s[grp];
     uint64_t* base = base_s[grp];
+    float4* rpos = pos_s[grp];
+    uint2* ract = act_s[grp];
+    float* rcut = cut_s[grp];
+    int32_t* ids = ids_s[grp];
     auto group_sync = [] {
         if constexpr (G == 64) {  // the wave's own LDS traffic: wait for it, keep the compiler from moving it
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -171,22 +218,74 @@ __global__ __launch_bounds__(BLOCK) void env_order_kernel(RenderArgs A) {
     const uint32_t cr = A.chunk_rec, ne = (uint32_t)A.env_samples;
     const uint32_t n = cr * ne, nch = (nrec + cr - 1) / cr;
     const bool cached = n <= kKeyCap;
+    const bool filter = A.sec_filter != 0 && A.wrec != nullptr;
+    Ctr c{};
+    uint32_t nfiltered = 0;  // this lane's rays cut on their list
+    if (cr > kRecMax) return;  // (never: gauss_pipeline sets chunk_rec = 1 << VR_CHUNK_SHIFT with env_order)
     for (uint32_t chunk = blockIdx.x * kGroups + grp; chunk < nch; chunk += gridDim.x * kGroups) {  // group-uniform loop
         const uint32_t r0 = chunk * cr;
-        for (uint32_t i = tid; i < kEnvCells; i += G) hist[i] = 0;
-        for (uint32_t rl = tid; rl < cr; rl += G)  // seeded once per record, not per sample
+        for (uint32_t i = tid; i <= kEnvCells; i += G) hist[i] = 0;
+        for (uint32_t rl = tid; rl < cr; rl += G) {  // seeded once per record, not per sample
+            float4 pos = make_float4(0.0f, 0.0f, 0.0f, -1.0f);  // a padding record: no ray to trace
+            uint2 act = make_uint2(0u, 0u);
+            float cut = A.tau_cut;
             if (r0 + rl < nrec) {
-                base[rl] = env_base_state(A.rec_meta[r0 + rl]);
+                const uint4 meta = A.rec_meta[r0 + rl];
+                base[rl] = env_base_state(meta);
                 A.env_base[r0 + rl] = base[rl];  // for sec_init: one 8-B load instead of the seeding per ray
+                pos = A.rec_pos[r0 + rl];
+                const uint32_t an = meta.w & ~kRecBoundary;
+                if (filter && an <= kFilterMax) act = make_uint2(meta.z, an);
+                if (A.rec_cut != nullptr) cut = A.rec_cut[r0 + rl];
+            }
+            rpos[rl] = pos;
+            ract[rl] = act;
+            rcut[rl] = cut;
+        }
+        group_sync();
+        if (filter)  // the members' ids, gathered side by side: no link of a ray's load chain
+            for (uint32_t i = tid; i < cr * kFilterMax; i += G) {
+                const uint2 act = ract[i / kFilterMax];
+                if (i % kFilterMax < act.y) ids[i] = A.rec_act[act.x + i % kFilterMax];
             }
         group_sync();
-        auto key = [&](uint32_t i) -> uint32_t {
-            const uint32_t rl = i / ne, r = r0 + rl;
-            if (r >= nrec) return kEnvCells - 1;  // padding records
+        // the ray's bucket; count: the instrumented build's counts (once per ray: an uncached chunk asks twice)
+        auto key = [&](uint32_t i, bool count) -> uint32_t {
+            const uint32_t rl = i / ne;
+            const float4 pos = rpos[rl];
+            if (!(pos.w > 0.0f)) {  // padding, weightless and orphaned records (sec_init hands none of their rays on)
+                if constexpr (S) c.v[kCtrSecRays] += count ? 1u : 0u;
+                return kTail;
+            }
             // the cell of the sample's (xi1, xi2) = (azimuth, cos polar) grid: equal-area direction
             // cells without evaluating the direction
             float xi1, xi2;
             env_xi_at(A, base[rl], i - rl * ne, xi1, xi2);
+            const uint2 act = ract[rl];
+            if (act.y > 0u) {  // the list phase, members in list order, up to the first that reaches the cut-off
+                float wx, wy, wz;
+                env_dir(xi1, xi2, wx, wy, wz);
+                const Ray ray{pos.x, pos.y, pos.z, wx, wy, wz};
+                const float cut = rcut[rl];
+                float tau = 0.0f, credit = 0.0f;
+                const int32_t* mem = ids + rl * kFilterMax;
+                for (uint32_t m = 0; m < act.y; ++m) {
+                    // (the next member's record loaded ahead of this test, A/B at C4: 86 VGPRs, 5 waves, 0.5 ms slower)
+                    const bool hit = list_member_depth(load_wrec(A.wrec, mem[m]), ray, tau, credit);
+                    if constexpr (S) {
+                        c.v[kCtrMu] += count ? 1u : 0u;
+                        c.v[kCtrOD] += (count && hit) ? 1u : 0u;
+                    }
+                    if (tau + credit >= cut) {  // cut_reached
+                        if constexpr (S) {
+                            c.v[kCtrSecRays] += count ? 1u : 0u;
+                            c.v[kCtrSteps] += count ? 1u : 0u;  // a cut ray without node steps
+                        }
+                        nfiltered += count ? 1u : 0u;
+                        return kTail;
+                    }
+                }
+            }
             const uint32_t cu = min((uint32_t)(xi1 * kEnvSide), (uint32_t)kEnvSide - 1u);
             const uint32_t cv = min((uint32_t)(xi2 * kEnvSide), (uint32_t)kEnvSide - 1u);
             uint32_t k = 0;
@@ -195,8 +294,12 @@ __global__ __launch_bounds__(BLOCK) void env_order_kernel(RenderArgs A) {
             return k;
         };
         for (uint32_t i = tid; i < n; i += G) {
-            const uint32_t k = key(i);
-            if (cached) keys[i] = (KeyT)k;
+            const uint32_t k = key(i, true);
+            if (cached) {
+                keys[i] = (uint8_t)k;  // (the last bucket: the bit below)
+                const uint64_t tails = __ballot(k == kTail);  // rays i - tid .. of this round (lane 0 is in every round)
+                if (tid == 0) tailm[i / 64u] = tails;
+            }
             atomicAdd(&hist[k], 1u);
         }
         group_sync();
@@ -220,16 +323,27 @@ __global__ __launch_bounds__(BLOCK) void env_order_kernel(RenderArgs A) {
                 hist[kPer * l + j] = ex;
                 ex += v[j];
             }
+            if (l == 63u) hist[kTail] = incl;  // the last bucket starts behind every direction cell
         }
+        group_sync();
+        const uint32_t kept = hist[kTail];  // rays the persistent kernel hands out (read before the scatter moves it)
         group_sync();
         uint16_t* out = A.env_order + (size_t)chunk * n;
         for (uint32_t i = tid; i < n; i += G) {
             const uint32_t rl = i / ne;
-            out[atomicAdd(&hist[cached ? (uint32_t)keys[i] : key(i)], 1u)] = (uint16_t)((rl << 8) | (i - rl * ne));
+            const uint32_t k = !cached ? key(i, false) : ((tailm[i / 64u] >> tid) & 1ull) ? kTail : (uint32_t)keys[i];
+            out[atomicAdd(&hist[k], 1u)] = (uint16_t)((rl << 8) | (i - rl * ne));
         }
+        // the last bucket's results: a contiguous run of the chunk's Tr slots (rays_per_chunk: lights first)
+        float* tr = A.tr + (size_t)chunk * rays_per_chunk(A) + cr * (uint32_t)A.num_lights;
+        for (uint32_t i = kept + tid; i < n; i += G) tr[i] = 0.0f;
+        if (tid == 0) A.env_count[chunk] = kept;
         group_sync();  // hist / keys / base are reused by the group's next chunk (staging the order in LDS
                        // for coalesced stores measured slower: 1.64 vs 1.56 ms at C4)
     }
+    for (int o = 32; o > 0; o >>= 1) nfiltered += __shfl_xor(nfiltered, o, 64);
+    if (tid == 0 && nfiltered != 0u) atomicAdd(&A.rec_alloc[3], nfiltered);
+    if constexpr (S) flush_counters(A.work + kNumCtr, c);
 }
 
 // Start ray `rem` of record chunk `chunk`. Returns false if the ray is already complete (Tr
@@ -890,8 +1004,12 @@ __global__ __launch_bounds__(BLOCK, WAVES) void secondary_ww_kernel(RenderArgs A
                 if (cnext < nunits) {
                     chunk = cnext >> split;
                     const uint32_t part = cnext & ((1u << split) - 1u);
-                    pool = (part * per) >> split;
-                    pool_end = ((part + 1u) * per) >> split;
+                    // with an environment-ray order, the chunk's light rays and the head of its order: the rays behind
+                    // it are complete (env_order_kernel); a chunk with neither is an empty unit, the next claim follows
+                    uint32_t cper = per;
+                    if (A.env_order != nullptr) cper = A.chunk_rec * (uint32_t)A.num_lights + A.env_count[chunk];
+                    pool = (part * cper) >> split;
+                    pool_end = ((part + 1u) * cper) >> split;
                 }
                 counter_done = cnext + 1u >= nunits;
 #ifdef VR_DIAG_DRAIN
@@ -1287,8 +1405,9 @@ hipError_t gauss_secondary(const RenderArgs& A, hipStream_t stream, bool stats) 
         if (e != hipSuccess) return e;
     }
     if (A.env_order != nullptr) {
-        hipLaunchKernelGGL(dev::env_order_kernel<256>, dim3(record_grid(A, A.chunk_rec * 4, 4096)), dim3(256), 0,
-                           stream, A);
+        // (stats: the instrumented build counts the list filter's work with the persistent kernel's)
+        if (stats) hipLaunchKernelGGL((dev::env_order_kernel<256, true>), dim3(record_grid(A, A.chunk_rec * 4, 4096)), dim3(256), 0, stream, A);
+        else hipLaunchKernelGGL((dev::env_order_kernel<256, false>), dim3(record_grid(A, A.chunk_rec * 4, 4096)), dim3(256), 0, stream, A);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

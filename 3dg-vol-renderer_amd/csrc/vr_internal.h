@@ -110,6 +110,10 @@ struct LightRecord {
 };
 
 constexpr int kMaxLights = 16;
+// 32-record chunks of the environment-ray order (A/B at C4: 8/16/32/64/128 -> 156.1/150.4/149.1/152.9/161.9 ms)
+#ifndef VR_CHUNK_SHIFT
+#define VR_CHUNK_SHIFT 5
+#endif
 constexpr int kEnvOrderMax = 240;  // environment rays are direction-ordered up to this many samples (LDS bound)
 constexpr uint32_t kNoRecord = 0xffffffffu;
 constexpr int kActInline = 4;  // active-list slots stored with each scatter record
@@ -208,7 +212,8 @@ struct RenderArgs {
                         // record, longer lists in the overflow pool after rec_cap * kActInline
     float* tr;          // per secondary ray: transmittance, slot = chunk * rays-per-chunk + hand-out index
     float4* rec_rad;    // per record: Li + Le (record_radiance_kernel), the radiance the accumulation weighs
-    uint32_t* rec_alloc;  // [0] records allocated, [1] overflow-pool entries allocated, [2] capacity exceeded
+    uint32_t* rec_alloc;  // [0] records allocated, [1] overflow-pool entries allocated, [2] capacity exceeded,
+                          // [3] environment rays cut on their record's active list (env_order_kernel)
     uint32_t rec_cap, act_ovf_cap;
     unsigned long long* rec_bloom;  // per record: 64-bit membership mask of its active list
     uint32_t* slowq;                // light rays needing the exact stopping event: [0] count, [1..] ray ids
@@ -262,6 +267,10 @@ struct RenderArgs {
     uint32_t* rec_bits;      // RECORD_PIXEL_GAUSSIANS bitset [word][pixel] (nullptr: not recording)
     uint32_t rec_npix;       // W * H
     const unsigned long long* pcg_jump;  // [2k] = A^k, [2k+1] = inc (A^(k-1) + ... + 1): PCG32 state after k draws
+    // The environment rays' list filter (env_order_kernel): a chunk's order lists the rays the persistent kernel
+    // still has to trace first; the others (cut on their record's active list, or without a ray to trace) follow.
+    uint32_t* env_count;     // with env_order: per record chunk, the environment rays handed out (the head of its order)
+    int32_t sec_filter;      // 1: environment rays are cut on their record's active list before the walk (VR_OPT_SEC_FILTER)
 };
 
 // A ray grid's own arguments (vr_render_rays). They travel beside RenderArgs, to the grid instantiations of the

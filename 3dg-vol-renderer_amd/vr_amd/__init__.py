@@ -371,7 +371,8 @@ class Device:
                 "error_pixels": s.error_pixels, "stage_ms": dict(zip(self.STAGES, list(s.stage_ms))),
                 "scatter_records": s.scatter_records, "secondary_rays": s.secondary_rays,
                 "record_overflow": bool(s.record_overflow), "deep_pixels": s.deep_pixels,
-                "slow_rays": s.slow_rays, "band_rays": s.band_rays}
+                "slow_rays": s.slow_rays, "band_rays": s.band_rays,
+                "filtered_rays": s.filtered_rays}
 
     def fallback_pixels(self):
         """(n, 2) int array of the (x, y) pixels of the last ray-march frame that were re-run on the
@@ -428,7 +429,8 @@ class Device:
                "device_bvh": L.VR_OPT_DEVICE_BVH, "ff_nee_queue": L.VR_OPT_FF_NEE_QUEUE,
                "march_binned": L.VR_OPT_MARCH_BINNED, "ff_solver": L.VR_OPT_FF_SOLVER,
                "start_subtree": L.VR_OPT_START_SUBTREE, "ff_kernel": L.VR_OPT_FF_KERNEL,
-               "sec_tight": L.VR_OPT_SEC_TIGHT, "march_wide_min": L.VR_OPT_MARCH_WIDE_MIN}
+               "sec_tight": L.VR_OPT_SEC_TIGHT, "march_wide_min": L.VR_OPT_MARCH_WIDE_MIN,
+               "sec_filter": L.VR_OPT_SEC_FILTER}
 
     def set_option(self, name, value):
         """vr_set_option (include/vr_hip.h): explicit per-context tuning (half_nodes applies at the

@@ -27,6 +27,7 @@ VR_OPT_START_SUBTREE = 9
 VR_OPT_SEC_TIGHT = 11
 VR_OPT_MARCH_WIDE_MIN = 12
 VR_OPT_FF_KERNEL = 13
+VR_OPT_SEC_FILTER = 14
 
 f3 = ctypes.c_float * 3
 
@@ -66,7 +67,7 @@ class vr_render_stats(ctypes.Structure):
                 ("error_pixels", ctypes.c_int64), ("stage_ms", ctypes.c_double * 4),
                 ("scatter_records", ctypes.c_int64), ("secondary_rays", ctypes.c_int64),
                 ("record_overflow", ctypes.c_int64), ("deep_pixels", ctypes.c_int64), ("slow_rays", ctypes.c_int64),
-                ("band_rays", ctypes.c_int64)]
+                ("band_rays", ctypes.c_int64), ("filtered_rays", ctypes.c_int64)]
 
 
 class vr_sfd_config(ctypes.Structure):

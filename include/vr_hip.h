@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define VR_ABI_VERSION 9
+#define VR_ABI_VERSION 10
 
 typedef enum vr_status {
     VR_OK = 0,
@@ -138,6 +138,10 @@ typedef struct vr_render_stats {
                                  chords or a member's within the reference f32 quadratic's error band) */
     int64_t band_rays;        /* RayMarchingGaussians: secondary rays with one non-member chord within that band,
                                  whose contribution the reference's M form recomputes (secondary_fix_kernel) */
+    int64_t filtered_rays;    /* RayMarchingGaussians: environment rays whose record's active list alone reaches the
+                                 optical-depth cut-off: their Tr = 0 is written by the pass that orders the
+                                 environment rays and the persistent kernel never traces them (VR_OPT_SEC_FILTER;
+                                 0 with the option off). Part of secondary_rays. (ABI 10) */
 } vr_render_stats;
 
 typedef struct vr_scene vr_scene; /* host-side scene: primitives, lights, env colour */
@@ -397,6 +401,12 @@ typedef enum vr_option {
                                     many pixels (default 2048) goes one pixel per lane with 64 slots in
                                     global memory, a shorter one one pixel per wave (64 LDS slots). Same
                                     operations either way: frames are identical. */
+    VR_OPT_SEC_FILTER = 14,      /* RayMarchingGaussians secondary rays (scenes with whitened records): 1 (default):
+                                    the pass that orders a record chunk's environment rays by direction also runs
+                                    each ray's list phase (the record's active Gaussians, at most 16 of them) and
+                                    keeps the rays that reach their optical-depth cut-off there out of the
+                                    persistent kernel (vr_render_stats.filtered_rays); 0: every ray is handed
+                                    out. The same arithmetic decides either way: frames are identical. */
     VR_OPT_FF_KERNEL = 13        /* free-flight integrators, persistent path kernel: 0 (default) chosen from the
                                     uploaded scene: the phase-scheduled kernel for translucent scenes of many
                                     Gaussians (at least 256, median central-chord optical depth below 16: long
