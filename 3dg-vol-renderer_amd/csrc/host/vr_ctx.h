@@ -132,6 +132,11 @@ struct vr_ctx {
     vr::DevBuf<unsigned long long> q_keys, q_keys2;  // sort keys (in / out),
     vr::DevBuf<std::byte> q_tmp;                // scan + sort scratch
     vr::DevBuf<std::byte> q_ctl;      // words [0..2] ray counters of the three persistent walks, [4..5] the 64-bit event total
+    // free-flight query (kernels/vr_query_flight.hip): its own scratch rows (the layouts of ff_scratch and of
+    // ff_fb's rows), so a frame queued on another stream never shares them; counters + queue of rays over the rows
+    vr::DevBuf<std::byte> q_ff_rows, q_ff_big;
+    vr::DevBuf<uint32_t> q_ff_ctl;
+    vr::DevBuf<float> q_tau;          // host form: the targets on the device
     // ray grids (vr_render_rays, vr_rays.cpp)
     vr::DevBuf<vr_ray> ray_in;        // host form: the grid on the device,
     vr::DevBuf<float> ray_tr;         //   and its transmittance output

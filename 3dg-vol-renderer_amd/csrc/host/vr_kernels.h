@@ -44,6 +44,12 @@ hipError_t query_events_fill(const RenderArgs& A, const vr_ray* rays, uint32_t n
 hipError_t query_pack_rays(const float* o, const float* d, const float* tmax, uint32_t tmax_stride, uint32_t n, vr_ray* rays,
                            hipStream_t s);
 
+// kernels/vr_query_flight.hip (the sweep, the solvers and the albedo are the path kernels': kernels/vr_ff_bounce.h)
+// (ctl: query_flight_ctl_words(n) words; A.ff_*: the scratch rows, sized as the free-flight frames size theirs)
+size_t query_flight_ctl_words(uint32_t n);
+hipError_t query_free_flight(const RenderArgs& A, const vr_ray* rays, const float* tau, uint32_t n, float* t, float* albedo,
+                             uint32_t* n_active, uint32_t* ctl, hipStream_t s);
+
 // kernels/vr_ray_extent.hip: *out = the bits of the largest distance from a ray's origin to the farthest corner of
 // the box, over the valid rays that hit the box (0: none does)
 hipError_t ray_extent(const vr_ray* rays, uint32_t n, const float bmin[3], const float bmax[3], uint32_t* out, hipStream_t s);

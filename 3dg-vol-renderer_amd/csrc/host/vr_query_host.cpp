@@ -1,4 +1,5 @@
-// Mixture queries (vr_query_*, kernels/vr_query.hip): batched transmittance, ray events and sigma.
+// Mixture queries (vr_query_*, kernels/vr_query.hip, kernels/vr_query_flight.hip): batched transmittance, ray events, sigma
+// and free-flight distances.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -191,6 +192,64 @@ vr_status vr_query_events(vr_ctx* c, const vr_ray* rays, size_t n, uint32_t* off
     HIP_TRY(hipStreamSynchronize(c->stream), "query_events_fill_kernel");
     HIP_TRY(hipMemcpy(t, c->q_out.get(), tot * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
     HIP_TRY(hipMemcpy(ev, c->q_out2.get(), tot * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    return VR_OK;
+}
+
+vr_status vr_query_free_flight_device(vr_ctx* c, const vr_ray* d_rays, const float* d_tau_target, size_t n, float* d_t,
+                                      float* d_albedo, uint32_t* d_n_active, void* stream) {
+    c = first_device(c);
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_free_flight", n, A));
+    if (n == 0) return VR_OK;
+    if (!d_rays || !d_tau_target || !d_t) return fail(VR_ERR_INVALID, "vr_query_free_flight: NULL argument");
+    if (!aligned16(d_rays)) return fail(VR_ERR_INVALID, "vr_query_free_flight: the device ray array must be 16-byte aligned");
+    if (c->opt_ff_solver == 4)
+        return fail(VR_ERR_UNSUPPORTED, "vr_query_free_flight: the UNIFORM solver (VR_OPT_FF_SOLVER = 4) draws from a path's seed");
+    // the rows of free_flight_pipeline (vr_frame.cpp), in this query's own buffers
+    const uint32_t threads = free_flight_threads(c->cus);
+    VR_TRY(c->q_ff_rows.grow((size_t)threads * (kFFHitCap + 2 * kFFActCap) * 16, "hipMalloc(free-flight query rows)"));
+    VR_TRY(c->q_ff_big.grow((size_t)kFFBigThreads * 3 * (size_t)kFFBigCap * 16, "hipMalloc(free-flight query rows)"));
+    VR_TRY(c->q_ff_ctl.grow(query_flight_ctl_words((uint32_t)n), "hipMalloc(free-flight query queue)"));
+    float4* base = (float4*)c->q_ff_rows.get();
+    A.ff_threads = threads;
+    A.ff_hit_cap = kFFHitCap;
+    A.ff_act_cap = kFFActCap;
+    const int64_t w0 = c->opt_ff_window0 > 0 ? c->opt_ff_window0 : (int64_t)c->auto_window0;
+    A.ff_hit_cap0 = (int32_t)std::max<int64_t>(1, std::min<int64_t>(kFFHitCap, w0));
+    A.ff_hit = base;
+    A.ff_act0 = base + (size_t)kFFHitCap * threads;
+    A.ff_act1 = base + (size_t)(kFFHitCap + kFFActCap) * threads;
+    A.ff_big = (float4*)c->q_ff_big.get();
+    A.ff_solver = (int32_t)c->opt_ff_solver;
+    HIP_TRY(query_free_flight(A, d_rays, d_tau_target, (uint32_t)n, d_t, d_albedo, d_n_active, c->q_ff_ctl.get(), (hipStream_t)stream),
+            "query_flight_kernel");
+    return VR_OK;
+}
+
+vr_status vr_query_free_flight(vr_ctx* c, const vr_ray* rays, const float* tau_target, size_t n, float* t, float* albedo,
+                               uint32_t* n_active) {
+    c = first_device(c);
+    RenderArgs A;
+    vr_status st = query_begin(c, "vr_query_free_flight", n, A);
+    if (st != VR_OK || n == 0) return st;
+    if (!rays || !tau_target || !t) return fail(VR_ERR_INVALID, "vr_query_free_flight: NULL argument");
+    VR_TRY(c->q_in.grow(n * sizeof(vr_ray), "hipMalloc(query rays)"));
+    VR_TRY(c->q_tau.grow(n, "hipMalloc(query targets)"));
+    VR_TRY(c->q_out.grow(n * 2, "hipMalloc(query results)"));
+    if (n_active) VR_TRY(c->q_out2.grow(n * sizeof(uint32_t), "hipMalloc(query results)"));
+    HIP_TRY(hipMemcpy(c->q_in.get(), rays, n * sizeof(vr_ray), hipMemcpyHostToDevice), "hipMemcpy(query rays)");
+    HIP_TRY(hipMemcpy(c->q_tau.get(), tau_target, n * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(query targets)");
+    VR_TRY(vr_query_free_flight_device(c, (const vr_ray*)c->q_in.get(), c->q_tau.get(), n, c->q_out.get(),
+                                       albedo ? c->q_out.get() + n : nullptr, n_active ? (uint32_t*)c->q_out2.get() : nullptr, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream), "query_flight_kernel");
+    HIP_TRY(hipMemcpy(t, c->q_out.get(), n * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    if (albedo) HIP_TRY(hipMemcpy(albedo, c->q_out.get() + n, n * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    if (n_active) HIP_TRY(hipMemcpy(n_active, c->q_out2.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    uint32_t failed = 0;  // rays over kFFBigCap Gaussians at one point (ctl word 2): every output is written, those NaN
+    HIP_TRY(hipMemcpy(&failed, c->q_ff_ctl.get() + 2, sizeof(failed), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    if (failed)
+        return fail(VR_ERR_OVERFLOW, "vr_query_free_flight: " + std::to_string(failed) + " rays cross more than " +
+                                         std::to_string(kFFBigCap) + " Gaussians overlapping one point (their results are NaN)");
     return VR_OK;
 }
 

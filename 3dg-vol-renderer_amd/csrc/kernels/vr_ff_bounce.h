@@ -499,7 +499,12 @@ __device__ __forceinline__ uint64_t ff_path_seed(const RenderArgs& A, uint32_t o
 // MULTI = false with a float sum, :422-498 for MULTI = true with a double sum). Returns t >= 0,
 // -1 (no scatter before the last event) or -2 (a per-thread capacity was exceeded). On return
 // with t >= 0 the active list holds the critical segment's Gaussians (count in m).
-template <bool MULTI, class SC>
+// KEEP (the free-flight query, vr_query_flight.hip; the path kernels run KEEP = false): the active list is carried
+// from window to window instead of being collected again at W0, where it would come back in walk order. A window
+// then collects only the hits that enter at or after W0 (the earlier ones are in the list, or gone), so the list is
+// the reference's at every event (append on entry, swap-remove on exit) however the windows fall, and the f32 sums
+// over it (solvers, albedo) do not depend on VR_OPT_FF_WINDOW0 or on the capacity doublings.
+template <bool MULTI, bool KEEP = false, class SC>
 __device__ float free_flight_distance(const RenderArgs& A, SC& S, const Ray& r, float target, int& m, int* stack,
                                       int stride, uint32_t path, int bounce) {
     using Acc = typename std::conditional<MULTI, double, float>::type;
@@ -509,6 +514,10 @@ __device__ float free_flight_distance(const RenderArgs& A, SC& S, const Ray& r, 
     // Window capacity starts small (most scatters happen within the first few events) and doubles
     // after every window without a scatter, or when the overlap at W0 does not fit, up to ff_hit_cap.
     int cap = A.ff_hit_cap0;
+    // The active list's next exit (see the sweep below); with KEEP they outlive a window, as the list does.
+    float next_exit = INFINITY;
+    int exit_pos = -1;
+    m = 0;
     for (;;) {
         // ---- collect the hits overlapping [W0, inf): the cap smallest entry keys, kept sorted ----
         // The walk is near-first; once the buffer is full, subtrees starting beyond its largest key
@@ -527,7 +536,11 @@ __device__ float free_flight_distance(const RenderArgs& A, SC& S, const Ray& r, 
             float t0, t1;
             if (!intersect(quad(g, r), t0, t1)) return;
             if (!(t0 <= t1)) return;  // NaN distances (degenerate covariance): no event
-            if (W0 > 0.0f && !(t1 > W0)) return;
+            if constexpr (KEEP) {
+                if (fmaxf(t0, 0.0f) < W0) return;  // entered in an earlier window (every entry before its cut did)
+            } else {
+                if (W0 > 0.0f && !(t1 > W0)) return;
+            }
             const float key = fmaxf(t0, W0);
             if (key >= t_cut) return;
             if (n == cap) {
@@ -574,16 +587,18 @@ __device__ float free_flight_distance(const RenderArgs& A, SC& S, const Ray& r, 
             cap = min(2 * cap, A.ff_hit_cap);
             continue;
         }
-        if (n == 0 && t_cut == INFINITY) return -1.0f;
+        if (n == 0 && t_cut == INFINITY && (!KEEP || m == 0)) return -1.0f;  // (KEEP: the list's exits are still to come)
         // ---- sweep the window's events (integrator.h:438-495) ----
         // The active list's next exit (the first entry with the smallest t1, as the reference's
         // scan finds it) is carried from event to event: the pass that integrates the segment also
         // finds the smallest t1 of the list as it will be after this event (entry appended, or the
         // exiting entry swap-removed), so each event reads every active entry once.
         int i = 0;
-        m = 0;
-        float next_exit = INFINITY;
-        int exit_pos = -1;
+        if constexpr (!KEEP) {  // the window's collection holds every hit overlapping W0: the list starts empty
+            m = 0;
+            next_exit = INFINITY;
+            exit_pos = -1;
+        }
         for (;;) {
             const float4 hn = i < n ? S.H(i) : make_float4(INFINITY, 0.0f, 0.0f, 0.0f);  // (the entry's row, once)
             const float next_entry = hn.x;

@@ -92,6 +92,23 @@ public:
         }
     }
 
+    // integrator.h:422-498 MultiScatterGaussians::get_free_flight_distance(ray, events, target_tau) per ray, the
+    // events being the ray's own: the collision distance, or -1 where the ray leaves the mixture before the
+    // target is reached. *albedo (if given) receives evaluate_albedo (gmm.h:128-143) over the critical segment's
+    // active Gaussians at the collision, *n_active how many those are (both 0 where t < 0).
+    std::vector<float> query_free_flight(const std::vector<Ray>& rays, const std::vector<float>& target_tau,
+                                         std::vector<float>* albedo = nullptr, std::vector<uint32_t>* n_active = nullptr) const {
+        if (target_tau.size() != rays.size()) throw std::runtime_error("query_free_flight: one target_tau per ray");
+        vr_ctx* ctx = ready();
+        const std::vector<vr_ray> r = pack(rays, nullptr, 0.0f);
+        std::vector<float> t(r.size());
+        if (albedo) albedo->assign(r.size(), 0.0f);
+        if (n_active) n_active->assign(r.size(), 0u);
+        vr_cpp::check(vr_query_free_flight(ctx, r.data(), target_tau.data(), r.size(), t.data(), albedo ? albedo->data() : nullptr,
+                                           n_active ? n_active->data() : nullptr));
+        return t;
+    }
+
 private:
     std::vector<float> transmittance(const std::vector<vr_ray>& r, std::vector<float>* tau) const {
         vr_ctx* ctx = ready();

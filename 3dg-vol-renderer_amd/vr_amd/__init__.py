@@ -604,6 +604,48 @@ class Device:
                                         ev.ctypes.data_as(L.U32P), total.value, ctypes.byref(total)))
         return off.astype(np.int64), t, (ev >> 1).astype(np.int32), (ev & 1).astype(bool)
 
+    def query_free_flight(self, scene, origins, directions, tau, unit=False, return_albedo=False, return_active=False):
+        """One free-flight step per ray, MultiScatterGaussians::get_free_flight_distance (integrator.h:422-498):
+        origins, directions (n, 3) float32, tau the target optical depth (-log(1 - xi), drawn by the caller), a
+        scalar or (n,) float32 (it broadcasts). unit=True: the directions are of unit length already (a Ray
+        object's) and are used as they stand. Returns t (n,): the collision distance, or -1 where the ray leaves
+        the mixture first; then, if asked for, the albedo at the collision (gmm.h:128-143; 0 where t < 0) and the
+        number of Gaussians active there (int32). Invalid rays and NaN targets give NaN. With query_transmittance
+        (next-event estimation) and query_sigma this is a volumetric path tracer's kit."""
+        torch_in = _query_ray_args(origins, directions, tau)
+        self.upload(scene)
+        n = origins.shape[0]
+        if torch_in:
+            import torch
+            self._check_torch(origins, directions, *([tau] if _is_torch(tau) else []))
+            rays, stream = self._pack_rays_torch(origins, directions, 0.0)
+            if unit:
+                rays[:, 7] = 1.0
+            if _is_torch(tau):
+                tg = tau.reshape(-1).expand(n).contiguous()
+            else:
+                tg = torch.full((n,), float(tau), dtype=torch.float32, device=origins.device)
+            t = torch.empty(n, dtype=torch.float32, device=origins.device)
+            alb = torch.empty(n, dtype=torch.float32, device=origins.device) if return_albedo else None
+            act = torch.empty(n, dtype=torch.int32, device=origins.device) if return_active else None
+            check(lib().vr_query_free_flight_device(self._h, rays.data_ptr(), tg.data_ptr(), n, t.data_ptr(),
+                                                    alb.data_ptr() if return_albedo else None,
+                                                    act.data_ptr() if return_active else None, stream))
+        else:
+            rays = self._pack_rays_numpy(origins, directions, 0.0)
+            if unit:
+                rays[:, 7] = 1.0
+            tg = np.ascontiguousarray(np.broadcast_to(np.asarray(tau, np.float32).reshape(-1), (n,)))
+            t = np.empty(n, np.float32)
+            alb = np.empty(n, np.float32) if return_albedo else None
+            cnt = np.empty(n, np.uint32) if return_active else None
+            check(lib().vr_query_free_flight(self._h, rays.ctypes.data, fptr(tg), n, fptr(t),
+                                             fptr(alb) if return_albedo else None,
+                                             cnt.ctypes.data_as(L.U32P) if return_active else None))
+            act = cnt.astype(np.int32) if return_active else None
+        out = (t,) + ((alb,) if return_albedo else ()) + ((act,) if return_active else ())
+        return out if len(out) > 1 else t
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and L is not None and L._lib is not None:  # (L is None during interpreter teardown)

@@ -187,6 +187,8 @@ SIGNATURES = {
     "vr_query_events_count_device": (ST, [P, P, ctypes.c_size_t, P, ctypes.POINTER(ctypes.c_uint64)]),
     "vr_query_events_fill_device": (ST, [P, P, ctypes.c_size_t, P, P, P, ctypes.c_uint64, P]),
     "vr_query_events": (ST, [P, P, ctypes.c_size_t, U32P, FP, U32P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    "vr_query_free_flight": (ST, [P, P, FP, ctypes.c_size_t, FP, FP, U32P]),
+    "vr_query_free_flight_device": (ST, [P, P, P, ctypes.c_size_t, P, P, P, P]),
     "vr_query_pack_rays_device": (ST, [P, P, P, P, ctypes.c_uint32, ctypes.c_size_t, P, P]),
     "vr_render_rays": (ST, [P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(vr_render_params), FP, FP]),
     "vr_render_rays_device": (ST, [P, P, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(vr_render_params), P, P, P]),

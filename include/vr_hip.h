@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define VR_ABI_VERSION 10
+#define VR_ABI_VERSION 11
 
 typedef enum vr_status {
     VR_OK = 0,
@@ -483,7 +483,7 @@ vr_status vr_debug_tree(vr_ctx* ctx, int32_t array, void* out, size_t cap, size_
 vr_status vr_tree_limits(int32_t* leaf_max, int32_t* max_depth, int32_t* wide_stack_max);
 
 /* ---------------- mixture queries (gmm.h) ---------------- */
-/* The three questions GaussianMixtureModel answers about the mixture itself, for a batch of the caller's
+/* The questions GaussianMixtureModel and the free-flight integrators ask about the mixture itself, for a batch of the caller's
  * rays or points against the uploaded Gaussian scene (sphere scenes: VR_ERR_UNSUPPORTED). Every Gaussian is
  * tested with the exact forms (intersect_direct gaussian.h:126-164, optical_depth :208-231, mu_t :111-117 in
  * the reference's evaluation order), so hit decisions and entry / exit distances are the reference's bit for
@@ -548,6 +548,36 @@ vr_status vr_query_events_fill_device(vr_ctx* ctx, const vr_ray* d_rays, size_t 
  * t or ev and the call returns VR_ERR_OVERFLOW. */
 vr_status vr_query_events(vr_ctx* ctx, const vr_ray* rays, size_t n, uint32_t* offsets, float* t, uint32_t* ev, uint64_t cap,
                           uint64_t* total);
+/* One free-flight step (ABI 11): MultiScatterGaussians::get_free_flight_distance (integrator.h:422-498, the double
+ * running sum over the ray's events) with solve_distance (distance_solvers.h:143-187) for ray i and the caller's
+ * target optical depth tau_target[i]; the caller draws -log(1 - xi) itself, nothing here consumes random numbers.
+ * With vr_query_transmittance (next-event estimation) and vr_query_sigma this is what a volumetric path tracer
+ * over the uploaded scene needs. The sweep, the solvers and the albedo are the path kernels' own code, so every
+ * discrete decision (segment, active list and its swap-remove order, solver branch) is taken in the exact forms a
+ * VR_MULTI_SCATTER path's bounce takes it.
+ *   t[i]        the collision distance, >= 0; -1 when the ray leaves the mixture before the running sum exceeds
+ *               the target (:496-497) or has no events at all.
+ *   albedo[i]   (may be NULL) evaluate_albedo (gmm.h:128-143) over the critical segment's active Gaussians at
+ *               origin + t * direction, clamped to [0, 1] as :142 does; 0 when t < 0.
+ *   n_active[i] (may be NULL) the size of that active set; 0 when t < 0.
+ * Asking for albedo or n_active changes no bit of t. `unit` means what it means for the other queries; tmax is not
+ * read. A ray with a non-finite origin, or a direction whose squared norm is 0, NaN or infinite in f32, gets NaN in
+ * t and albedo and 0 in n_active, and so does a NaN target; every other target, <= 0 and +inf included (+inf: -1),
+ * goes through the reference's own comparisons.
+ * VR_OPT_FF_SOLVER 0-3 selects the solver as for frames; 4 (UNIFORM) is VR_ERR_UNSUPPORTED: it draws from a path's
+ * seed, which a query does not have. VR_OPT_FF_WINDOW0 sizes the first hit window as for frames and changes no
+ * result. VR_OPT_HALF_NODES / VR_OPT_DEVICE_BVH change the order in which Gaussians that enter at the same distance
+ * join the active list, hence the order of f32 sums over it: t may move by rounding, nothing else.
+ * Capacity: a ray on which more than 128 Gaussians overlap one point is run again with 1024-entry rows, as the
+ * frames' fallback runs such paths; beyond 1024 the ray gets NaN in t and albedo (0 in n_active). The host form
+ * then returns VR_ERR_OVERFLOW after writing every output of the batch; the device form reports the NaN only.
+ * The query owns its scratch rows (sized as a free-flight frame's), so a frame queued on another stream is never
+ * disturbed; the one-query-at-a-time rule above holds. */
+vr_status vr_query_free_flight(vr_ctx* ctx, const vr_ray* rays, const float* tau_target, size_t n, float* t, float* albedo,
+                               uint32_t* n_active);
+vr_status vr_query_free_flight_device(vr_ctx* ctx, const vr_ray* d_rays, const float* d_tau_target, size_t n, float* d_t,
+                                      float* d_albedo, uint32_t* d_n_active, void* stream);
+
 /* Packs n rays from separate device arrays (origins[3n], directions[3n], tmax[n], or one tmax for all rays
  * with tmax_stride = 0, else 1) into vr_ray rows on the device. Asynchronous on `stream`. */
 vr_status vr_query_pack_rays_device(vr_ctx* ctx, const float* d_origins, const float* d_directions, const float* d_tmax,

@@ -1,0 +1,255 @@
+"""Reference data for the free-flight query (Device.query_free_flight, vr_query_free_flight): the oracle's
+per-path record of a MultiScatterGaussians frame, the rays and targets that reproduce it, and a float64
+closed-form model of the mixture along those rays. Computed once per case, shared, never modified.
+
+The record. orc_ff_debug(buf) makes render_ff write 8 floats per pixel for sample 0, bounce 0: target_tau,
+t_scatter, albedo, Li, pos xyz, is_env. A pixel whose first flight escapes is left untouched (NaN here).
+
+The rays. With num_samples = 1 pixel (x, y)'s ray is sample_ray(u, v), u = (f32(x) + xi1) / W, v = (f32(y) + xi2) / H,
+xi1, xi2 the first two outputs of pcg32(derive_path_seed(x, y, 0), 1), each >> 8 and times 2^-24 in f32
+(integrator.h:560-570); they reproduce the record's pos bit for bit (test_flight_reference.py). The target is the
+record's slot 0; for a pixel the record leaves untouched it is -log(1 - xi3) of the third output in numpy's f32
+(glibc's logf may differ by an ulp; the escape margins of the cases are thousands of ulps).
+
+The model (float64, from records()): each Gaussian's interval [max(t_enter, 0), t_exit] on the ray is the oracle's
+f32 probe (intersect_direct, gaussian.h:126-164: the decision both sides take in f32), its optical depth up to t the
+closed form of gaussian.h:208-231, the active set at t the intervals holding t, and evaluate_albedo (gmm.h:128-143)
+the mu_t-weighted mean albedo over that set, clamped.
+"""
+import ctypes
+import functools
+
+import numpy as np
+
+import pyoracle as O
+import vr_amd as vr
+from helpers import CAM_POS, FOV, main_view_dir, scene_path
+
+QUERY = vr.Device.query_free_flight  # the method this module is the reference of (and of nothing else)
+W = H = 16
+PARITY = 1e-4  # the project's parity bound
+EDGE = 1e-5    # a t this close to an entry / exit distance has no defined active set
+
+
+def _iso(mean, sigma, dens, alb):
+    n = len(mean)
+    s2 = (np.asarray(sigma, np.float32) ** 2).astype(np.float32)
+    z = np.zeros(n, np.float32)
+    cov6 = np.stack([s2, z, z, s2, z, s2], 1).astype(np.float32)
+    return (np.asarray(mean, np.float32), cov6, np.full(n, dens, np.float32) if np.isscalar(dens) else dens,
+            np.asarray(alb, np.float32))
+
+
+def slab_gaussians():
+    """2000 isotropic Gaussians, default_rng(7): means x in U(-1, 1), y in U(0, 2), z in U(-1.5, 1.5), then sigma in
+    U(0.1, 0.2), then albedo in U(0.5, 0.9), in that draw order; density 0.02."""
+    rng = np.random.default_rng(7)
+    n = 2000
+    x, y, z = rng.uniform(-1, 1, n), rng.uniform(0, 2, n), rng.uniform(-1.5, 1.5, n)
+    sigma = rng.uniform(0.1, 0.2, n)
+    alb = rng.uniform(0.5, 0.9, n)
+    return _iso(np.stack([x, y, z], 1), sigma, 0.02, alb)
+
+
+def coincident_gaussians(n):
+    """n coincident Gaussians at (0, 1, 0), covariance 0.04 I, density 0.1, albedo 0.8."""
+    return _iso(np.tile(np.float32([0.0, 1.0, 0.0]), (n, 1)), np.full(n, 0.2), 0.1, np.full(n, 0.8))
+
+
+LIGHT = ((0.0, 4.0, 0.0), (30.0, 30.0, 30.0))
+# name -> (scene file or Gaussian recipe, camera type, fov)
+CASES = {
+    "250_random": ("250_random.txt", O.PINHOLE, FOV),
+    "1000_random": ("1000_random.txt", O.PINHOLE, FOV),
+    "many_gaussians": ("many_gaussians.txt", O.PINHOLE, FOV),
+    "250_random_ortho": ("250_random.txt", O.ORTHO, 0.0),
+    "slab": (slab_gaussians, O.PINHOLE, FOV),
+    "coincident200": (lambda: coincident_gaussians(200), O.PINHOLE, np.float32(0.08)),
+}
+# scattering rays of the 256 (the oracle's own counts, ANALYTIC_PLUS_NEWTON)
+SCATTERING = {"250_random": 222, "1000_random": 246, "many_gaussians": 44, "250_random_ortho": 256, "slab": 235,
+              "coincident200": 115}
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_scene(name):
+    src = CASES[name][0]
+    if callable(src):
+        return O.OracleScene.from_gaussians(*src(), [LIGHT[0]], [LIGHT[1]])
+    return O.OracleScene.load_gmm(scene_path(src))
+
+
+@functools.lru_cache(maxsize=None)
+def device_scene(name):
+    src = CASES[name][0]
+    if callable(src):
+        return vr.Scene.from_gaussians(*src(), lights=[vr.Light(*LIGHT)])
+    return vr.Scene.load_GMM(scene_path(src))
+
+
+@functools.lru_cache(maxsize=None)
+def record(name, solver=0):
+    """(256, 8) f32: the oracle's record under distance solver `solver` (distance_solvers.h:143-187; 0 is the
+    reference's ANALYTIC_PLUS_NEWTON), NaN where the first flight escapes."""
+    _, cam, fov = CASES[name]
+    L = O.lib()
+    L.orc_ff_debug.argtypes = [ctypes.POINTER(ctypes.c_float)]
+    L.orc_ff_debug.restype = None
+    L.orc_set_solver.argtypes = [ctypes.c_int]
+    L.orc_set_solver.restype = ctypes.c_int
+    buf = np.full((H * W, 8), np.nan, np.float32)
+    old = L.orc_set_solver(int(solver))
+    try:
+        L.orc_ff_debug(buf.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
+        O.render_ff(oracle_scene(name), cam, CAM_POS, main_view_dir(), float(fov), W, H, multi=True, num_samples=1)
+    finally:
+        L.orc_ff_debug(None)
+        L.orc_set_solver(old)
+    buf.setflags(write=False)
+    return buf
+
+
+@functools.lru_cache(maxsize=None)
+def rays(name):
+    """(origins (256, 3), unit directions (256, 3), targets (256,)) f32 of the case's paths, pixel y * W + x."""
+    _, cam_type, fov = CASES[name]
+    cam = vr.Pinhole_Camera(CAM_POS, main_view_dir(), fov) if cam_type == O.PINHOLE else \
+        vr.Orthographic_Camera(CAM_POS, main_view_dir())
+    f = np.float32
+    o, d, tgt = np.zeros((H * W, 3), f), np.zeros((H * W, 3), f), np.zeros(H * W, f)
+    for y in range(H):
+        for x in range(W):
+            xi = (O.pcg32(O.derive_path_seed(x, y, 0), 1, 3) >> 8).astype(f) * f(2.0 ** -24)
+            u, v = (f(x) + xi[0]) / f(W), (f(y) + xi[1]) / f(H)
+            r = cam.sample_ray((u, v))
+            o[y * W + x], d[y * W + x] = r.origin, r.direction
+            tgt[y * W + x] = -np.log(f(1) - xi[2])
+    rec = record(name)
+    tgt = np.where(np.isnan(rec[:, 0]), tgt, rec[:, 0]).astype(f)
+    for a in (o, d, tgt):
+        a.setflags(write=False)
+    return o, d, tgt
+
+
+def ask(dev, name, **kw):
+    """(t, albedo, n_active) of context `dev` for rays(name): the oracle's rays as they stand (unit = 1) and its targets."""
+    o, d, tgt = rays(name)
+    return QUERY(dev, device_scene(name), o, d, tgt, unit=True, return_albedo=True, return_active=True, **kw)
+
+
+class Model:
+    """The float64 mixture along the case's 256 rays."""
+
+    def __init__(self, name):
+        sc = oracle_scene(name)
+        o, d, _ = rays(name)
+        n, N = len(o), sc.num
+        pr = np.zeros((n, N, 4), np.float32)
+        fp = ctypes.POINTER(ctypes.c_float)
+        probe, base = O.lib().orc_gaussian_probe, pr.ctypes.data
+        for r in range(n):
+            po, pd = o[r].ctypes.data_as(fp), d[r].ctypes.data_as(fp)
+            for i in range(N):
+                probe(sc.h, i, po, pd, ctypes.cast(base + 16 * (r * N + i), fp))
+        # gmm.h:482-485: an entry event if t_enter >= 0 (clamped to 0 for an origin inside), an exit if t_exit >= 0
+        self.hit = (pr[..., 0] != 0) & (pr[..., 2] >= 0) & (pr[..., 2] >= pr[..., 1])
+        self.a = np.maximum(pr[..., 1].astype(np.float64), 0.0)
+        self.b = pr[..., 2].astype(np.float64)
+        rec = sc.records().astype(np.float64)
+        self.mean, self.dens, self.norm, self.alb = rec[:, :3], rec[:, 3], rec[:, 10], rec[:, 11]
+        m = rec[:, 4:10]
+        self.M = np.stack([np.stack([m[:, 0], m[:, 1], m[:, 2]], -1), np.stack([m[:, 1], m[:, 3], m[:, 4]], -1),
+                           np.stack([m[:, 2], m[:, 4], m[:, 5]], -1)], -2)  # (N, 3, 3)
+        self.o, self.d = o.astype(np.float64), d.astype(np.float64)
+        p = self.o[:, None, :] - self.mean[None]  # (n, N, 3)
+        Md = np.einsum("gij,rj->rgi", self.M, self.d)
+        self.A = np.einsum("ri,rgi->rg", self.d, Md)
+        self.B = 2.0 * np.einsum("rgi,rgi->rg", p, Md)
+        C = np.einsum("rgi,gij,rgj->rg", p, self.M, p)
+        with np.errstate(all="ignore"):
+            self.pref = self.dens * self.norm * np.sqrt(np.pi / (2.0 * self.A)) * np.exp(-0.5 * (C - self.B ** 2 / (4.0 * self.A)))
+            self.den = 2.0 * np.sqrt(2.0 * self.A)
+
+    def tau(self, t):
+        """(n,) float64: optical depth of the mixture on [0, t[i]] along ray i (t = inf: the whole ray)."""
+        from scipy.special import erf
+        t = np.asarray(t, np.float64)[:, None]
+        hi = np.minimum(t, self.b)
+        with np.errstate(all="ignore"):
+            od = self.pref * (erf((self.B + 2.0 * self.A * hi) / self.den) - erf((self.B + 2.0 * self.A * self.a) / self.den))
+        return np.where(self.hit & (hi > self.a), od, 0.0).sum(1)
+
+    def active(self, t):
+        """(n, N) bool: Gaussians with max(t_enter, 0) <= t < t_exit."""
+        t = np.asarray(t, np.float64)[:, None]
+        return self.hit & (self.a <= t) & (t < self.b)
+
+    def near_event(self, t):
+        """(n,) bool: t within EDGE of an entry or exit distance of the ray."""
+        t = np.asarray(t, np.float64)[:, None]
+        near = self.hit & ((np.abs(t - self.a) <= EDGE) | (np.abs(t - self.b) <= EDGE))
+        return near.any(1)
+
+    def albedo(self, t):
+        """(n,) float64: evaluate_albedo over active(t) at origin + t * direction (NaN for an empty set)."""
+        t = np.asarray(t, np.float64)
+        pos = self.o + t[:, None] * self.d
+        q = pos[:, None, :] - self.mean[None]
+        ex = -0.5 * np.einsum("rgi,gij,rgj->rg", q, self.M, q)
+        with np.errstate(all="ignore"):
+            mu = np.where(self.active(t), self.dens * self.norm * np.exp(ex), 0.0)
+            return np.clip((mu * self.alb).sum(1) / mu.sum(1), 0.0, 1.0)
+
+
+@functools.lru_cache(maxsize=None)
+def model(name):
+    return Model(name)
+
+
+def judge(name, t, albedo, n_active, solver=0, label=None):
+    """The issue's conditions 1-3 for a device answer (t, albedo, n_active) to rays(name) against record(name,
+    solver); prints every figure first, then asserts. Returns the figures."""
+    label = label or f"{name} solver {solver}"
+    rec, mdl = record(name, solver), model(name)
+    t = np.asarray(t, np.float32)
+    esc = np.isnan(rec[:, 1])
+    sc = ~esc
+    # 1. scatter-or-escape on every ray
+    wrong = np.nonzero((t == np.float32(-1.0)) != esc)[0]
+    bad_t = np.nonzero(sc & ~(t >= 0))[0]
+    print(f"{label}: {int(sc.sum())} scattering rays; scatter/escape disagreements {wrong.tolist()}")
+    both = sc & (t >= 0)
+    # 2. collision distance through the float64 model
+    t_orc = rec[:, 1]
+    td, to = np.where(both, t, 0.0), np.where(both, t_orc, 0.0)
+    dT = np.where(both, np.abs(np.exp(-mdl.tau(td)) - np.exp(-mdl.tau(to))), 0.0)
+    miss = np.nonzero(dT > PARITY)[0]
+    same = float(np.mean(t[both].view(np.uint32) == t_orc[both].view(np.uint32))) if both.any() else 1.0
+    dt_max = float(np.max(np.abs(t[both].astype(np.float64) - t_orc[both]))) if both.any() else 0.0
+    print(f"{label}: max |dTr| {dT.max():.3e}, rays over {PARITY:g}: "
+          f"{[(int(i), float(t[i]), float(t_orc[i]), float(dT[i])) for i in miss]}; bit-identical t {100 * same:.1f} %, "
+          f"max |dt| {dt_max:.3e}")
+    # 3. albedo and active count at the device's own t
+    skip = both & mdl.near_event(td)
+    use = both & ~skip
+    act = mdl.active(td).sum(1)
+    figures = {"scattering": int(sc.sum()), "dTr": float(dT.max()), "same_t": same, "dt": dt_max, "skipped": int(skip.sum())}
+    if albedo is not None:
+        da = np.where(use, np.abs(np.asarray(albedo, np.float64) - np.where(use, mdl.albedo(td), 0.0)), 0.0)
+        figures["dalbedo"] = float(da.max())
+        print(f"{label}: max |albedo - model| {da.max():.3e}; albedo where t < 0: {np.unique(np.asarray(albedo)[esc & (t < 0)]).tolist()}")
+    if n_active is not None:
+        na = np.asarray(n_active).astype(np.int64)
+        wrong_n = np.nonzero(use & (na != act))[0]
+        print(f"{label}: active counts {int(na[use].min()) if use.any() else 0}..{int(na[use].max()) if use.any() else 0}, "
+              f"wrong {[(int(i), int(na[i]), int(act[i])) for i in wrong_n]}; skipped near an event: {int(skip.sum())}")
+    assert wrong.size == 0 and bad_t.size == 0, (wrong, bad_t)
+    assert miss.size <= 1, miss
+    assert skip.sum() <= 2
+    if albedo is not None:
+        assert figures["dalbedo"] <= PARITY
+        assert np.all(np.asarray(albedo)[t < 0] == 0.0)
+    if n_active is not None:
+        assert wrong_n.size == 0
+        assert np.all(na[t < 0] == 0)
+    return figures

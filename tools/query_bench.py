@@ -6,6 +6,7 @@ rays packed on the device), every query is warmed up, and the figure is the medi
 events on torch's current stream. Prints one JSON line and, with --out, writes it to a file.
 
     python tools/query_bench.py [--gaussians 1000000] [--rays 4194304] [--points 4194304] [--repeats 5] [--out F]
+                                [--flight-scene FILE] [--only all|mixture|flight]
 """
 import argparse
 import json
@@ -47,20 +48,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--seed", type=int, default=2025)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--flight-scene", default=os.path.join(ROOT, "tests", "golden", "scenes", "1000_random.txt"))
+    ap.add_argument("--only", choices=("all", "mixture", "flight"), default="all")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         sys.exit("query_bench: no GPU (there is no CPU path to time)")
 
-    scene = vr.Scene(vr.Scene.GAUSSIANS)
-    scene.add_random_gaussians(args.gaussians, seed=args.seed, variant=0)
-    info = scene.info()
-    lo, hi = np.array(list(info.bounds_min), np.float32), np.array(list(info.bounds_max), np.float32)
-    o, d = camera_rays(args.rays)
-    p = np.random.default_rng(7).uniform(lo, hi, (args.points, 3)).astype(np.float32)
-    o, d, p = (torch.tensor(a).cuda() for a in (o, d, p))
+    o, d = (torch.tensor(a).cuda() for a in camera_rays(args.rays))
     dev = vr.Device.get(0)
-    dev.upload(scene)
 
     def timed(fn):
         for _ in range(args.warmup):
@@ -75,13 +71,52 @@ def main():
             ms.append(e0.elapsed_time(e1))
         return statistics.median(ms), ms, out
 
+    res = {"rays": args.rays, "repeats": args.repeats}
+    if args.only != "flight":
+        res.update(mixture(args, dev, o, d, timed))
+    if args.only != "mixture":
+        res.update(flight(args, dev, o, d, timed))
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+def flight(args, dev, o, d, timed):
+    """The free-flight query on --flight-scene, and query_events for the same rays on the same scene."""
+    import torch
+    scene = vr.Scene.load_GMM(args.flight_scene)
+    dev.upload(scene)
+    tau = torch.tensor((-np.log1p(-np.random.default_rng(7).random(args.rays))).astype(np.float32)).cuda()
+    t_ms, t_all, t = timed(lambda: dev.query_free_flight(scene, o, d, tau))
+    f_ms, f_all, _ = timed(lambda: dev.query_free_flight(scene, o, d, tau, return_albedo=True, return_active=True))
+    ev_ms, ev_all, ev = timed(lambda: dev.query_events(scene, o, d))
+    return {
+        "flight_scene": os.path.basename(args.flight_scene), "flight_ms": t_ms, "flight_mrays_s": args.rays / t_ms / 1e3,
+        "flight_full_ms": f_ms, "flight_full_mrays_s": args.rays / f_ms / 1e3,
+        "flight_scattering_share": float((t >= 0).float().mean()),
+        "flight_events_ms": ev_ms, "flight_events_mrays_s": args.rays / ev_ms / 1e3,
+        "flight_events_per_ray": int(ev[0][-1]) / args.rays,
+        "flight_all_ms": {"t": t_all, "t_albedo_active": f_all, "events": ev_all},
+    }
+
+
+def mixture(args, dev, o, d, timed):
+    import torch
+    scene = vr.Scene(vr.Scene.GAUSSIANS)
+    scene.add_random_gaussians(args.gaussians, seed=args.seed, variant=0)
+    info = scene.info()
+    lo, hi = np.array(list(info.bounds_min), np.float32), np.array(list(info.bounds_max), np.float32)
+    p = torch.tensor(np.random.default_rng(7).uniform(lo, hi, (args.points, 3)).astype(np.float32)).cuda()
+    dev.upload(scene)
     tr_ms, tr_all, tr = timed(lambda: dev.query_transmittance(scene, o, d))
     tau_ms, tau_all, _ = timed(lambda: dev.query_transmittance(scene, o, d, return_tau=True))
     ev_ms, ev_all, ev = timed(lambda: dev.query_events(scene, o, d))
     sg_ms, sg_all, sg = timed(lambda: dev.query_sigma(scene, p, return_active=True))
     n_events = int(ev[0][-1])
-    res = {
-        "gaussians": args.gaussians, "rays": args.rays, "points": args.points, "repeats": args.repeats,
+    return {
+        "gaussians": args.gaussians, "points": args.points,
         "transmittance_ms": tr_ms, "transmittance_mrays_s": args.rays / tr_ms / 1e3,
         "transmittance_tau_ms": tau_ms, "transmittance_tau_mrays_s": args.rays / tau_ms / 1e3,
         "events": n_events, "events_per_ray": n_events / args.rays, "events_ms": ev_ms,
@@ -92,11 +127,6 @@ def main():
         "timing": "median of HIP-event intervals on torch's current stream; the events figure spans both passes, "
                   "the count pass's host synchronisation and the allocation of the output tensors",
     }
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
 
 
 if __name__ == "__main__":

@@ -18,8 +18,9 @@
 // --devices renders on a multi-GPU context over exactly these GPUs (tiles split, RCCL gather); by
 // default every visible GPU is used (one GPU: a plain single-device context).
 // --dump-rays N prints the first N primary rays (host only, no GPU) — used by the CPU tests.
-// --query RAYS.bin runs the three mixture queries of vr/query.h (MixtureQuery: transmittance_up_to,
-// intersect_events, evaluate_sigma) on the scene and prints every result with the bits of its floats. The
+// --query RAYS.bin runs the mixture queries of vr/query.h (MixtureQuery: transmittance_up_to,
+// intersect_events, evaluate_sigma, then query_free_flight aimed at half of each ray's optical depth) on the scene
+// and prints every result with the bits of its floats. The
 // file: uint32 n_rays, uint32 n_points, then n_rays rows of 7 floats (origin, direction, tmax; the direction
 // is normalised by Ray's constructor), then n_points rows of 3 floats.
 #include <chrono>
@@ -73,6 +74,12 @@ static int run_queries(const Scene& scene, const std::string& path) {
     std::vector<uint32_t> na;
     q.evaluate_sigma(pos, sa, ss, &na);
     for (size_t i = 0; i < sa.size(); ++i) std::printf("sigma %zu %08x %08x %u\n", i, fbits(sa[i]), fbits(ss[i]), na[i]);
+    // one free-flight step per ray, aimed at half the optical depth the ray has up to its tmax
+    std::vector<float> target(tau.size()), albedo;
+    for (size_t i = 0; i < tau.size(); ++i) target[i] = 0.5f * tau[i];
+    std::vector<uint32_t> nf;
+    const std::vector<float> tf = q.query_free_flight(rays, target, &albedo, &nf);
+    for (size_t i = 0; i < tf.size(); ++i) std::printf("ff %zu %08x %08x %08x %u\n", i, fbits(target[i]), fbits(tf[i]), fbits(albedo[i]), nf[i]);
     return 0;
 }
 
