@@ -41,6 +41,9 @@ hipError_t query_events_count(const RenderArgs& A, const vr_ray* rays, uint32_t 
 hipError_t query_events_fill(const RenderArgs& A, const vr_ray* rays, uint32_t n, const uint32_t* offsets, uint32_t total,
                              unsigned long long* keys, unsigned long long* keys2, float* t, uint32_t* ev, uint32_t* next,
                              int refill, int cus, void* tmp, size_t& tmp_bytes, hipStream_t s);
+// (acc: 10 doubles per Gaussian of staging, zeroed by the call; grad: 10 floats per Gaussian)
+hipError_t query_transmittance_grad(const RenderArgs& A, const vr_ray* rays, const float* weight, uint32_t n, bool moving,
+                                    double* acc, float* grad, uint32_t* next, int refill, int cus, hipStream_t s);
 hipError_t query_pack_rays(const float* o, const float* d, const float* tmax, uint32_t tmax_stride, uint32_t n, vr_ray* rays,
                            hipStream_t s);
 

@@ -1,5 +1,5 @@
-// Mixture queries (vr_query_*, kernels/vr_query.hip, kernels/vr_query_flight.hip): batched transmittance, ray events, sigma
-// and free-flight distances.
+// Mixture queries (vr_query_*, kernels/vr_query.hip, kernels/vr_query_flight.hip): batched transmittance and its
+// gradient with respect to the Gaussians, ray events, sigma and free-flight distances.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -70,6 +70,45 @@ vr_status vr_query_transmittance(vr_ctx* c, const vr_ray* rays, size_t n, float*
     HIP_TRY(hipStreamSynchronize(c->stream), "query_transmittance_kernel");
     HIP_TRY(hipMemcpy(tr, c->q_out.get(), n * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
     if (tau) HIP_TRY(hipMemcpy(tau, c->q_out2.get(), n * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    return VR_OK;
+}
+
+vr_status vr_query_transmittance_grad_device(vr_ctx* c, const vr_ray* d_rays, const float* d_weight, size_t n, uint32_t flags,
+                                             float* d_grad, void* stream) {
+    c = first_device(c);
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_transmittance_grad", n, A));
+    if (flags & ~(uint32_t)VR_GRAD_FROZEN_BOUNDS) return fail(VR_ERR_INVALID, "vr_query_transmittance_grad: unknown flag bits");
+    if (!d_grad || (n > 0 && !d_rays)) return fail(VR_ERR_INVALID, "vr_query_transmittance_grad: NULL argument");
+    if (!aligned16(d_rays)) return fail(VR_ERR_INVALID, "vr_query_transmittance_grad: the device ray array must be 16-byte aligned");
+    // the staging rows are the query's own: a frame queued on another stream never sees them
+    VR_TRY(c->q_grad.grow((size_t)std::max(A.num_prims, 1) * 10, "hipMalloc(gradient staging)"));
+    HIP_TRY(query_transmittance_grad(A, d_rays, d_weight, (uint32_t)n, !(flags & VR_GRAD_FROZEN_BOUNDS), c->q_grad.get(), d_grad,
+                                     (uint32_t*)c->q_ctl.get() + 3, query_refill(c), c->cus, (hipStream_t)stream),
+            "query_grad_kernel");
+    return VR_OK;
+}
+
+vr_status vr_query_transmittance_grad(vr_ctx* c, const vr_ray* rays, const float* weight, size_t n, uint32_t flags, float* grad) {
+    c = first_device(c);
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_transmittance_grad", n, A));
+    if (flags & ~(uint32_t)VR_GRAD_FROZEN_BOUNDS) return fail(VR_ERR_INVALID, "vr_query_transmittance_grad: unknown flag bits");
+    if (!grad || (n > 0 && !rays)) return fail(VR_ERR_INVALID, "vr_query_transmittance_grad: NULL argument");
+    const size_t words = (size_t)std::max(A.num_prims, 0) * 10;
+    if (n == 0 || words == 0) {
+        std::memset(grad, 0, words * sizeof(float));
+        return VR_OK;
+    }
+    VR_TRY(c->q_in.grow(n * sizeof(vr_ray), "hipMalloc(query rays)"));
+    if (weight) VR_TRY(c->q_tau.grow(n, "hipMalloc(query weights)"));
+    VR_TRY(c->q_out.grow(words, "hipMalloc(query results)"));
+    HIP_TRY(hipMemcpy(c->q_in.get(), rays, n * sizeof(vr_ray), hipMemcpyHostToDevice), "hipMemcpy(query rays)");
+    if (weight) HIP_TRY(hipMemcpy(c->q_tau.get(), weight, n * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(query weights)");
+    VR_TRY(vr_query_transmittance_grad_device(c, (const vr_ray*)c->q_in.get(), weight ? c->q_tau.get() : nullptr, n, flags,
+                                              c->q_out.get(), c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream), "query_grad_kernel");
+    HIP_TRY(hipMemcpy(grad, c->q_out.get(), words * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
     return VR_OK;
 }
 

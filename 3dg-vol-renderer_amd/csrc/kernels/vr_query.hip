@@ -4,6 +4,8 @@
 //   intersect_events(ray, events)           gmm.h:457-515   query_events_count_kernel / _fill_kernel + sort
 //   evaluate_sigma(active, pos, sa, ss)     gmm.h:98-126    query_sigma_kernel (active = the 3-sigma ellipsoids
 //                                                            holding pos, the set the integrators pass)
+// and, for the first of them, the gradient of its optical depth with respect to the Gaussians
+// (query_grad_kernel / query_grad_finish_kernel: f32 decisions, double arithmetic per hit, double atomic adds).
 //
 // Floating point: a query is an API for fidelity, so every Gaussian is tested with the exact forms of
 // vr_march.h (quad / intersect / optical_depth / mu_t: the reference's evaluation order, correctly rounded
@@ -150,6 +152,117 @@ struct EventFillOp : QueryOp<EventFillOp, false> {
     __device__ __forceinline__ void invalid(uint32_t) {}
 };
 
+// The gradient of the ray's optical depth (TransOp<true>'s sum, without its rounding to f32) with respect to the
+// Gaussians it crosses, times the ray's weight, added to the staging rows acc[10 j .. 10 j + 9] of record j (tree
+// order): g_mean[3], G_M {00, 01, 02, 11, 12, 22} and U, each per unit density (include/vr_hip.h,
+// vr_query_transmittance_grad, has the formulas; query_grad_finish_kernel turns a row into the caller's).
+// The hit decision and the clip bounds [a, b] are TransOp's f32 ones; everything on a decided hit is double.
+// No early-out: every hit counts. The adds are global_atomic_add_f64 (no compare-and-swap loop), in arrival order.
+// A walk that is redone after Gaussians were added (the LDS stack could overflow) first takes those back: the
+// FIFO handed them out in traverse_wide's order, so the first `cnt` Gaussians of that walk are added with the
+// opposite sign before the pair-tree walk adds the ray's whole hit set.
+struct GradOp : QueryOp<GradOp, true> {
+    const float* weight;
+    double* acc;
+    uint32_t moving;  // the ellipsoid's own bounds move with the parameters (not VR_GRAD_FROZEN_BOUNDS)
+    float w;          // the ray's weight (negated while a walk is taken back)
+    uint32_t cnt;     // Gaussians this walk has tested
+    __device__ __forceinline__ int load(const RenderArgs& A, uint32_t id, Ray& r, float& tmax) {
+        w = weight ? weight[id] : 1.0f;
+        const int what = QueryOp::load(A, id, r, tmax);
+        return what == kRayWalk && w == 0.0f ? kRayFinish : what;
+    }
+    __device__ __forceinline__ void reset() { cnt = 0; }
+    __device__ void add(const GRec& g, const Ray& r, float a, float b, bool mv_in, bool mv_out, uint32_t j) {
+        const double dx = r.dx, dy = r.dy, dz = r.dz;
+        const double px = (double)r.ox - (double)g.mx, py = (double)r.oy - (double)g.my, pz = (double)r.oz - (double)g.mz;
+        const double m00 = g.m00, m01 = g.m01, m02 = g.m02, m11 = g.m11, m12 = g.m12, m22 = g.m22;
+        const double mdx = m00 * dx + m01 * dy + m02 * dz, mdy = m01 * dx + m11 * dy + m12 * dz, mdz = m02 * dx + m12 * dy + m22 * dz;
+        const double mpx = m00 * px + m01 * py + m02 * pz, mpy = m01 * px + m11 * py + m12 * pz, mpz = m02 * px + m12 * py + m22 * pz;
+        const double A = dx * mdx + dy * mdy + dz * mdz;
+        const double B = 2.0 * (px * mdx + py * mdy + pz * mdz);
+        const double C = px * mpx + py * mpy + pz * mpz;
+        const double m = -B / (2.0 * A);  // the line's closest approach: c = p + m d, u = t - m
+        const double cx = px + m * dx, cy = py + m * dy, cz = pz + m * dz;
+        const double ua = (double)a - m, ub = (double)b - m;
+        const double k = exp(-0.5 * (C - B * B / (4.0 * A)));
+        const double sA = sqrt(0.5 * A);
+        const double J0 = sqrt(3.14159265358979323846 / (2.0 * A)) * (erf(ub * sA) - erf(ua * sA));
+        const double ea = exp(-0.5 * A * ua * ua), eb = exp(-0.5 * A * ub * ub);
+        const double J1 = (ea - eb) / A;
+        const double J2 = (ua * ea - ub * eb) / A + J0 / A;
+        const double wn = (double)w * (double)g.norm;
+        const double s = wn * k;
+        // g_mean = s M (c J0 + d J1)
+        const double vx = cx * J0 + dx * J1, vy = cy * J0 + dy * J1, vz = cz * J0 + dz * J1;
+        double o0 = s * (m00 * vx + m01 * vy + m02 * vz);
+        double o1 = s * (m01 * vx + m11 * vy + m12 * vz);
+        double o2 = s * (m02 * vx + m12 * vy + m22 * vz);
+        // G_M = -s/2 (J0 c c^T + J1 (c d^T + d c^T) + J2 d d^T)
+        const double h = -0.5 * s;
+        double g00 = h * (J0 * cx * cx + J1 * (2.0 * cx * dx) + J2 * dx * dx);
+        double g01 = h * (J0 * cx * cy + J1 * (cx * dy + cy * dx) + J2 * dx * dy);
+        double g02 = h * (J0 * cx * cz + J1 * (cx * dz + cz * dx) + J2 * dx * dz);
+        double g11 = h * (J0 * cy * cy + J1 * (2.0 * cy * dy) + J2 * dy * dy);
+        double g12 = h * (J0 * cy * cz + J1 * (cy * dz + cz * dy) + J2 * dy * dz);
+        double g22 = h * (J0 * cz * cz + J1 * (2.0 * cz * dz) + J2 * dz * dz);
+        // a bound on the ellipsoid itself (q = 9 there) moves with the parameters: x = p + t d,
+        // wb = +- w norm e^-4.5 / (2 A t + B), G_M -= wb x x^T, g_mean += 2 wb M x
+        auto bound = [&](double t, double sg) {
+            const double x = px + t * dx, y = py + t * dy, z = pz + t * dz;
+            const double wb = sg * wn * 0.011108996538242306 / (2.0 * A * t + B);
+            g00 -= wb * x * x, g01 -= wb * x * y, g02 -= wb * x * z;
+            g11 -= wb * y * y, g12 -= wb * y * z, g22 -= wb * z * z;
+            o0 += 2.0 * wb * (mpx + t * mdx);
+            o1 += 2.0 * wb * (mpy + t * mdy);
+            o2 += 2.0 * wb * (mpz + t * mdz);
+        };
+        if (mv_out) bound((double)b, 1.0);
+        if (mv_in) bound((double)a, -1.0);
+        double* row = acc + 10 * (size_t)j;
+#ifdef VR_DIAG_GRAD_NO_ADD  // A/B: the per-hit arithmetic without its adds (kept alive by a comparison that never holds)
+        if (o0 + o1 + o2 + g00 + g01 + g02 + g11 + g12 + g22 + s * J0 != 0x1.23456789abcdep+300) return;
+#endif
+        atomicAdd(row + 0, o0);
+        atomicAdd(row + 1, o1);
+        atomicAdd(row + 2, o2);
+        atomicAdd(row + 3, g00);
+        atomicAdd(row + 4, g01);
+        atomicAdd(row + 5, g02);
+        atomicAdd(row + 6, g11);
+        atomicAdd(row + 7, g12);
+        atomicAdd(row + 8, g22);
+        atomicAdd(row + 9, s * J0);
+    }
+    __device__ __forceinline__ bool prim(const RenderArgs& A, const Ray& r, float tmax, uint32_t j) {
+        ++cnt;
+        const GRec g = load_rec(A.gauss, (int)j);
+        const Quad q = quad(g, r);
+        float t0, t1;
+        if (intersect(q, t0, t1)) {  // (t0 is clamped to 0 already)
+            const float b = fminf(tmax, t1);
+            if (b > t0) add(g, r, t0, b, moving != 0u && t0 > 0.0f, moving != 0u && t1 <= tmax, j);
+        }
+        return true;
+    }
+    __device__ __forceinline__ void redo(const RenderArgs& A, uint32_t id, const Ray& r, float tmax, float lim, int* stack) {
+        if (cnt > 0) {
+            uint32_t left = cnt;
+            w = -w;
+            auto prune = [&](float tmin, float) { return tmin <= lim; };
+            auto leaf = [&](uint32_t first, uint32_t count) {
+                for (uint32_t j = first; j < first + count && left > 0; ++j, --left) prim(A, r, tmax, j);
+                return left > 0;
+            };
+            traverse_wide<kStackSize>(A, r, stack, kQBlock, prune, leaf);
+            w = -w;
+        }
+        QueryOp::redo(A, id, r, tmax, lim, stack);
+    }
+    __device__ __forceinline__ void finish(const RenderArgs&, uint32_t, float) {}
+    __device__ __forceinline__ void invalid(uint32_t) {}
+};
+
 // One block of the persistent grid: its LDS stack and leaf FIFO, then the walk.
 template <class Op>
 __device__ __forceinline__ void query_walk(const RenderArgs& A, uint32_t n, uint32_t* next, int refill, Op& op) {
@@ -192,6 +305,54 @@ __global__ void __launch_bounds__(kQBlock) query_events_fill_kernel(RenderArgs A
     op.cap = cap;
     op.base = op.room = op.w = 0;
     query_walk(A, n, next, refill, op);
+}
+
+__global__ void __launch_bounds__(kQBlock) query_grad_kernel(RenderArgs A, const vr_ray* __restrict__ rays,
+                                                             const float* __restrict__ weight, uint32_t n, uint32_t moving,
+                                                             double* __restrict__ acc, uint32_t* __restrict__ next, int refill) {
+    GradOp op;
+    op.rays = rays;
+    op.weight = weight;
+    op.acc = acc;
+    op.moving = moving;
+    op.w = 0.0f;
+    op.cnt = 0;
+    query_walk(A, n, next, refill, op);
+}
+
+// Staging row j (tree order, per unit density, in M's space) -> the caller's row gauss_order[j]: d/d mean[3],
+// d/d cov {xx, xy, xz, yy, yz, zz}, d/d density. T = rho sum U, G_Sigma = -M G_M M - T M / 2, all in double and
+// rounded to f32 once; an off-diagonal stored number stands at (i, j) and (j, i), hence twice G_Sigma[i][j].
+__global__ void __launch_bounds__(256) query_grad_finish_kernel(const GaussianRecord* __restrict__ gauss,
+                                                                const uint32_t* __restrict__ order,
+                                                                const double* __restrict__ acc, uint32_t n,
+                                                                float* __restrict__ grad) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= n) return;
+    const GRec g = load_rec(gauss, (int)j);
+    const double* a = acc + 10 * (size_t)j;
+    const double rho = g.density, U = a[9], T = rho * U;
+    const double M[3][3] = {{g.m00, g.m01, g.m02}, {g.m01, g.m11, g.m12}, {g.m02, g.m12, g.m22}};
+    const double G[3][3] = {{rho * a[3], rho * a[4], rho * a[5]},
+                            {rho * a[4], rho * a[6], rho * a[7]},
+                            {rho * a[5], rho * a[7], rho * a[8]}};
+    double MG[3][3], S[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) MG[r][c] = M[r][0] * G[0][c] + M[r][1] * G[1][c] + M[r][2] * G[2][c];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) S[r][c] = -(MG[r][0] * M[0][c] + MG[r][1] * M[1][c] + MG[r][2] * M[2][c]) - 0.5 * T * M[r][c];
+    float* out = grad + 10 * (size_t)order[j];
+    // (+ 0.0: a Gaussian no ray hit gets +0, not the -0 of -(0) - 0)
+    out[0] = (float)(rho * a[0]);
+    out[1] = (float)(rho * a[1]);
+    out[2] = (float)(rho * a[2]);
+    out[3] = (float)(S[0][0] + 0.0);
+    out[4] = (float)(2.0 * S[0][1] + 0.0);
+    out[5] = (float)(2.0 * S[0][2] + 0.0);
+    out[6] = (float)(S[1][1] + 0.0);
+    out[7] = (float)(2.0 * S[1][2] + 0.0);
+    out[8] = (float)(S[2][2] + 0.0);
+    out[9] = (float)U;
 }
 
 // Sorted keys -> the caller's arrays: t, and ev = scene_index << 1 | entering.
@@ -358,6 +519,23 @@ hipError_t query_transmittance(const RenderArgs& A, const vr_ray* rays, uint32_t
     if (e != hipSuccess) return e;
     if (tau) hipLaunchKernelGGL(dev::query_transmittance_kernel<true>, query_grid(cus), dim3(dev::kQBlock), 0, s, A, rays, n, tr, tau, next, refill);
     else hipLaunchKernelGGL(dev::query_transmittance_kernel<false>, query_grid(cus), dim3(dev::kQBlock), 0, s, A, rays, n, tr, tau, next, refill);
+    return hipGetLastError();
+}
+
+// acc: 10 doubles per Gaussian of staging, zeroed here; grad: 10 floats per Gaussian, every one written.
+hipError_t query_transmittance_grad(const RenderArgs& A, const vr_ray* rays, const float* weight, uint32_t n, bool moving,
+                                    double* acc, float* grad, uint32_t* next, int refill, int cus, hipStream_t s) {
+    if (A.num_prims <= 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(next, 0, sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    if ((e = hipMemsetAsync(acc, 0, (size_t)A.num_prims * 10 * sizeof(double), s)) != hipSuccess) return e;
+    if (n > 0) {
+        hipLaunchKernelGGL(dev::query_grad_kernel, query_grid(cus), dim3(dev::kQBlock), 0, s, A, rays, weight, n, moving ? 1u : 0u,
+                           acc, next, refill);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(dev::query_grad_finish_kernel, dim3(((uint32_t)A.num_prims + 255u) / 256u), dim3(256), 0, s, A.gauss,
+                       A.gauss_order, acc, (uint32_t)A.num_prims, grad);
     return hipGetLastError();
 }
 

@@ -55,6 +55,23 @@ public:
         return transmittance(pack(rays, nullptr, tmax), tau);
     }
 
+    // The gradient of those optical depths with respect to the Gaussians (vr_query_transmittance_grad): row g of the
+    // result (10 floats per scene Gaussian) is sum_i weights[i] * d tau_i / d (mean[3], cov[6] = {xx, xy, xz, yy, yz,
+    // zz}, density); an empty `weights` means 1 for every ray. moving_bounds = false holds each Gaussian's entry and
+    // exit distances fixed (VR_GRAD_FROZEN_BOUNDS).
+    std::vector<float> transmittance_gradient(const std::vector<Ray>& rays, const std::vector<float>& tmax,
+                                              const std::vector<float>& weights = {}, bool moving_bounds = true) const {
+        if (tmax.size() != rays.size()) throw std::runtime_error("transmittance_gradient: one tmax per ray");
+        if (!weights.empty() && weights.size() != rays.size()) throw std::runtime_error("transmittance_gradient: one weight per ray");
+        vr_ctx* ctx = ready();
+        const std::vector<vr_ray> r = pack(rays, &tmax, 0.0f);
+        std::vector<float> grad(10 * scene_.get_num_primitives() + 1, 0.0f);  // (+ 1: never a NULL pointer)
+        vr_cpp::check(vr_query_transmittance_grad(ctx, r.data(), weights.empty() ? nullptr : weights.data(), r.size(),
+                                                  moving_bounds ? 0u : (uint32_t)VR_GRAD_FROZEN_BOUNDS, grad.data()));
+        grad.pop_back();
+        return grad;
+    }
+
     // gmm.h:457-515 intersect_events(ray, events) per ray: sorted by t; events with equal t in scene order,
     // entry before exit (not the order the reference's std::sort happens to leave).
     std::vector<std::vector<PrimitiveHitEvent>> intersect_events(const std::vector<Ray>& rays) const {

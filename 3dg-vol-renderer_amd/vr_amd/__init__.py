@@ -547,6 +547,42 @@ class Device:
             check(lib().vr_query_transmittance(self._h, rays.ctypes.data, n, fptr(tr), fptr(tau) if return_tau else None))
         return (tr, tau) if return_tau else tr
 
+    def query_transmittance_grad(self, scene, origins, directions, weights=None, tmax=float("inf"), moving_bounds=True):
+        """The gradient of the optical depth with respect to the Gaussians (vr_query_transmittance_grad): for the
+        rays of query_transmittance and one weight per ray (None: all 1; a loss over Tr passes -Tr * dL/dTr), the
+        (N, 10) float32 array sum_i weights[i] * d tau_i / d (mean[3], cov6 [xx xy xz yy yz zz], density) of scene
+        Gaussian g, tau_i being query_transmittance's tau. An off-diagonal cov6 entry is the derivative with
+        respect to the stored number (it stands at (i, j) and (j, i)). moving_bounds=False holds each Gaussian's
+        3-sigma entry / exit distances fixed (VR_GRAD_FROZEN_BOUNDS). Invalid rays and rays with tmax <= 0
+        contribute nothing. Sums are double atomics: reproducible to the rounding of a double sum, not bit for bit."""
+        torch_in = _query_ray_args(origins, directions, tmax)
+        n = origins.shape[0]
+        if weights is not None:
+            if _query_f32(weights, "weights", ()) != torch_in:
+                raise ValueError("weights must be of the same kind as origins")
+            if weights.shape[0] != n:
+                raise ValueError(f"weights has {weights.shape[0]} entries for {n} rays")
+        self.upload(scene)
+        N = scene.get_num_primitives()
+        flags = 0 if moving_bounds else L.VR_GRAD_FROZEN_BOUNDS
+        if N == 0:
+            return origins.new_zeros((0, 10)) if torch_in else np.zeros((0, 10), np.float32)
+        if torch_in:
+            import torch
+            self._check_torch(origins, directions, *([tmax] if _is_torch(tmax) else []), *([] if weights is None else [weights]))
+            rays, stream = self._pack_rays_torch(origins, directions, tmax)
+            wt = None if weights is None else weights.contiguous()
+            grad = torch.empty((N, 10), dtype=torch.float32, device=origins.device)
+            check(lib().vr_query_transmittance_grad_device(self._h, rays.data_ptr(), None if wt is None else wt.data_ptr(), n,
+                                                           flags, grad.data_ptr(), stream))
+        else:
+            rays = self._pack_rays_numpy(origins, directions, tmax)
+            wt = None if weights is None else np.ascontiguousarray(weights)
+            grad = np.empty((N, 10), np.float32)
+            check(lib().vr_query_transmittance_grad(self._h, rays.ctypes.data, None if wt is None else fptr(wt), n, flags,
+                                                    fptr(grad)))
+        return grad
+
     def query_sigma(self, scene, points, return_active=False):
         """GaussianMixtureModel::evaluate_sigma (gmm.h:98-126) at n points (n, 3) float32, over the Gaussians
         whose 3-sigma ellipsoid holds the point. Returns sigma (n, 2) = (sigma_a, sigma_s), or (sigma,

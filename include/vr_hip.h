@@ -515,6 +515,42 @@ vr_status vr_query_transmittance(vr_ctx* ctx, const vr_ray* rays, size_t n, floa
 vr_status vr_query_transmittance_device(vr_ctx* ctx, const vr_ray* d_rays, size_t n, float* d_tr, float* d_tau,
                                         void* stream);
 
+/* The gradient of the optical depth with respect to the Gaussians (differentiable transmittance):
+ *   grad[10 g + k] = sum_i weight[i] * d tau_i / d theta_{g,k}
+ * tau_i being what vr_query_transmittance returns as tau for ray i (tmax, unit and the validity rule as there), g the
+ * SCENE index and theta the vr_gaussian row in its own order: mean[3], cov[6] = {xx, xy, xz, yy, yz, zz}, density. An
+ * off-diagonal cov component is the derivative with respect to the stored number, which stands at (i, j) and (j, i):
+ * 2 G_Sigma[i][j]. Albedo and emission do not enter tau; gradients with respect to the rays are not computed.
+ * weight == NULL: every weight is 1. A weight is used as it stands: for a loss over Tr the caller passes dL/dtau =
+ * -Tr dL/dTr. Invalid rays contribute nothing, nor do rays with tmax <= 0 or NaN; a Gaussian no ray hits gets ten
+ * zeros. Every entry of grad (10 * num_primitives floats) is written; n == 0 zeroes it (VR_OK). Unknown flag bits:
+ * VR_ERR_INVALID; grad == NULL: VR_ERR_INVALID; the common errors above apply.
+ * Definition. From the record's f32 mean, M (inverse covariance), norm and density rho, read as doubles, and the ray,
+ * with p = o - mean: A = d.Md, B = 2 p.Md, C = p.Mp, q(t) = A t^2 + B t + C. [a, b] are the f32 clip bounds of the
+ * transmittance query, a = max(0, t_enter), b = min(tmax, t_exit) from the exact f32 intersect_direct, so the hit set is
+ * that query's bit for bit; a hit contributes iff b > a (no early-out at large optical depths). Centred at m = -B / 2A:
+ * c = p + m d, k = exp(-(C - B^2 / 4A) / 2), u = t - m, and over [u_a, u_b]
+ *   J0 = sqrt(pi / 2A) (erf(u_b sqrt(A / 2)) - erf(u_a sqrt(A / 2)))
+ *   J1 = (e^{-A u_a^2 / 2} - e^{-A u_b^2 / 2}) / A
+ *   J2 = (u_a e^{-A u_a^2 / 2} - u_b e^{-A u_b^2 / 2}) / A + J0 / A
+ *   U = norm k J0 (tau per unit density), G_M = -rho norm k (J0 c c^T + J1 (c d^T + d c^T) + J2 d d^T) / 2,
+ *   g_mean = rho norm k M (c J0 + d J1).
+ * Without VR_GRAD_FROZEN_BOUNDS the ellipsoid's own bounds move with the parameters: the exit iff t_exit <= tmax, the
+ * entry iff t_enter > 0. For each moving bound t, x = p + t d and w = +- rho norm e^{-4.5} / (2 A t + B) (+ exit,
+ * - entry; 2 A t + B in double at the f32 t): G_M -= w x x^T, g_mean += 2 w M x. (A ray that grazes the ellipsoid has
+ * 2 A t + B near 0: its bound terms are as large as the true derivative is.) With the flag the bounds are held, the
+ * gradient of the integral over a fixed interval. Per Gaussian, summed over the rays with their weights: T = rho sum U,
+ * G_Sigma = -M G_M M - T M / 2, and the density component is sum U.
+ * Arithmetic: the decisions are f32 (the forward query's), everything on a decided hit is double, the sums over rays
+ * are double atomic adds in arrival order and the result is rounded to f32 once. A result is therefore reproducible
+ * to the rounding of a double sum, not bit for bit, and does not depend on VR_OPT_HALF_NODES / VR_OPT_DEVICE_BVH
+ * beyond that. The staging (80 bytes per Gaussian) is the query's own and is zeroed on `stream` by each call. */
+enum { VR_GRAD_FROZEN_BOUNDS = 1 };
+vr_status vr_query_transmittance_grad(vr_ctx* ctx, const vr_ray* rays, const float* weight, size_t n, uint32_t flags,
+                                      float* grad);
+vr_status vr_query_transmittance_grad_device(vr_ctx* ctx, const vr_ray* d_rays, const float* d_weight, size_t n,
+                                             uint32_t flags, float* d_grad, void* stream);
+
 /* GaussianMixtureModel::evaluate_sigma (gmm.h:98-126) at n points xyz[3n], with `active` = the Gaussians
  * whose 3-sigma ellipsoid holds the point (p.(M p) - 9 <= 0 in f32, p = x - mean: the sign of
  * intersect_direct's C, gaussian.h:136, for a ray starting there), the set the integrators pass.

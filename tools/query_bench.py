@@ -6,7 +6,10 @@ rays packed on the device), every query is warmed up, and the figure is the medi
 events on torch's current stream. Prints one JSON line and, with --out, writes it to a file.
 
     python tools/query_bench.py [--gaussians 1000000] [--rays 4194304] [--points 4194304] [--repeats 5] [--out F]
-                                [--flight-scene FILE] [--only all|mixture|flight]
+                                [--flight-scene FILE] [--only all|mixture|flight|grad]
+
+--only grad times the optical-depth gradient query (Device.query_transmittance_grad, unit weights, moving and frozen
+bounds) beside the tau query on the same rays, on --flight-scene and on the make_random scene (--gaussians 0 skips it).
 """
 import argparse
 import json
@@ -49,7 +52,7 @@ def main():
     ap.add_argument("--seed", type=int, default=2025)
     ap.add_argument("--out", default=None)
     ap.add_argument("--flight-scene", default=os.path.join(ROOT, "tests", "golden", "scenes", "1000_random.txt"))
-    ap.add_argument("--only", choices=("all", "mixture", "flight"), default="all")
+    ap.add_argument("--only", choices=("all", "mixture", "flight", "grad"), default="all")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -72,15 +75,38 @@ def main():
         return statistics.median(ms), ms, out
 
     res = {"rays": args.rays, "repeats": args.repeats}
-    if args.only != "flight":
+    if args.only == "grad":
+        res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
+        res.update(grad(args, dev, o, d, timed))
+    if args.only in ("all", "mixture"):
         res.update(mixture(args, dev, o, d, timed))
-    if args.only != "mixture":
+    if args.only in ("all", "flight"):
         res.update(flight(args, dev, o, d, timed))
     line = json.dumps(res)
     print(line)
     if args.out:
         with open(args.out, "w") as f:
             f.write(line + "\n")
+
+
+def grad(args, dev, o, d, timed):
+    """The gradient query and the tau query on the same rays, per scene."""
+    scenes = [(os.path.basename(args.flight_scene), vr.Scene.load_GMM(args.flight_scene))]
+    if args.gaussians > 0:
+        big = vr.Scene(vr.Scene.GAUSSIANS)
+        big.add_random_gaussians(args.gaussians, seed=args.seed, variant=0)
+        scenes.append((f"make_random_{args.gaussians}", big))
+    out = []
+    for name, scene in scenes:
+        dev.upload(scene)
+        tau_ms, tau_all, tau = timed(lambda: dev.query_transmittance(scene, o, d, return_tau=True))
+        g_ms, g_all, g = timed(lambda: dev.query_transmittance_grad(scene, o, d))
+        f_ms, f_all, _ = timed(lambda: dev.query_transmittance_grad(scene, o, d, moving_bounds=False))
+        out.append({"scene": name, "gaussians": scene.get_num_primitives(), "tau_ms": tau_ms, "grad_ms": g_ms,
+                    "grad_frozen_ms": f_ms, "grad_mrays_s": args.rays / g_ms / 1e3, "grad_over_tau": g_ms / tau_ms,
+                    "gaussians_hit": int((g[:, 9] != 0).sum()), "mean_tau": float(tau[1].mean()),
+                    "all_ms": {"tau": tau_all, "grad": g_all, "grad_frozen": f_all}})
+    return {"grad": out, "timing": "median of HIP-event intervals on torch's current stream, inputs on the device"}
 
 
 def flight(args, dev, o, d, timed):

@@ -23,6 +23,8 @@
 // and prints every result with the bits of its floats. The
 // file: uint32 n_rays, uint32 n_points, then n_rays rows of 7 floats (origin, direction, tmax; the direction
 // is normalised by Ray's constructor), then n_points rows of 3 floats.
+// --query-grad RAYS.bin (the same file) prints MixtureQuery::transmittance_gradient of the file's rays, all weights 1:
+// one line `tg <scene index> <10 hex words>` per Gaussian (d/d mean[3], cov[6], density).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -45,7 +47,8 @@ static uint32_t fbits(float f) {
     return u;
 }
 
-static int run_queries(const Scene& scene, const std::string& path) {
+static void read_query_file(const std::string& path, std::vector<Ray>& rays, std::vector<float>& tmax,
+                            std::vector<Eigen::Vector3f>& pos) {
     std::FILE* f = std::fopen(path.c_str(), "rb");
     if (!f) throw std::runtime_error("cannot open " + path);
     uint32_t hdr[2] = {0, 0};
@@ -54,15 +57,19 @@ static int run_queries(const Scene& scene, const std::string& path) {
     ok = ok && std::fread(rows.data(), 4, rows.size(), f) == rows.size() && std::fread(pts.data(), 4, pts.size(), f) == pts.size();
     std::fclose(f);
     if (!ok) throw std::runtime_error("short query file " + path);
-    std::vector<Ray> rays;
-    std::vector<float> tmax;
     for (uint32_t i = 0; i < hdr[0]; ++i) {
         const float* r = &rows[7 * (size_t)i];
         rays.emplace_back(Eigen::Vector3f(r[0], r[1], r[2]), Eigen::Vector3f(r[3], r[4], r[5]));
         tmax.push_back(r[6]);
     }
-    std::vector<Eigen::Vector3f> pos;
     for (uint32_t i = 0; i < hdr[1]; ++i) pos.emplace_back(pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]);
+}
+
+static int run_queries(const Scene& scene, const std::string& path) {
+    std::vector<Ray> rays;
+    std::vector<float> tmax;
+    std::vector<Eigen::Vector3f> pos;
+    read_query_file(path, rays, tmax, pos);
     MixtureQuery q(scene);
     std::vector<float> tau;
     const std::vector<float> tr = q.transmittance_up_to(rays, tmax, &tau);
@@ -83,6 +90,21 @@ static int run_queries(const Scene& scene, const std::string& path) {
     return 0;
 }
 
+// --query-grad: the optical-depth gradient of the file's rays (their tmax; all weights 1), one line per Gaussian.
+static int run_query_grad(const Scene& scene, const std::string& path) {
+    std::vector<Ray> rays;
+    std::vector<float> tmax;
+    std::vector<Eigen::Vector3f> pos;
+    read_query_file(path, rays, tmax, pos);
+    const std::vector<float> g = MixtureQuery(scene).transmittance_gradient(rays, tmax);
+    for (size_t i = 0; i < g.size() / 10; ++i) {
+        std::printf("tg %zu", i);
+        for (int k = 0; k < 10; ++k) std::printf(" %08x", fbits(g[10 * i + k]));
+        std::printf("\n");
+    }
+    return 0;
+}
+
 static Eigen::Vector3f parse3(const char* s) {
     float a = 0, b = 0, c = 0;
     if (std::sscanf(s, "%f,%f,%f", &a, &b, &c) != 3) throw std::runtime_error(std::string("bad vector: ") + s);
@@ -100,7 +122,7 @@ int main(int argc, char** argv) try {
     int inverse = 0, stoch = 4, final_spp = 0;
     uint64_t seed = 0;
     float lr = 1e-2f;
-    std::string ref_path, sfd_out, gif_path, query_path;
+    std::string ref_path, sfd_out, gif_path, query_path, query_grad_path;
     int frames = 120;
     float fps = 30.0f;
     Eigen::Vector3f pos(0, 1, 6), lookat(0, 1, 0);
@@ -126,6 +148,7 @@ int main(int argc, char** argv) try {
         else if (a == "--dump-rays") dump = std::atoi(next());
         else if (a == "--record") record = true;
         else if (a == "--query") query_path = next();
+        else if (a == "--query-grad") query_grad_path = next();
         else if (a == "--gif") gif_path = next();
         else if (a == "--frames") frames = std::atoi(next());
         else if (a == "--fps") fps = std::strtof(next(), nullptr);
@@ -182,6 +205,7 @@ int main(int argc, char** argv) try {
     }
 
     if (!query_path.empty()) return run_queries(scene, query_path);
+    if (!query_grad_path.empty()) return run_query_grad(scene, query_grad_path);
 
     if (!gif_path.empty()) {  // main.cpp:81-114
         const float radius = 6.0f, height_pos = 1.0f;
