@@ -131,7 +131,7 @@ struct vr_ctx {
     vr::DevBuf<uint32_t> q_off, q_cnt;          // events: offsets (host form), counts,
     vr::DevBuf<unsigned long long> q_keys, q_keys2;  // sort keys (in / out),
     vr::DevBuf<std::byte> q_tmp;                // scan + sort scratch
-    vr::DevBuf<std::byte> q_ctl;      // words [0..3] ray counters of the four persistent walks, [4..5] the 64-bit event total
+    vr::DevBuf<std::byte> q_ctl;      // words [0..3], [6] ray counters of the five persistent walks, [4..5] the 64-bit event total
     vr::DevBuf<double> q_grad;        // gradient query: 10 doubles of staging per Gaussian (tree order), zeroed per call
     // free-flight query (kernels/vr_query_flight.hip): its own scratch rows (the layouts of ff_scratch and of
     // ff_fb's rows), so a frame queued on another stream never shares them; counters + queue of rays over the rows

@@ -1,5 +1,5 @@
 // Mixture queries (vr_query_*, kernels/vr_query.hip, kernels/vr_query_flight.hip): batched transmittance and its
-// gradient with respect to the Gaussians, ray events, sigma and free-flight distances.
+// gradients with respect to the Gaussians and to the rays, ray events, sigma and free-flight distances.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -109,6 +109,39 @@ vr_status vr_query_transmittance_grad(vr_ctx* c, const vr_ray* rays, const float
                                               c->q_out.get(), c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream), "query_grad_kernel");
     HIP_TRY(hipMemcpy(grad, c->q_out.get(), words * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    return VR_OK;
+}
+
+vr_status vr_query_transmittance_ray_grad_device(vr_ctx* c, const vr_ray* d_rays, size_t n, uint32_t flags, vr_ray_grad* d_out,
+                                                 void* stream) {
+    c = first_device(c);
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_transmittance_ray_grad", n, A));
+    if (flags & ~(uint32_t)VR_GRAD_FROZEN_BOUNDS) return fail(VR_ERR_INVALID, "vr_query_transmittance_ray_grad: unknown flag bits");
+    if (n == 0) return VR_OK;
+    if (!d_rays || !d_out) return fail(VR_ERR_INVALID, "vr_query_transmittance_ray_grad: NULL argument");
+    if (!aligned16(d_rays) || !aligned16(d_out))
+        return fail(VR_ERR_INVALID, "vr_query_transmittance_ray_grad: the device arrays must be 16-byte aligned");
+    HIP_TRY(query_transmittance_ray_grad(A, d_rays, (uint32_t)n, !(flags & VR_GRAD_FROZEN_BOUNDS), d_out,
+                                         (uint32_t*)c->q_ctl.get() + 6, query_refill(c), c->cus, (hipStream_t)stream),
+            "query_ray_grad_kernel");
+    return VR_OK;
+}
+
+vr_status vr_query_transmittance_ray_grad(vr_ctx* c, const vr_ray* rays, size_t n, uint32_t flags, vr_ray_grad* out) {
+    c = first_device(c);
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_transmittance_ray_grad", n, A));
+    if (flags & ~(uint32_t)VR_GRAD_FROZEN_BOUNDS) return fail(VR_ERR_INVALID, "vr_query_transmittance_ray_grad: unknown flag bits");
+    if (n == 0) return VR_OK;
+    if (!rays || !out) return fail(VR_ERR_INVALID, "vr_query_transmittance_ray_grad: NULL argument");
+    VR_TRY(c->q_in.grow(n * sizeof(vr_ray), "hipMalloc(query rays)"));
+    VR_TRY(c->q_out.grow(n * (sizeof(vr_ray_grad) / sizeof(float)), "hipMalloc(query results)"));
+    HIP_TRY(hipMemcpy(c->q_in.get(), rays, n * sizeof(vr_ray), hipMemcpyHostToDevice), "hipMemcpy(query rays)");
+    VR_TRY(vr_query_transmittance_ray_grad_device(c, (const vr_ray*)c->q_in.get(), n, flags, (vr_ray_grad*)c->q_out.get(),
+                                                  c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream), "query_ray_grad_kernel");
+    HIP_TRY(hipMemcpy(out, c->q_out.get(), n * sizeof(vr_ray_grad), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
     return VR_OK;
 }
 

@@ -5,7 +5,8 @@
 //   evaluate_sigma(active, pos, sa, ss)     gmm.h:98-126    query_sigma_kernel (active = the 3-sigma ellipsoids
 //                                                            holding pos, the set the integrators pass)
 // and, for the first of them, the gradient of its optical depth with respect to the Gaussians
-// (query_grad_kernel / query_grad_finish_kernel: f32 decisions, double arithmetic per hit, double atomic adds).
+// (query_grad_kernel / query_grad_finish_kernel: f32 decisions, double arithmetic per hit, double atomic adds)
+// and with respect to the ray (query_ray_grad_kernel: the same per-hit arithmetic, summed per ray in registers).
 //
 // Floating point: a query is an API for fidelity, so every Gaussian is tested with the exact forms of
 // vr_march.h (quad / intersect / optical_depth / mu_t: the reference's evaluation order, correctly rounded
@@ -152,6 +153,38 @@ struct EventFillOp : QueryOp<EventFillOp, false> {
     __device__ __forceinline__ void invalid(uint32_t) {}
 };
 
+// The head of a decided hit's double arithmetic (include/vr_hip.h, vr_query_transmittance_grad, has the notation): the
+// record's f32 numbers and the ray read as doubles, p = o - mean, M d, M p, A, B, the closest approach m, c = p + m d,
+// u = t - m at the f32 clip bounds [a, b], k and the moments. RayGradOp's; GradOp::add keeps its own copy of the same
+// lines, because calling this from it changes query_grad_kernel's register allocation (SGPR spills 99 -> 95).
+struct HitMoments {
+    double dx, dy, dz, px, py, pz;
+    double m00, m01, m02, m11, m12, m22;
+    double mdx, mdy, mdz, mpx, mpy, mpz;
+    double A, B, m, cx, cy, cz, k, eb, J0, J1, J2;
+};
+__device__ __forceinline__ HitMoments hit_moments(const GRec& g, const Ray& r, float a, float b) {
+    const double dx = r.dx, dy = r.dy, dz = r.dz;
+    const double px = (double)r.ox - (double)g.mx, py = (double)r.oy - (double)g.my, pz = (double)r.oz - (double)g.mz;
+    const double m00 = g.m00, m01 = g.m01, m02 = g.m02, m11 = g.m11, m12 = g.m12, m22 = g.m22;
+    const double mdx = m00 * dx + m01 * dy + m02 * dz, mdy = m01 * dx + m11 * dy + m12 * dz, mdz = m02 * dx + m12 * dy + m22 * dz;
+    const double mpx = m00 * px + m01 * py + m02 * pz, mpy = m01 * px + m11 * py + m12 * pz, mpz = m02 * px + m12 * py + m22 * pz;
+    const double A = dx * mdx + dy * mdy + dz * mdz;
+    const double B = 2.0 * (px * mdx + py * mdy + pz * mdz);
+    const double C = px * mpx + py * mpy + pz * mpz;
+    const double m = -B / (2.0 * A);  // the line's closest approach: c = p + m d, u = t - m
+    const double cx = px + m * dx, cy = py + m * dy, cz = pz + m * dz;
+    const double ua = (double)a - m, ub = (double)b - m;
+    const double k = exp(-0.5 * (C - B * B / (4.0 * A)));
+    const double sA = sqrt(0.5 * A);
+    const double J0 = sqrt(3.14159265358979323846 / (2.0 * A)) * (erf(ub * sA) - erf(ua * sA));
+    const double ea = exp(-0.5 * A * ua * ua), eb = exp(-0.5 * A * ub * ub);
+    const double J1 = (ea - eb) / A;
+    const double J2 = (ua * ea - ub * eb) / A + J0 / A;
+    return HitMoments{dx, dy, dz, px, py, pz, m00, m01, m02, m11, m12, m22, mdx, mdy, mdz, mpx, mpy, mpz,
+                      A, B, m, cx, cy, cz, k, eb, J0, J1, J2};
+}
+
 // The gradient of the ray's optical depth (TransOp<true>'s sum, without its rounding to f32) with respect to the
 // Gaussians it crosses, times the ray's weight, added to the staging rows acc[10 j .. 10 j + 9] of record j (tree
 // order): g_mean[3], G_M {00, 01, 02, 11, 12, 22} and U, each per unit density (include/vr_hip.h,
@@ -263,6 +296,86 @@ struct GradOp : QueryOp<GradOp, true> {
     __device__ __forceinline__ void invalid(uint32_t) {}
 };
 
+// The gradient of the ray's optical depth with respect to the ray itself, and the optical depth: row `id` of out
+// (vr_ray_grad: d tau / d origin[3], d tau / d tmax, d tau / d direction[3], tau; include/vr_hip.h,
+// vr_query_transmittance_ray_grad, has the formulas). Hit decisions, clip bounds and tau are TransOp<true>'s, f32 and
+// bit for bit; everything else on a decided hit is double. The seven sums and TransOp's stay in registers and are
+// rounded once in finish(), so nothing is written before it: the base redo() (reset, the whole walk again) is right
+// as it stands, and there are no atomics.
+struct RayGradOp : QueryOp<RayGradOp, true> {
+    vr_ray_grad* out;
+    uint32_t moving;   // the ellipsoid's own bounds move with the ray (not VR_GRAD_FROZEN_BOUNDS)
+    float dx, dy, dz;  // the direction the walk uses
+    float len2;        // the loader's f32 squared norm of the stored direction; 0: `unit` was set, no chain through v / |v|
+    double o0, o1, o2, d0, d1, d2, gt, sum;
+    __device__ __forceinline__ int load(const RenderArgs& A, uint32_t id, Ray& r, float& tmax) {
+        const int what = QueryOp::load(A, id, r, tmax);
+        const float4 b = reinterpret_cast<const float4*>(rays)[2 * (size_t)id + 1];
+        len2 = b.w != 0.0f ? 0.0f : dot3(b.x, b.y, b.z, b.x, b.y, b.z);
+        dx = r.dx, dy = r.dy, dz = r.dz;
+        return what;
+    }
+    __device__ __forceinline__ void reset() { o0 = o1 = o2 = d0 = d1 = d2 = gt = sum = 0.0; }
+    __device__ void add(const GRec& g, const Ray& r, float a, float b, bool mv_in, bool mv_out, bool clipped) {
+        const HitMoments h = hit_moments(g, r, a, b);
+        const double rn = (double)g.density * (double)g.norm;
+        const double s = rn * h.k;
+        // g_o = -s M (c J0 + d J1), g_d = -s M (m c J0 + (c + m d) J1 + d J2) = -s M (m v + c J1 + d J2)
+        const double vx = h.cx * h.J0 + h.dx * h.J1, vy = h.cy * h.J0 + h.dy * h.J1, vz = h.cz * h.J0 + h.dz * h.J1;
+        const double ux = h.m * vx + h.cx * h.J1 + h.dx * h.J2, uy = h.m * vy + h.cy * h.J1 + h.dy * h.J2,
+                     uz = h.m * vz + h.cz * h.J1 + h.dz * h.J2;
+        double go0 = -s * (h.m00 * vx + h.m01 * vy + h.m02 * vz);
+        double go1 = -s * (h.m01 * vx + h.m11 * vy + h.m12 * vz);
+        double go2 = -s * (h.m02 * vx + h.m12 * vy + h.m22 * vz);
+        double gd0 = -s * (h.m00 * ux + h.m01 * uy + h.m02 * uz);
+        double gd1 = -s * (h.m01 * ux + h.m11 * uy + h.m12 * uz);
+        double gd2 = -s * (h.m02 * ux + h.m12 * uy + h.m22 * uz);
+        // a bound on the ellipsoid itself (q = 9 there) moves with the ray: x = p + t d,
+        // wb = +- rho norm e^-4.5 / (2 A t + B), g_o -= 2 wb M x, g_d -= 2 wb t M x
+        auto bound = [&](double t, double sg) {
+            const double wb = 2.0 * sg * rn * 0.011108996538242306 / (2.0 * h.A * t + h.B);
+            const double x = wb * (h.mpx + t * h.mdx), y = wb * (h.mpy + t * h.mdy), z = wb * (h.mpz + t * h.mdz);
+            go0 -= x, go1 -= y, go2 -= z;
+            gd0 -= t * x, gd1 -= t * y, gd2 -= t * z;
+        };
+        if (mv_out) bound((double)b, 1.0);
+        if (mv_in) bound((double)a, -1.0);
+        o0 += go0, o1 += go1, o2 += go2;
+        d0 += gd0, d1 += gd1, d2 += gd2;
+        if (clipped) gt += s * h.eb;  // the upper bound is tmax itself: the integrand there
+    }
+    __device__ __forceinline__ bool prim(const RenderArgs& A, const Ray& r, float tmax, uint32_t j) {
+        const GRec g = load_rec(A.gauss, (int)j);
+        const Quad q = quad(g, r);
+        float t0, t1;
+        if (intersect(q, t0, t1)) {
+            const float a = fmaxf(0.0f, t0);
+            const float b = fminf(tmax, t1);
+            if (b > a) {
+                sum += (double)optical_depth(g, q, a, b);
+                add(g, r, a, b, moving != 0u && t0 > 0.0f, moving != 0u && t1 <= tmax, t1 > tmax);
+            }
+        }
+        return true;
+    }
+    __device__ __forceinline__ void finish(const RenderArgs&, uint32_t id, float) {
+        double e0 = d0, e1 = d1, e2 = d2;
+        if (len2 != 0.0f) {  // the library normalised v: (g_d - d (d . g_d)) / |v|
+            const double x = dx, y = dy, z = dz;
+            const double dot = x * d0 + y * d1 + z * d2, len = sqrt((double)len2);
+            e0 = (d0 - x * dot) / len, e1 = (d1 - y * dot) / len, e2 = (d2 - z * dot) / len;
+        }
+        float4* p = reinterpret_cast<float4*>(out) + 2 * (size_t)id;
+        p[0] = make_float4((float)o0, (float)o1, (float)o2, (float)gt);
+        p[1] = make_float4((float)e0, (float)e1, (float)e2, (float)sum);
+    }
+    __device__ __forceinline__ void invalid(uint32_t id) {
+        const float q = __builtin_nanf("");
+        float4* p = reinterpret_cast<float4*>(out) + 2 * (size_t)id;
+        p[0] = p[1] = make_float4(q, q, q, q);
+    }
+};
+
 // One block of the persistent grid: its LDS stack and leaf FIFO, then the walk.
 template <class Op>
 __device__ __forceinline__ void query_walk(const RenderArgs& A, uint32_t n, uint32_t* next, int refill, Op& op) {
@@ -317,6 +430,18 @@ __global__ void __launch_bounds__(kQBlock) query_grad_kernel(RenderArgs A, const
     op.moving = moving;
     op.w = 0.0f;
     op.cnt = 0;
+    query_walk(A, n, next, refill, op);
+}
+
+__global__ void __launch_bounds__(kQBlock) query_ray_grad_kernel(RenderArgs A, const vr_ray* __restrict__ rays, uint32_t n,
+                                                                 uint32_t moving, vr_ray_grad* __restrict__ out,
+                                                                 uint32_t* __restrict__ next, int refill) {
+    RayGradOp op;
+    op.rays = rays;
+    op.out = out;
+    op.moving = moving;
+    op.dx = op.dy = op.dz = op.len2 = 0.0f;
+    op.reset();
     query_walk(A, n, next, refill, op);
 }
 
@@ -536,6 +661,16 @@ hipError_t query_transmittance_grad(const RenderArgs& A, const vr_ray* rays, con
     }
     hipLaunchKernelGGL(dev::query_grad_finish_kernel, dim3(((uint32_t)A.num_prims + 255u) / 256u), dim3(256), 0, s, A.gauss,
                        A.gauss_order, acc, (uint32_t)A.num_prims, grad);
+    return hipGetLastError();
+}
+
+// out: one vr_ray_grad row per ray, every one written.
+hipError_t query_transmittance_ray_grad(const RenderArgs& A, const vr_ray* rays, uint32_t n, bool moving, vr_ray_grad* out,
+                                        uint32_t* next, int refill, int cus, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(next, 0, sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(dev::query_ray_grad_kernel, query_grid(cus), dim3(dev::kQBlock), 0, s, A, rays, n, moving ? 1u : 0u, out,
+                       next, refill);
     return hipGetLastError();
 }
 

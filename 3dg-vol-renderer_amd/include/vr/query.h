@@ -72,6 +72,21 @@ public:
         return grad;
     }
 
+    // The gradient of those optical depths with respect to the rays (vr_query_transmittance_ray_grad): row i is
+    // d tau_i / d (origin, tmax, direction) and tau_i itself (the forward query's, bit for bit). A Ray's direction is
+    // its constructor's (unit = 1), so `direction` is the derivative with respect to the three stored components
+    // taken as free. moving_bounds = false holds each Gaussian's entry and exit distances fixed (VR_GRAD_FROZEN_BOUNDS).
+    std::vector<vr_ray_grad> transmittance_ray_gradient(const std::vector<Ray>& rays, const std::vector<float>& tmax,
+                                                        bool moving_bounds = true) const {
+        if (tmax.size() != rays.size()) throw std::runtime_error("transmittance_ray_gradient: one tmax per ray");
+        vr_ctx* ctx = ready();
+        const std::vector<vr_ray> r = pack(rays, &tmax, 0.0f);
+        std::vector<vr_ray_grad> out(r.size());
+        vr_cpp::check(vr_query_transmittance_ray_grad(ctx, r.data(), r.size(),
+                                                      moving_bounds ? 0u : (uint32_t)VR_GRAD_FROZEN_BOUNDS, out.data()));
+        return out;
+    }
+
     // gmm.h:457-515 intersect_events(ray, events) per ray: sorted by t; events with equal t in scene order,
     // entry before exit (not the order the reference's std::sort happens to leave).
     std::vector<std::vector<PrimitiveHitEvent>> intersect_events(const std::vector<Ray>& rays) const {

@@ -583,6 +583,37 @@ class Device:
                                                     fptr(grad)))
         return grad
 
+    def query_transmittance_ray_grad(self, scene, origins, directions, tmax=float("inf"), unit=False, moving_bounds=True):
+        """The gradient of the optical depth with respect to the rays (vr_query_transmittance_ray_grad), and the
+        optical depth: for the rays of query_transmittance, (d_origin (n, 3), d_direction (n, 3), d_tmax (n,),
+        tau (n,)) float32, row i being d tau_i / d (origin, direction, tmax) of ray i and tau_i query_transmittance's
+        tau bit for bit. unit=False: the library normalises the directions and d_direction holds the chain through
+        v / |v| (it is orthogonal to the direction); unit=True: the directions are unit vectors already, are used as
+        they stand, and d_direction is the derivative with respect to the three components taken as free.
+        d_tmax is the integrand at tmax where tmax cuts a Gaussian short, else 0 (always 0 for tmax = inf).
+        moving_bounds=False holds each Gaussian's 3-sigma entry / exit distances fixed (VR_GRAD_FROZEN_BOUNDS).
+        Invalid rays give NaN in every output, rays with tmax <= 0 or NaN zeros. Sums are per ray, in double, with
+        no atomics. Inputs are numpy arrays or torch tensors on this context's device, never a mix."""
+        torch_in = _query_ray_args(origins, directions, tmax)
+        self.upload(scene)
+        n = origins.shape[0]
+        flags = 0 if moving_bounds else L.VR_GRAD_FROZEN_BOUNDS
+        if torch_in:
+            import torch
+            self._check_torch(origins, directions, *([tmax] if _is_torch(tmax) else []))
+            rays, stream = self._pack_rays_torch(origins, directions, tmax)
+            if unit:
+                rays[:, 7] = 1.0
+            out = torch.empty((n, 8), dtype=torch.float32, device=origins.device)
+            check(lib().vr_query_transmittance_ray_grad_device(self._h, rays.data_ptr(), n, flags, out.data_ptr(), stream))
+        else:
+            rays = self._pack_rays_numpy(origins, directions, tmax)
+            if unit:
+                rays[:, 7] = 1.0
+            out = np.empty((n, 8), np.float32)
+            check(lib().vr_query_transmittance_ray_grad(self._h, rays.ctypes.data, n, flags, out.ctypes.data))
+        return out[:, 0:3], out[:, 4:7], out[:, 3], out[:, 7]
+
     def query_sigma(self, scene, points, return_active=False):
         """GaussianMixtureModel::evaluate_sigma (gmm.h:98-126) at n points (n, 3) float32, over the Gaussians
         whose 3-sigma ellipsoid holds the point. Returns sigma (n, 2) = (sigma_a, sigma_s), or (sigma,

@@ -28,7 +28,7 @@ VR_OPT_SEC_TIGHT = 11
 VR_OPT_MARCH_WIDE_MIN = 12
 VR_OPT_FF_KERNEL = 13
 VR_OPT_SEC_FILTER = 14
-VR_GRAD_FROZEN_BOUNDS = 1  # vr_query_transmittance_grad flags
+VR_GRAD_FROZEN_BOUNDS = 1  # vr_query_transmittance_grad / _ray_grad flags
 
 f3 = ctypes.c_float * 3
 
@@ -185,6 +185,8 @@ SIGNATURES = {
     "vr_query_transmittance_device": (ST, [P, P, ctypes.c_size_t, P, P, P]),
     "vr_query_transmittance_grad": (ST, [P, P, FP, ctypes.c_size_t, ctypes.c_uint32, FP]),
     "vr_query_transmittance_grad_device": (ST, [P, P, P, ctypes.c_size_t, ctypes.c_uint32, P, P]),
+    "vr_query_transmittance_ray_grad": (ST, [P, P, ctypes.c_size_t, ctypes.c_uint32, P]),
+    "vr_query_transmittance_ray_grad_device": (ST, [P, P, ctypes.c_size_t, ctypes.c_uint32, P, P]),
     "vr_query_sigma": (ST, [P, FP, ctypes.c_size_t, FP, U32P]),
     "vr_query_sigma_device": (ST, [P, P, ctypes.c_size_t, P, P, P]),
     "vr_query_events_count_device": (ST, [P, P, ctypes.c_size_t, P, ctypes.POINTER(ctypes.c_uint64)]),

@@ -1,14 +1,22 @@
-"""torch.autograd entry point over the mixture queries: the optical depth along known rays, differentiable with respect
-to the Gaussians' parameters (Device.query_transmittance / Device.query_transmittance_grad).
+"""torch.autograd entry point over the mixture queries: the optical depth along rays, differentiable with respect to
+the Gaussians' parameters (Device.query_transmittance / Device.query_transmittance_grad) and with respect to the rays
+themselves (Device.query_transmittance_ray_grad).
 
     tau = optical_depth(mean, cov6, density, albedo, origins, directions)      # (n,), on the rays' device
     loss = ((1 - torch.exp(-tau)) - matte).square().sum()                       # alpha mattes, silhouettes, tomography
     loss.backward()                                                             # mean.grad, cov6.grad, density.grad
+                                                                                # and, where they require grad,
+                                                                                # origins.grad, directions.grad, tmax.grad
 
 Cost: every forward copies the parameters to the host once and builds the scene's tree (Scene.from_gaussians and an
 upload); backward uploads the same scene object, which is a no-op while it is the context's current scene, and runs
-one gradient query with grad_output as the rays' weights. The gradient is exact (closed form, float64 per hit); it is
-not differentiable a second time, and no gradient flows to the rays, tmax or albedo.
+one gradient query with grad_output as the rays' weights. When origins, directions or a tensor tmax requires grad,
+forward runs the ray-gradient query instead of the transmittance query: one walk gives tau (the same bits) and the
+seven columns d tau_i / d (origin_i, direction_i, tmax_i), which forward saves and backward multiplies by grad_output.
+That is the exact Jacobian product, since tau_i depends on ray i only. The directions are normalised by the library,
+so directions.grad is the gradient through v / |v|. Both gradients are exact (closed form, float64 per hit); they are
+not differentiable a second time, and no gradient flows to albedo. When no ray input requires grad, forward and
+backward issue the calls they issue for the Gaussians alone.
 """
 import numpy as np
 import torch
@@ -24,26 +32,49 @@ class _OpticalDepth(torch.autograd.Function):
         scene = Scene.from_gaussians(*host)
         o, d = origins.detach().contiguous(), directions.detach().contiguous()
         tm = tmax.detach() if torch.is_tensor(tmax) else float(tmax)
-        _, tau = dev.query_transmittance(scene, o, d, tm, return_tau=True)
+        ctx.ray_needs = tuple(ctx.needs_input_grad[4:7])
+        ctx.ray_jac = None
+        if any(ctx.ray_needs):
+            g_o, g_d, g_t, tau = dev.query_transmittance_ray_grad(scene, o, d, tm, moving_bounds=bool(moving_bounds))
+            ctx.ray_jac = (g_o, g_d, g_t)
+            tau = tau.contiguous()
+        else:
+            _, tau = dev.query_transmittance(scene, o, d, tm, return_tau=True)
         ctx.dev, ctx.scene, ctx.rays, ctx.moving = dev, scene, (o, d, tm), bool(moving_bounds)
         ctx.like = (mean, cov6, density)
+        ctx.ray_like = tuple((tuple(t.shape), t.dtype) if torch.is_tensor(t) else None for t in (origins, directions, tmax))
         return tau
 
     @staticmethod
     def backward(ctx, grad_tau):
         o, d, tm = ctx.rays
-        g = ctx.dev.query_transmittance_grad(ctx.scene, o, d, grad_tau.to(torch.float32).contiguous(), tm,
-                                             moving_bounds=ctx.moving)
-        mean, cov6, density = ctx.like
-        out = (g[:, 0:3].reshape(mean.shape), g[:, 3:9].reshape(cov6.shape), g[:, 9].reshape(density.shape))
-        out = tuple(x.to(device=p.device, dtype=p.dtype) if need else None
-                    for x, p, need in zip(out, ctx.like, ctx.needs_input_grad[:3]))
-        return out + (None,) * 6
+        out = (None,) * 3
+        if ctx.ray_jac is None or any(ctx.needs_input_grad[:3]):
+            g = ctx.dev.query_transmittance_grad(ctx.scene, o, d, grad_tau.to(torch.float32).contiguous(), tm,
+                                                 moving_bounds=ctx.moving)
+            mean, cov6, density = ctx.like
+            out = (g[:, 0:3].reshape(mean.shape), g[:, 3:9].reshape(cov6.shape), g[:, 9].reshape(density.shape))
+            out = tuple(x.to(device=p.device, dtype=p.dtype) if need else None
+                        for x, p, need in zip(out, ctx.like, ctx.needs_input_grad[:3]))
+        rays = [None, None, None]
+        if ctx.ray_jac is not None:
+            g_o, g_d, g_t = ctx.ray_jac
+            gt = grad_tau.to(torch.float32)
+            if ctx.ray_needs[0]:
+                rays[0] = (g_o * gt[:, None]).to(ctx.ray_like[0][1])
+            if ctx.ray_needs[1]:
+                rays[1] = (g_d * gt[:, None]).to(ctx.ray_like[1][1])
+            if ctx.ray_needs[2]:  # (one tmax for all rays: the sum over the rays)
+                shape, dtype = ctx.ray_like[2]
+                gtm = g_t * gt
+                rays[2] = (gtm if gtm.numel() == int(np.prod(shape)) else gtm.sum()).reshape(shape).to(dtype)
+        return out + (None,) + tuple(rays) + (None, None)
 
 
 def optical_depth(mean, cov6, density, albedo, origins, directions, tmax=float("inf"), device=0, moving_bounds=True):
     """tau (n,) float32 along rays (origins, directions: (n, 3) float32 tensors on cuda:`device`; tmax a number or an
     (n,) tensor there) through the mixture of Gaussians mean (N, 3), cov6 (N, 6) [xx xy xz yy yz zz], density (N,),
-    albedo (N,) (tensors on any device). Differentiable with respect to mean, cov6 and density; the other arguments
-    get None. moving_bounds=False differentiates with each Gaussian's 3-sigma entry / exit distances held fixed."""
+    albedo (N,) (tensors on any device). Differentiable with respect to mean, cov6 and density, and with respect to
+    origins, directions (through the library's normalisation v / |v|) and a tensor tmax; the other arguments get
+    None. moving_bounds=False differentiates with each Gaussian's 3-sigma entry / exit distances held fixed."""
     return _OpticalDepth.apply(mean, cov6, density, albedo, origins, directions, tmax, device, moving_bounds)

@@ -520,7 +520,8 @@ vr_status vr_query_transmittance_device(vr_ctx* ctx, const vr_ray* d_rays, size_
  * tau_i being what vr_query_transmittance returns as tau for ray i (tmax, unit and the validity rule as there), g the
  * SCENE index and theta the vr_gaussian row in its own order: mean[3], cov[6] = {xx, xy, xz, yy, yz, zz}, density. An
  * off-diagonal cov component is the derivative with respect to the stored number, which stands at (i, j) and (j, i):
- * 2 G_Sigma[i][j]. Albedo and emission do not enter tau; gradients with respect to the rays are not computed.
+ * 2 G_Sigma[i][j]. Albedo and emission do not enter tau; the gradient with respect to the rays is
+ * vr_query_transmittance_ray_grad's, below.
  * weight == NULL: every weight is 1. A weight is used as it stands: for a loss over Tr the caller passes dL/dtau =
  * -Tr dL/dTr. Invalid rays contribute nothing, nor do rays with tmax <= 0 or NaN; a Gaussian no ray hits gets ten
  * zeros. Every entry of grad (10 * num_primitives floats) is written; n == 0 zeroes it (VR_OK). Unknown flag bits:
@@ -550,6 +551,40 @@ vr_status vr_query_transmittance_grad(vr_ctx* ctx, const vr_ray* rays, const flo
                                       float* grad);
 vr_status vr_query_transmittance_grad_device(vr_ctx* ctx, const vr_ray* d_rays, const float* d_weight, size_t n,
                                              uint32_t flags, float* d_grad, void* stream);
+
+/* The gradient of the optical depth with respect to the ray (the other half of differentiable transmittance): row i
+ * of out is d tau_i / d (origin, tmax, direction) of ray i and tau_i itself, tau_i being what vr_query_transmittance
+ * returns as tau (tmax, unit and the validity rule as there). flags: 0 or VR_GRAD_FROZEN_BOUNDS, as above; unknown bits:
+ * VR_ERR_INVALID. out == NULL with n > 0: VR_ERR_INVALID; the device form wants both arrays 16-byte aligned; the common
+ * errors above apply (n == 0 is VR_OK and touches nothing).
+ * Per hit, in double, in the notation of vr_query_transmittance_grad (the record's f32 numbers read as doubles, p, d the
+ * direction the walk uses, A, B, C, m, c, k, u, J0, J1, J2, and [a, b] the forward query's f32 clip bounds; a hit
+ * contributes iff b > a, no early-out):
+ *   g_o = -rho norm k M (c J0 + d J1)                      (minus that hit's g_mean: tau sees o and mean through p only)
+ *   g_d = -rho norm k M (m c J0 + (c + m d) J1 + d J2)
+ * Without VR_GRAD_FROZEN_BOUNDS, for each moving bound t (the exit iff t_exit <= tmax, the entry iff t_enter > 0), with
+ * x = p + t d and w = +- rho norm e^{-4.5} / (2 A t + B) (+ exit, - entry): g_o -= 2 w M x, g_d -= 2 w t M x.
+ *   g_tmax = rho norm k e^{-A u_b^2 / 2} iff the upper bound is tmax itself (t_exit > tmax), else 0, with or without the
+ * flag: tmax is the caller's bound, not the ellipsoid's. At t_exit == tmax the ellipsoid's exit is the bound (one-sided:
+ * no tmax term). tmax = +inf gives 0.
+ * The row: the seven sums over the ray's hits are kept in double and rounded to f32 once. `direction` with unit != 0 is
+ * the sum of g_d, the derivative with respect to the three stored components taken as free; with unit == 0 the library
+ * normalised the stored v itself and the row holds the chain through v / |v|, (g_d - d (d.g_d)) / |v|, |v| the square
+ * root (in double) of the f32 squared norm the query computes. `tau` is computed as the transmittance query computes it
+ * (f32 optical_depth per hit, added in double, rounded once) and equals its tau bit for bit: one call gives the value
+ * and its ray Jacobian. An invalid ray (the queries' rule) gets NaN in all eight floats; tmax <= 0 or NaN gives eight
+ * zeros. The hit set and every bound are the forward query's f32 ones and nothing is added atomically, so a result is
+ * reproducible to the rounding of a double sum and does not depend on VR_OPT_HALF_NODES / VR_OPT_DEVICE_BVH beyond that. */
+/* d tau / d ray, one row per ray, laid out as the vr_ray row it differentiates. 32 bytes. */
+typedef struct vr_ray_grad {
+    float origin[3];     /* d tau / d origin */
+    float tmax;          /* d tau / d tmax */
+    float direction[3];  /* d tau / d direction (see `unit`) */
+    float tau;           /* the optical depth itself: vr_query_transmittance's tau for this ray, bit for bit */
+} vr_ray_grad;
+vr_status vr_query_transmittance_ray_grad(vr_ctx* ctx, const vr_ray* rays, size_t n, uint32_t flags, vr_ray_grad* out);
+vr_status vr_query_transmittance_ray_grad_device(vr_ctx* ctx, const vr_ray* d_rays, size_t n, uint32_t flags,
+                                                 vr_ray_grad* d_out, void* stream);
 
 /* GaussianMixtureModel::evaluate_sigma (gmm.h:98-126) at n points xyz[3n], with `active` = the Gaussians
  * whose 3-sigma ellipsoid holds the point (p.(M p) - 9 <= 0 in f32, p = x - mean: the sign of

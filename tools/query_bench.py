@@ -6,10 +6,12 @@ rays packed on the device), every query is warmed up, and the figure is the medi
 events on torch's current stream. Prints one JSON line and, with --out, writes it to a file.
 
     python tools/query_bench.py [--gaussians 1000000] [--rays 4194304] [--points 4194304] [--repeats 5] [--out F]
-                                [--flight-scene FILE] [--only all|mixture|flight|grad]
+                                [--flight-scene FILE] [--only all|mixture|flight|grad|raygrad]
 
 --only grad times the optical-depth gradient query (Device.query_transmittance_grad, unit weights, moving and frozen
 bounds) beside the tau query on the same rays, on --flight-scene and on the make_random scene (--gaussians 0 skips it).
+--only raygrad does the same for the ray gradient (Device.query_transmittance_ray_grad, moving and frozen bounds, and
+with unit=True on the same stored directions).
 """
 import argparse
 import json
@@ -52,7 +54,7 @@ def main():
     ap.add_argument("--seed", type=int, default=2025)
     ap.add_argument("--out", default=None)
     ap.add_argument("--flight-scene", default=os.path.join(ROOT, "tests", "golden", "scenes", "1000_random.txt"))
-    ap.add_argument("--only", choices=("all", "mixture", "flight", "grad"), default="all")
+    ap.add_argument("--only", choices=("all", "mixture", "flight", "grad", "raygrad"), default="all")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -78,6 +80,9 @@ def main():
     if args.only == "grad":
         res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
         res.update(grad(args, dev, o, d, timed))
+    if args.only == "raygrad":
+        res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
+        res.update(raygrad(args, dev, o, d, timed))
     if args.only in ("all", "mixture"):
         res.update(mixture(args, dev, o, d, timed))
     if args.only in ("all", "flight"):
@@ -107,6 +112,30 @@ def grad(args, dev, o, d, timed):
                     "gaussians_hit": int((g[:, 9] != 0).sum()), "mean_tau": float(tau[1].mean()),
                     "all_ms": {"tau": tau_all, "grad": g_all, "grad_frozen": f_all}})
     return {"grad": out, "timing": "median of HIP-event intervals on torch's current stream, inputs on the device"}
+
+
+def raygrad(args, dev, o, d, timed):
+    """The ray-gradient query and the tau query on the same rays, per scene."""
+    import torch
+    scenes = [(os.path.basename(args.flight_scene), vr.Scene.load_GMM(args.flight_scene))]
+    if args.gaussians > 0:
+        big = vr.Scene(vr.Scene.GAUSSIANS)
+        big.add_random_gaussians(args.gaussians, seed=args.seed, variant=0)
+        scenes.append((f"make_random_{args.gaussians}", big))
+    out = []
+    for name, scene in scenes:
+        dev.upload(scene)
+        tau_ms, tau_all, tau = timed(lambda: dev.query_transmittance(scene, o, d, return_tau=True))
+        g_ms, g_all, g = timed(lambda: dev.query_transmittance_ray_grad(scene, o, d))
+        f_ms, f_all, _ = timed(lambda: dev.query_transmittance_ray_grad(scene, o, d, moving_bounds=False))
+        u_ms, u_all, _ = timed(lambda: dev.query_transmittance_ray_grad(scene, o, d, unit=True))
+        out.append({"scene": name, "gaussians": scene.get_num_primitives(), "tau_ms": tau_ms, "raygrad_ms": g_ms,
+                    "raygrad_frozen_ms": f_ms, "raygrad_unit_ms": u_ms, "raygrad_mrays_s": args.rays / g_ms / 1e3,
+                    "raygrad_over_tau": g_ms / tau_ms, "rays_hit": int((g[3] != 0).sum()),
+                    "tau_same_bits": bool((g[3].view(torch.int32) == tau[1].view(torch.int32)).all()),
+                    "mean_tau": float(tau[1].mean()),
+                    "all_ms": {"tau": tau_all, "raygrad": g_all, "raygrad_frozen": f_all, "raygrad_unit": u_all}})
+    return {"raygrad": out, "timing": "median of HIP-event intervals on torch's current stream, inputs on the device"}
 
 
 def flight(args, dev, o, d, timed):

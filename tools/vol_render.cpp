@@ -25,6 +25,8 @@
 // is normalised by Ray's constructor), then n_points rows of 3 floats.
 // --query-grad RAYS.bin (the same file) prints MixtureQuery::transmittance_gradient of the file's rays, all weights 1:
 // one line `tg <scene index> <10 hex words>` per Gaussian (d/d mean[3], cov[6], density).
+// --query-ray-grad RAYS.bin (the same file) prints MixtureQuery::transmittance_ray_gradient of the file's rays: one line
+// `rg <ray index> <8 hex words>` per ray (d/d origin[3], d/d tmax, d/d direction[3], tau).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -105,6 +107,23 @@ static int run_query_grad(const Scene& scene, const std::string& path) {
     return 0;
 }
 
+// --query-ray-grad: the optical depth of the file's rays (their tmax) and its gradient with respect to each ray.
+static int run_query_ray_grad(const Scene& scene, const std::string& path) {
+    std::vector<Ray> rays;
+    std::vector<float> tmax;
+    std::vector<Eigen::Vector3f> pos;
+    read_query_file(path, rays, tmax, pos);
+    const std::vector<vr_ray_grad> g = MixtureQuery(scene).transmittance_ray_gradient(rays, tmax);
+    for (size_t i = 0; i < g.size(); ++i) {
+        const float row[8] = {g[i].origin[0], g[i].origin[1], g[i].origin[2], g[i].tmax,
+                              g[i].direction[0], g[i].direction[1], g[i].direction[2], g[i].tau};
+        std::printf("rg %zu", i);
+        for (int k = 0; k < 8; ++k) std::printf(" %08x", fbits(row[k]));
+        std::printf("\n");
+    }
+    return 0;
+}
+
 static Eigen::Vector3f parse3(const char* s) {
     float a = 0, b = 0, c = 0;
     if (std::sscanf(s, "%f,%f,%f", &a, &b, &c) != 3) throw std::runtime_error(std::string("bad vector: ") + s);
@@ -122,7 +141,7 @@ int main(int argc, char** argv) try {
     int inverse = 0, stoch = 4, final_spp = 0;
     uint64_t seed = 0;
     float lr = 1e-2f;
-    std::string ref_path, sfd_out, gif_path, query_path, query_grad_path;
+    std::string ref_path, sfd_out, gif_path, query_path, query_grad_path, query_ray_grad_path;
     int frames = 120;
     float fps = 30.0f;
     Eigen::Vector3f pos(0, 1, 6), lookat(0, 1, 0);
@@ -149,6 +168,7 @@ int main(int argc, char** argv) try {
         else if (a == "--record") record = true;
         else if (a == "--query") query_path = next();
         else if (a == "--query-grad") query_grad_path = next();
+        else if (a == "--query-ray-grad") query_ray_grad_path = next();
         else if (a == "--gif") gif_path = next();
         else if (a == "--frames") frames = std::atoi(next());
         else if (a == "--fps") fps = std::strtof(next(), nullptr);
@@ -206,6 +226,7 @@ int main(int argc, char** argv) try {
 
     if (!query_path.empty()) return run_queries(scene, query_path);
     if (!query_grad_path.empty()) return run_query_grad(scene, query_grad_path);
+    if (!query_ray_grad_path.empty()) return run_query_ray_grad(scene, query_ray_grad_path);
 
     if (!gif_path.empty()) {  // main.cpp:81-114
         const float radius = 6.0f, height_pos = 1.0f;
