@@ -784,8 +784,10 @@ __device__ __forceinline__ void sec_node4v(const RenderArgs& A, SecRay& R, LdsIn
         next = nearer ? ref[i] : next;
     }
     Q.n = cur - head;
-    // the other inner children -> stack (branch-free while every stepping lane has room for 3)
-    if (__builtin_expect(__ballot(sp > STACK - 3) == 0ull, 1)) {
+    // the other inner children -> stack, branch-free while every stepping lane has room for 4: the loop stores at
+    // the running sp for every slot, so after three pushes the fourth slot's store, kept or not, lands at sp + 3,
+    // and row STACK is the leaf queue's ring slot 0 (with room for 3 only, a queued leaf there was overwritten)
+    if (__builtin_expect(__ballot(sp > STACK - 4) == 0ull, 1)) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             stack[sp * BLOCK] = ref[i];

@@ -56,8 +56,28 @@ def coincident_gaussians(n):
     return _iso(np.tile(np.float32([0.0, 1.0, 0.0]), (n, 1)), np.full(n, 0.2), 0.1, np.full(n, 0.8))
 
 
+def comb_gaussians(mirrored=False):
+    """The stack-limit comb of wide_walk_reference.py (256 Gaussians, 102 of them over one another): every ray of
+    the forward camera below overflows the 32-entry stack of the 4-wide walk, no ray of the backward camera does
+    (test_wide_walk_reference.py asserts both on the reference tree)."""
+    import tree_reference as T
+    import wide_walk_reference as WW
+    return WW.comb_arrays(T.limits()["leaf_max"], mirrored)
+
+
+COMB_FOV = np.float32(2.0 * np.arctan(1.0 / 5.0))  # the pinhole lies 5 in front of the 2 x 2 film
+
+
+def _comb_camera(sign):
+    """A camera whose pinhole is the comb's centre: every ray passes through it, within 16 degrees of +-u."""
+    import wide_walk_reference as WW
+    u = np.array([0.55, 0.6, 0.58])
+    u /= np.linalg.norm(u)
+    return (WW.CENTRE - sign * 5.0 * u).astype(np.float32), (sign * u).astype(np.float32)
+
+
 LIGHT = ((0.0, 4.0, 0.0), (30.0, 30.0, 30.0))
-# name -> (scene file or Gaussian recipe, camera type, fov)
+# name -> (scene file or Gaussian recipe, camera type, fov[, camera position, view direction: the main view's otherwise])
 CASES = {
     "250_random": ("250_random.txt", O.PINHOLE, FOV),
     "1000_random": ("1000_random.txt", O.PINHOLE, FOV),
@@ -65,10 +85,18 @@ CASES = {
     "250_random_ortho": ("250_random.txt", O.ORTHO, 0.0),
     "slab": (slab_gaussians, O.PINHOLE, FOV),
     "coincident200": (lambda: coincident_gaussians(200), O.PINHOLE, np.float32(0.08)),
+    "comb": (comb_gaussians, O.PINHOLE, COMB_FOV, *_comb_camera(1.0)),
+    "comb_back": (comb_gaussians, O.PINHOLE, COMB_FOV, *_comb_camera(-1.0)),
 }
 # scattering rays of the 256 (the oracle's own counts, ANALYTIC_PLUS_NEWTON)
 SCATTERING = {"250_random": 222, "1000_random": 246, "many_gaussians": 44, "250_random_ortho": 256, "slab": 235,
-              "coincident200": 115}
+              "coincident200": 115, "comb": 214, "comb_back": 214}
+
+
+def camera_of(name):
+    """(position, view direction) of the case's camera."""
+    case = CASES[name]
+    return (case[3], case[4]) if len(case) > 3 else (CAM_POS, main_view_dir())
 
 
 @functools.lru_cache(maxsize=None)
@@ -91,7 +119,8 @@ def device_scene(name):
 def record(name, solver=0):
     """(256, 8) f32: the oracle's record under distance solver `solver` (distance_solvers.h:143-187; 0 is the
     reference's ANALYTIC_PLUS_NEWTON), NaN where the first flight escapes."""
-    _, cam, fov = CASES[name]
+    _, cam, fov = CASES[name][:3]
+    pos, view = camera_of(name)
     L = O.lib()
     L.orc_ff_debug.argtypes = [ctypes.POINTER(ctypes.c_float)]
     L.orc_ff_debug.restype = None
@@ -101,7 +130,7 @@ def record(name, solver=0):
     old = L.orc_set_solver(int(solver))
     try:
         L.orc_ff_debug(buf.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
-        O.render_ff(oracle_scene(name), cam, CAM_POS, main_view_dir(), float(fov), W, H, multi=True, num_samples=1)
+        O.render_ff(oracle_scene(name), cam, pos, view, float(fov), W, H, multi=True, num_samples=1)
     finally:
         L.orc_ff_debug(None)
         L.orc_set_solver(old)
@@ -112,9 +141,9 @@ def record(name, solver=0):
 @functools.lru_cache(maxsize=None)
 def rays(name):
     """(origins (256, 3), unit directions (256, 3), targets (256,)) f32 of the case's paths, pixel y * W + x."""
-    _, cam_type, fov = CASES[name]
-    cam = vr.Pinhole_Camera(CAM_POS, main_view_dir(), fov) if cam_type == O.PINHOLE else \
-        vr.Orthographic_Camera(CAM_POS, main_view_dir())
+    _, cam_type, fov = CASES[name][:3]
+    pos, view = camera_of(name)
+    cam = vr.Pinhole_Camera(pos, view, fov) if cam_type == O.PINHOLE else vr.Orthographic_Camera(pos, view)
     f = np.float32
     o, d, tgt = np.zeros((H * W, 3), f), np.zeros((H * W, 3), f), np.zeros(H * W, f)
     for y in range(H):

@@ -44,12 +44,7 @@ def read_back(scene, set_opt, device_bvh, **options):
     return dev.debug_tree(), T.prim_boxes(scene.gaussians()), scene.records()
 
 
-def check_against_reference(tree, pb):
-    """The device builder's order and pair tree are the reference's: stable argsort, unique radix tree."""
-    rt = T.radix_tree(T.morton_keys(pb), tree["info"]["leaf_max"])
-    assert np.array_equal(tree["order"], rt["order"])
-    assert T.same_pair_tree(tree, rt, pb[rt["order"]]) == len(rt["c"])
-    assert tree["info"]["bvh_depth"] == rt["levels"]
+check_against_reference = T.check_against_reference  # (shared with test_gpu_wide_stack.py)
 
 
 # ---- host builder ---------------------------------------------------------------------------------

@@ -561,6 +561,14 @@ def same_pair_tree(tree, rt, sorted_boxes):
     return visited
 
 
+def check_against_reference(tree, pb):
+    """The device builder's order and pair tree are the reference's: stable argsort, unique radix tree."""
+    rt = radix_tree(morton_keys(pb), tree["info"]["leaf_max"])
+    assert np.array_equal(tree["order"], rt["order"])
+    assert same_pair_tree(tree, rt, pb[rt["order"]]) == len(rt["c"])
+    assert tree["info"]["bvh_depth"] == rt["levels"]
+
+
 # ---- the scenes both test files use ----
 def rotated_cov(rng, n, lo=0.02, hi=0.12):
     """(n, 6) anisotropic covariances R diag(s^2) R^T with random rotations, as xx xy xz yy yz zz."""
