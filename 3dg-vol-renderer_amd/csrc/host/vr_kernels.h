@@ -60,6 +60,16 @@ hipError_t query_free_flight(const RenderArgs& A, const vr_ray* rays, const floa
 // the box, over the valid rays that hit the box (0: none does)
 hipError_t ray_extent(const vr_ray* rays, uint32_t n, const float bmin[3], const float bmax[3], uint32_t* out, hipStream_t s);
 
+// kernels/vr_scene_dev.hip: the front of an upload from device arrays (vr_upload_gaussians_device)
+// (rec, boxes (6 n), ext: in scene order; partials: scene_prepare_blocks(n) + 1 entries, the last one the scene's)
+uint32_t scene_prepare_blocks(uint32_t n);
+hipError_t scene_prepare(const float* mean, const float* cov6, const float* density, const float* albedo, uint32_t n, double K,
+                         GaussianRecord* rec, float* boxes, float* ext, SceneStats* partials, hipStream_t s);
+// (out[k]: the central-chord depth of Gaussian k * step along direction k & 3, NaN where the host loop skips it)
+hipError_t scene_chord_samples(const GaussianRecord* rec, uint32_t n, uint32_t step, uint32_t count, double* out, hipStream_t s);
+// (tmp == nullptr: sets tmp_bytes only)
+hipError_t scene_sort_ext(const float* ext, float* sorted, uint32_t n, void* tmp, size_t& tmp_bytes, hipStream_t s);
+
 // kernels/vr_spheres.hip
 hipError_t launch_render(const RenderArgs& A, hipStream_t stream, int volume_type, int integrator, const GridSrc* grid = nullptr);
 hipError_t launch_unshuffle(const float* slabs, uint32_t nslabs, uint32_t tiles_per_slab, uint32_t tiles_x, uint32_t W,

@@ -7,6 +7,7 @@
 #include <bit>
 #include <cmath>
 #include <cstring>
+#include <numbers>
 #include <vector>
 
 #include "vr_ctx.h"
@@ -44,15 +45,21 @@ uint16_t f16_directed(double v, bool up) {  // smallest half >= v (up) / largest
 // scene suits them: f16 keeps ~11 bits, so boxes widen by up to ~1e-3 of the scene's half extent; scenes
 // whose boxes are small against that (median of `ext`, the largest extent of every leaf box, under 3 % of
 // the half extent) keep the f32 nodes only. Reorders `ext`.
-bool half_tree_rule(vr_ctx* c, std::vector<float>& ext) {
+// (half_tree_norm: the normalisation and the half extent it rests on; false: no half trees whatever `ext` holds)
+bool half_tree_norm(vr_ctx* c, double& half) {
     SceneDev& s = c->scene;
-    double half = 0.0;
+    half = 0.0;
     for (int k = 0; k < 3; ++k) {
         s.hn_center[k] = 0.5f * (s.bmin[k] + s.bmax[k]);
         half = std::max(half, 0.5 * ((double)s.bmax[k] - (double)s.bmin[k]));
     }
     if (!c->opt_half_nodes || !(half > 0.0) || !std::isfinite(half)) return false;
     s.hn_scale = (float)(1.0 / half);
+    return true;
+}
+bool half_tree_rule(vr_ctx* c, std::vector<float>& ext) {
+    double half;
+    if (!half_tree_norm(c, half)) return false;
     if (ext.empty()) return true;
     std::nth_element(ext.begin(), ext.begin() + ext.size() / 2, ext.end());
     return ext[ext.size() / 2] >= 0.03 * half;
@@ -181,11 +188,36 @@ vr_status upload_whitened(vr_ctx* c, size_t N) {
     return VR_OK;
 }
 
+// The part both device-builder uploads share, from the point where the records and boxes lie on the device in
+// scene order (either copied up, upload_device_bvh, or computed there, vr_upload_gaussians_device): the build,
+// the hand-over of its buffers to the scene and the whitened records. Frees d_rec and d_boxes.
+vr_status finish_device_bvh(vr_ctx* c, DevBuf<GaussianRecord>& d_rec, DevBuf<float>& d_boxes, size_t N, const float cmin[3],
+                            const float cmax[3], bool use_half) {
+    SceneDev& s = c->scene;
+    LbvhResult R;
+    hipError_t e = lbvh_build(d_rec.get(), d_boxes.get(), (uint32_t)N, cmin, cmax, use_half, s.hn_center, s.hn_scale, c->stream, R);
+    d_rec.reset();
+    d_boxes.reset();
+    if (e == hipErrorNotSupported) return fail(VR_ERR_UNSUPPORTED, "device BVH deeper than the traversal stacks");
+    if (e != hipSuccess) return hip_fail(e, "device BVH build");
+    // every buffer of the build belongs to the scene first (a fresh scene frees them on error)
+    s.gauss.adopt(R.gauss, N);
+    s.order.adopt(R.order, N);
+    s.nodes.adopt(R.nodes, R.num_nodes);
+    s.hnodes.adopt(R.hnodes, R.num_nodes);
+    s.hnodes4.adopt(R.hnodes4, R.num_nodes4);
+    s.num_nodes4 = R.hnodes4 ? R.num_nodes4 : 0;
+    s.num_nodes = R.num_nodes;
+    s.bvh_depth = R.max_depth;
+    c->num_prims = (int32_t)N;
+    s.last_upload_device_bvh = true;
+    return upload_whitened(c, N);
+}
+
 // Device BVH build (kernels/vr_lbvh.hip): records and boxes go up in scene order, the device sorts
 // them by Morton code and emits the child-pair, half-precision and 4-wide trees. VR_ERR_UNSUPPORTED:
 // the tree is deeper than the traversal stacks allow (the caller builds on the host instead).
 vr_status upload_device_bvh(vr_ctx* c, const HostScene& hs, const std::vector<float>& boxes) {
-    SceneDev& s = c->scene;
     const size_t N = hs.pre.size();
     std::vector<GaussianRecord> rec(N);
     float cmin[3] = {INFINITY, INFINITY, INFINITY}, cmax[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -210,24 +242,7 @@ vr_status upload_device_bvh(vr_ctx* c, const HostScene& hs, const std::vector<fl
     VR_TRY(d_boxes.alloc(N * 6, "hipMalloc(boxes)"));
     HIP_TRY(hipMemcpyAsync(d_rec.get(), rec.data(), N * sizeof(GaussianRecord), hipMemcpyHostToDevice, c->stream), "hipMemcpy(records)");
     HIP_TRY(hipMemcpyAsync(d_boxes.get(), boxes.data(), N * 24, hipMemcpyHostToDevice, c->stream), "hipMemcpy(boxes)");
-    LbvhResult R;
-    hipError_t e = lbvh_build(d_rec.get(), d_boxes.get(), (uint32_t)N, cmin, cmax, use_half, s.hn_center, s.hn_scale, c->stream, R);
-    d_rec.reset();
-    d_boxes.reset();
-    if (e == hipErrorNotSupported) return fail(VR_ERR_UNSUPPORTED, "device BVH deeper than the traversal stacks");
-    if (e != hipSuccess) return hip_fail(e, "device BVH build");
-    // every buffer of the build belongs to the scene first (a fresh scene frees them on error)
-    s.gauss.adopt(R.gauss, N);
-    s.order.adopt(R.order, N);
-    s.nodes.adopt(R.nodes, R.num_nodes);
-    s.hnodes.adopt(R.hnodes, R.num_nodes);
-    s.hnodes4.adopt(R.hnodes4, R.num_nodes4);
-    s.num_nodes4 = R.hnodes4 ? R.num_nodes4 : 0;
-    s.num_nodes = R.num_nodes;
-    s.bvh_depth = R.max_depth;
-    c->num_prims = (int32_t)N;
-    s.last_upload_device_bvh = true;
-    return upload_whitened(c, N);
+    return finish_device_bvh(c, d_rec, d_boxes, N, cmin, cmax, use_half);
 }
 
 // The secondary rays' 4-wide tree: the shared tree's nodes refit with the records' tight boxes on the
@@ -348,11 +363,13 @@ int32_t scene_window0(double med, double overlap) {
 #endif
 int32_t scene_nee_refill(double med) { return med >= 50.0 ? VR_NEE_REFILL_OPAQUE : VR_NEE_REFILL_TRANSLUCENT; }
 
-vr_status vr_upload_scene(vr_ctx* c, const vr_scene* sc) {
-    if (!c || !sc) return fail(VR_ERR_INVALID, "vr_upload_scene: NULL argument");
-    if (c->group) return vr::group_upload(c->group, sc);
-    const HostScene& s = sc->s;
-    if (s.lights.size() > (size_t)kMaxLights) return fail(VR_ERR_UNSUPPORTED, "more than 16 lights");
+}  // extern "C"
+
+namespace {
+
+// What every upload begins with: the device is idle, the previous scene's last report is collected, the scene
+// and what hangs on it are reset, and the lights and the environment are the new scene's.
+vr_status begin_upload(vr_ctx* c, int32_t type, const vr_light* lights, size_t n_lights, const float env[3]) {
     HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
     HIP_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
     VR_TRY(collect(c));  // the previous scene's last report, before the reset
@@ -363,16 +380,26 @@ vr_status vr_upload_scene(vr_ctx* c, const vr_scene* sc) {
     c->filter_low = false;
     c->filter_skipped = 0;
     c->nee_inline = false;  // (nee_hint is kept: the inverse loop re-uploads every iteration and renders alike)
-    c->type = s.type;
+    c->type = type;
     c->lights.clear();
-    for (const vr_light& l : s.lights)
+    for (size_t i = 0; i < n_lights; ++i) {
+        const vr_light& l = lights[i];
         c->lights.push_back(LightRecord{l.position[0], l.position[1], l.position[2], l.intensity[0], l.intensity[1], l.intensity[2]});
-    std::memcpy(c->env, s.env, sizeof(c->env));
-    float *bmin = c->scene.bmin, *bmax = c->scene.bmax;
-    for (int k = 0; k < 3; ++k) {
-        bmin[k] = INFINITY;
-        bmax[k] = -INFINITY;
     }
+    std::memcpy(c->env, env, sizeof(c->env));
+    for (int k = 0; k < 3; ++k) {
+        c->scene.bmin[k] = INFINITY;
+        c->scene.bmax[k] = -INFINITY;
+    }
+    return VR_OK;
+}
+
+// vr_upload_scene on one device. try_device: Gaussian scenes of kDeviceBvhMin primitives or more try the device
+// builder first (VR_OPT_DEVICE_BVH).
+vr_status upload_host_scene(vr_ctx* c, const HostScene& s, bool try_device) {
+    if (s.lights.size() > (size_t)kMaxLights) return fail(VR_ERR_UNSUPPORTED, "more than 16 lights");
+    VR_TRY(begin_upload(c, s.type, s.lights.data(), s.lights.size(), s.env));
+    float *bmin = c->scene.bmin, *bmax = c->scene.bmax;
     if (s.type == VR_VOLUME_GAUSSIANS) {
         const size_t N = s.pre.size();
         if (N >= (1u << 27)) return fail(VR_ERR_UNSUPPORTED, "more than 2^27 Gaussians");
@@ -390,7 +417,7 @@ vr_status vr_upload_scene(vr_ctx* c, const vr_scene* sc) {
                 bmax[k] = std::max(bmax[k], boxes[6 * i + 3 + k]);
             }
         }
-        if (c->opt_device_bvh && N >= kDeviceBvhMin) {
+        if (try_device && N >= kDeviceBvhMin) {
             vr_status ds = upload_device_bvh(c, s, boxes);
             if (ds == VR_OK) {
                 if ((ds = upload_parents(c)) != VR_OK) return ds;
@@ -443,6 +470,133 @@ vr_status vr_upload_scene(vr_ctx* c, const vr_scene* sc) {
     VR_TRY(upload_parents(c));
     c->has_scene = true;
     return VR_OK;
+}
+
+// The caller's device arrays as a host scene (vr_scene_add_gaussians of the same floats), through the host path:
+// scenes under kDeviceBvhMin Gaussians, and those whose radix tree is deeper than the stacks.
+vr_status upload_device_arrays_on_host(vr_ctx* c, const float* d_mean, const float* d_cov6, const float* d_density,
+                                       const float* d_albedo, size_t n, const vr_light* lights, size_t n_lights,
+                                       const float env[3]) {
+    HostScene hs;
+    std::vector<float> mean(3 * n), cov(6 * n), density(n), albedo(n);
+    if (n > 0) {
+        HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
+        HIP_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        HIP_TRY(hipMemcpy(mean.data(), d_mean, 12 * n, hipMemcpyDeviceToHost), "hipMemcpy(means D2H)");
+        HIP_TRY(hipMemcpy(cov.data(), d_cov6, 24 * n, hipMemcpyDeviceToHost), "hipMemcpy(covariances D2H)");
+        HIP_TRY(hipMemcpy(density.data(), d_density, 4 * n, hipMemcpyDeviceToHost), "hipMemcpy(densities D2H)");
+        HIP_TRY(hipMemcpy(albedo.data(), d_albedo, 4 * n, hipMemcpyDeviceToHost), "hipMemcpy(albedos D2H)");
+    }
+    hs.gaussians.resize(n);
+    hs.pre.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        vr_gaussian g{};
+        std::memcpy(g.mean, &mean[3 * i], sizeof(g.mean));
+        std::memcpy(g.cov, &cov[6 * i], sizeof(g.cov));
+        g.density = density[i];
+        g.albedo = albedo[i];
+        hs.gaussians[i] = g;
+        hs.pre[i] = precompute_gaussian(g);
+    }
+    hs.lights.assign(lights, lights + n_lights);
+    if (env) std::memcpy(hs.env, env, sizeof(hs.env));
+    return upload_host_scene(c, hs, false);
+}
+
+// The device front of vr_upload_gaussians_device (kernels/vr_scene_dev.hip) and the shared tail. VR_ERR_UNSUPPORTED
+// with nothing of the build in the scene: the radix tree is deeper than the stacks (the caller takes the host path).
+vr_status upload_gaussians_device(vr_ctx* c, const float* d_mean, const float* d_cov6, const float* d_density,
+                                  const float* d_albedo, size_t N, const vr_light* lights, size_t n_lights, const float env[3]) {
+    VR_TRY(begin_upload(c, VR_VOLUME_GAUSSIANS, lights, n_lights, env));
+    SceneDev& s = c->scene;
+    const uint32_t n = (uint32_t)N, nb = scene_prepare_blocks(n);
+    DevBuf<GaussianRecord> d_rec;
+    DevBuf<float> d_boxes;
+    SceneStats st;
+    bool use_half = false;
+    {
+        DevBuf<float> d_ext, d_sorted;
+        DevBuf<SceneStats> d_part;
+        DevBuf<double> d_chord;
+        DevBuf<std::byte> d_tmp;
+        const size_t step = std::max<size_t>(1, N / 4096), count = (N + step - 1) / step;  // scene_median_chord_depth's samples
+        VR_TRY(d_rec.alloc(N, "hipMalloc(records)"));
+        VR_TRY(d_boxes.alloc(N * 6, "hipMalloc(boxes)"));
+        VR_TRY(d_ext.alloc(N, "hipMalloc(box extents)"));
+        VR_TRY(d_part.alloc((size_t)nb + 1, "hipMalloc(scene statistics)"));
+        VR_TRY(d_chord.alloc(count, "hipMalloc(chord depths)"));
+        // gaussian.h:55's first factor, as precompute_gaussian evaluates it (double)
+        const double K = std::pow(2.0f * std::numbers::pi, -1.5f);
+        HIP_TRY(scene_prepare(d_mean, d_cov6, d_density, d_albedo, n, K, d_rec.get(), d_boxes.get(), d_ext.get(), d_part.get(), c->stream),
+                "scene records and boxes");
+        HIP_TRY(scene_chord_samples(d_rec.get(), n, (uint32_t)step, (uint32_t)count, d_chord.get(), c->stream), "chord depths");
+        std::vector<double> tau(count);
+        HIP_TRY(hipMemcpyAsync(&st, d_part.get() + nb, sizeof(st), hipMemcpyDeviceToHost, c->stream), "scene statistics D2H");
+        HIP_TRY(hipMemcpyAsync(tau.data(), d_chord.get(), count * sizeof(double), hipMemcpyDeviceToHost, c->stream), "chord depths D2H");
+        HIP_TRY(hipStreamSynchronize(c->stream), "hipStreamSynchronize(scene statistics)");
+        // the scene heuristics, as vr_upload_scene sets them
+        tau.erase(std::remove_if(tau.begin(), tau.end(), [](double t) { return std::isnan(t); }), tau.end());
+        double med = 0.0;
+        if (!tau.empty()) {
+            std::nth_element(tau.begin(), tau.begin() + tau.size() / 2, tau.end());
+            med = tau[tau.size() / 2];
+        }
+        const double box = (st.ohi[0] - st.olo[0]) * (st.ohi[1] - st.olo[1]) * (st.ohi[2] - st.olo[2]);
+        const double overlap = box > 0.0 && std::isfinite(box) ? st.vol / box : 0.0;
+        c->auto_window0 = scene_window0(med, overlap);
+        c->auto_nee_refill = scene_nee_refill(med);
+        c->auto_ff_sm = N >= 256 && med > 0.0 && med < 16.0;
+        for (int k = 0; k < 3; ++k) {
+            s.bmin[k] = st.bmin[k];
+            s.bmax[k] = st.bmax[k];
+        }
+        // half_tree_rule: the element of rank N / 2 of `ext`, by a full sort of the keys
+        double half;
+        if ((use_half = half_tree_norm(c, half))) {
+            size_t tmp_bytes = 0;
+            float median = 0.0f;
+            HIP_TRY(scene_sort_ext(d_ext.get(), nullptr, n, nullptr, tmp_bytes, c->stream), "box extent sort");
+            VR_TRY(d_sorted.alloc(N, "hipMalloc(sorted box extents)"));
+            VR_TRY(d_tmp.alloc(std::max<size_t>(tmp_bytes, 1), "hipMalloc(sort scratch)"));
+            HIP_TRY(scene_sort_ext(d_ext.get(), d_sorted.get(), n, d_tmp.get(), tmp_bytes, c->stream), "box extent sort");
+            HIP_TRY(hipMemcpyAsync(&median, d_sorted.get() + N / 2, sizeof(float), hipMemcpyDeviceToHost, c->stream), "box extent D2H");
+            HIP_TRY(hipStreamSynchronize(c->stream), "hipStreamSynchronize(box extents)");
+            use_half = median >= 0.03 * half;
+        }
+    }
+    VR_TRY(finish_device_bvh(c, d_rec, d_boxes, N, st.cmin, st.cmax, use_half));
+    VR_TRY(upload_parents(c));
+    c->has_scene = true;
+    return VR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+vr_status vr_upload_scene(vr_ctx* c, const vr_scene* sc) {
+    if (!c || !sc) return fail(VR_ERR_INVALID, "vr_upload_scene: NULL argument");
+    if (c->group) return vr::group_upload(c->group, sc);
+    return upload_host_scene(c, sc->s, c->opt_device_bvh != 0);
+}
+
+vr_status vr_upload_gaussians_device(vr_ctx* c, const float* d_mean, const float* d_cov6, const float* d_density,
+                                     const float* d_albedo, size_t n, const vr_light* lights, size_t n_lights,
+                                     const float env_color[3]) {
+    if (!c) return fail(VR_ERR_INVALID, "vr_upload_gaussians_device: NULL ctx");
+    if (n > 0 && (!d_mean || !d_cov6 || !d_density || !d_albedo)) return fail(VR_ERR_INVALID, "vr_upload_gaussians_device: NULL array");
+    if (n_lights > 0 && !lights) return fail(VR_ERR_INVALID, "vr_upload_gaussians_device: NULL lights");
+    if (c->group) return fail(VR_ERR_UNSUPPORTED, "vr_upload_gaussians_device: a multi-device context (the arrays live on one device)");
+    if (n_lights > (size_t)kMaxLights) return fail(VR_ERR_UNSUPPORTED, "more than 16 lights");
+    if (n >= (1u << 27)) return fail(VR_ERR_UNSUPPORTED, "more than 2^27 Gaussians");
+    const HostScene defaults;
+    const float* env = env_color ? env_color : defaults.env;
+    if (n >= kDeviceBvhMin) {
+        vr_status st = upload_gaussians_device(c, d_mean, d_cov6, d_density, d_albedo, n, lights, n_lights, env);
+        // UNSUPPORTED: too deep for the stacks -> host build, as vr_upload_scene falls back
+        if (st != VR_ERR_UNSUPPORTED) return st;
+    }
+    return upload_device_arrays_on_host(c, d_mean, d_cov6, d_density, d_albedo, n, lights, n_lights, env);
 }
 
 vr_status vr_tree_limits(int32_t* leaf_max, int32_t* max_depth, int32_t* wide_stack_max) {

@@ -23,6 +23,15 @@ struct GaussianRecord {
 };
 static_assert(sizeof(GaussianRecord) == 48, "record must be 48 B");
 
+// What the device front of an upload (kernels/vr_scene_dev.hip) reduces over a scene's Gaussians, per block and
+// folded: the scene box and the centroid box of the primitive boxes (f32, as vr_upload_scene's loops), and
+// scene_overlap's box and ellipsoid-volume sum (double).
+struct SceneStats {
+    double olo[3], ohi[3], vol;
+    float bmin[3], bmax[3], cmin[3], cmax[3];
+};
+static_assert(sizeof(SceneStats) == 104, "scene statistics: 7 doubles, 12 floats");
+
 // Whitened copy of a record for the secondary rays (48 B, same leaf order): M = L^T L with L upper
 // triangular (Cholesky of the inverse covariance, in double), so a ray's quadratic is that of a unit
 // sphere in the coordinates L (x - mean): A = |L d|^2, B/2 = L p . L d, Cq = |L p|^2. dn = density *

@@ -89,6 +89,22 @@ public:
             uploaded[ctx] = {ns, scene.native_version()};
         }
     }
+    // A Gaussian scene straight from device memory (vr_upload_gaussians_device, include/vr_hip.h): d_mean (3 n),
+    // d_cov6 (6 n), d_density (n), d_albedo (n) on the context's GPU, lights and env_color (nullptr: the default) on
+    // the host. The upload cache forgets the context, so it cannot mistake its scene for a host one: the next
+    // render(scene, ...) uploads `scene` again, and render_uploaded() renders what this call put there.
+    static void upload_device(vr_ctx* ctx, const float* d_mean, const float* d_cov6, const float* d_density, const float* d_albedo,
+                              size_t n, const vr_light* lights = nullptr, size_t n_lights = 0, const float* env_color = nullptr) {
+        vr_status st = vr_upload_gaussians_device(ctx, d_mean, d_cov6, d_density, d_albedo, n, lights, n_lights, env_color);
+        forget(ctx);
+        vr_cpp::check(st);
+    }
+    // render() of the scene the context holds (upload_device's), without an upload
+    void render_uploaded(Image& image) {
+        vr_ctx* ctx = context();
+        apply_solver(ctx);
+        vr_cpp::check(vr_render(ctx, &camera->state(), &params_, image.get_width(), image.get_height(), image.data()));
+    }
     void apply_solver(vr_ctx* ctx) const {
         if (solver_ >= 0) vr_cpp::check(vr_set_option(ctx, VR_OPT_FF_SOLVER, solver_));
     }

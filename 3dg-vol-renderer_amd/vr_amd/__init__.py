@@ -23,7 +23,7 @@ __all__ = [
     "VRError", "Light", "Scene", "Camera", "Pinhole_Camera", "Orthographic_Camera", "Ray", "Image",
     "Integrator", "RayMarchingGaussians", "PureRayMarching", "RayMarchingSpheres", "FreeFlightGaussians",
     "MultiScatterGaussians", "bits_to_lists", "TestIntegrator", "Device",
-    "load_xml",
+    "DeviceScene", "load_xml",
     "num_tiles", "RAY_BATCH_WIDTH",
 ]
 
@@ -357,9 +357,23 @@ class Device:
     def upload(self, scene, force=False):
         key = (id(scene), scene.version)
         if force or key != self._scene_key:
-            check(lib().vr_upload_scene(self._h, scene._h))
+            if isinstance(scene, DeviceScene):
+                scene._upload_to(self)
+            else:
+                check(lib().vr_upload_scene(self._h, scene._h))
             self._scene_key = key
             self._scene_ref = scene
+
+    def upload_gaussians(self, mean, cov6, density, albedo, lights=(), env_color=None):
+        """vr_upload_gaussians_device: a Gaussian scene straight from device memory. mean (N, 3), cov6 (N, 6)
+        [xx xy xz yy yz zz], density (N,), albedo (N,): float32 contiguous torch tensors on this context's GPU
+        (ValueError otherwise, before the library is touched). Records, boxes and the tree are computed on the
+        device; nothing is copied to the host (scenes under 256 Gaussians and trees deeper than the stacks take
+        the host path, see include/vr_hip.h). Returns the DeviceScene, which is the context's current scene and
+        stands wherever a scene argument stands."""
+        ds = DeviceScene(mean, cov6, density, albedo, lights, env_color)
+        self.upload(ds, force=True)
+        return ds
 
     def stats(self):
         s = L.vr_render_stats()
@@ -718,6 +732,53 @@ class Device:
         if h is not None and L is not None and L._lib is not None:  # (L is None during interpreter teardown)
             L._lib.vr_destroy(h)
             self._h = None
+
+
+class DeviceScene:
+    """A Gaussian scene whose parameters live in torch tensors on the GPU (Device.upload_gaussians). It stands
+    wherever a `scene` argument stands: a context uploads it from the held tensors (vr_upload_gaussians_device)
+    when another scene displaced it, and not at all while it is the context's current scene. The tensors are
+    held detached, not copied: after changing them in place (an optimiser step), call refresh()."""
+
+    GAUSSIANS = L.VR_VOLUME_GAUSSIANS
+    volume_type = L.VR_VOLUME_GAUSSIANS
+    _h = None  # no host vr_scene stands behind it
+
+    def __init__(self, mean, cov6, density, albedo, lights=(), env_color=None):
+        args = ((mean, "mean", (3,)), (cov6, "cov6", (6,)), (density, "density", ()), (albedo, "albedo", ()))
+        for x, name, tail in args:
+            if not _query_f32(x, name, tail):
+                raise ValueError(f"{name} must be a torch tensor on the context's GPU, not a numpy array")
+        for x, name, _ in args:
+            if x.shape[0] != mean.shape[0]:
+                raise ValueError(f"{name} has {x.shape[0]} rows for {mean.shape[0]} means")
+            if not x.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+        for x, name, _ in args:
+            if x.device.type != "cuda" or x.device != mean.device:
+                raise ValueError(f"{name} is on {x.device}: upload_gaussians takes tensors on the context's GPU")
+        self.mean, self.cov6, self.density, self.albedo = (x.detach() for x in (mean, cov6, density, albedo))
+        self.lights = [Light(l.position, l.intensity) for l in lights]
+        self.env_color = _v3([0.53, 0.81, 0.92] if env_color is None else env_color)  # (scene.h:29's default)
+        self.version = 0
+
+    def get_num_primitives(self):
+        return int(self.mean.shape[0])
+
+    def refresh(self):
+        """The tensors changed in place: the next use uploads them again."""
+        self.version += 1
+
+    def _upload_to(self, dev):
+        dev._check_torch(self.mean)
+        n = len(self.lights)
+        arr = (L.vr_light * max(n, 1))()
+        for i, l in enumerate(self.lights):
+            arr[i].position[:] = [float(v) for v in l.position]
+            arr[i].intensity[:] = [float(v) for v in l.intensity]
+        env = fptr(self.env_color)
+        check(lib().vr_upload_gaussians_device(dev._h, self.mean.data_ptr(), self.cov6.data_ptr(), self.density.data_ptr(),
+                                               self.albedo.data_ptr(), self.get_num_primitives(), arr, n, env))
 
 
 def _is_torch(x):

@@ -158,6 +158,7 @@ SIGNATURES = {
     "vr_get_rank_stats": (ST, [P, ctypes.c_int32, ctypes.POINTER(vr_render_stats)]),
     "vr_destroy": (None, [P]),
     "vr_upload_scene": (ST, [P, P]),
+    "vr_upload_gaussians_device": (ST, [P, P, P, P, P, ctypes.c_size_t, ctypes.POINTER(vr_light), ctypes.c_size_t, FP]),
     "vr_render": (ST, [P, ctypes.POINTER(vr_camera), ctypes.POINTER(vr_render_params), ctypes.c_uint32,
                        ctypes.c_uint32, FP]),
     "vr_render_tiles_device": (ST, [P, ctypes.POINTER(vr_camera), ctypes.POINTER(vr_render_params),

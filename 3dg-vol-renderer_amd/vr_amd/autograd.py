@@ -8,8 +8,13 @@ themselves (Device.query_transmittance_ray_grad).
                                                                                 # and, where they require grad,
                                                                                 # origins.grad, directions.grad, tmax.grad
 
-Cost: every forward copies the parameters to the host once and builds the scene's tree (Scene.from_gaussians and an
-upload); backward uploads the same scene object, which is a no-op while it is the context's current scene, and runs
+Cost: every forward of optical_depth copies the parameters to the host once and builds the scene's tree
+(Scene.from_gaussians and an upload). optical_depth_resident is the same function for parameters that live on the
+rays' device: its forward hands them to Device.upload_gaussians, which computes records, boxes and the tree on the
+device, so nothing is copied to the host and nothing runs per Gaussian on a host thread; it saves the DeviceScene.
+tau has the bits of optical_depth's wherever the records' norm words agree (include/vr_hip.h,
+vr_upload_gaussians_device: at most 2 ulp apart, on well under 1 % of Gaussians). Either way backward uploads the
+saved scene object, which is a no-op while it is the context's current scene, and runs
 one gradient query with grad_output as the rays' weights. When origins, directions or a tensor tmax requires grad,
 forward runs the ray-gradient query instead of the transmittance query: one walk gives tau (the same bits) and the
 seven columns d tau_i / d (origin_i, direction_i, tmax_i), which forward saves and backward multiplies by grad_output.
@@ -26,10 +31,18 @@ from . import Device, Scene
 
 class _OpticalDepth(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mean, cov6, density, albedo, origins, directions, tmax, device, moving_bounds):
+    def forward(ctx, mean, cov6, density, albedo, origins, directions, tmax, device, moving_bounds, resident=False):
+        if resident:
+            for t, name in ((mean, "mean"), (cov6, "cov6"), (density, "density"), (albedo, "albedo")):
+                if t.device != origins.device:
+                    raise ValueError(f"{name} is on {t.device}, the rays on {origins.device}: a resident scene's "
+                                     "parameters live on the rays' device")
         dev = Device.get(device)
-        host = [t.detach().to("cpu", torch.float32).contiguous().numpy() for t in (mean, cov6, density, albedo)]
-        scene = Scene.from_gaussians(*host)
+        if resident:
+            scene = dev.upload_gaussians(*(t.detach().to(torch.float32).contiguous() for t in (mean, cov6, density, albedo)))
+        else:
+            host = [t.detach().to("cpu", torch.float32).contiguous().numpy() for t in (mean, cov6, density, albedo)]
+            scene = Scene.from_gaussians(*host)
         o, d = origins.detach().contiguous(), directions.detach().contiguous()
         tm = tmax.detach() if torch.is_tensor(tmax) else float(tmax)
         ctx.ray_needs = tuple(ctx.needs_input_grad[4:7])
@@ -68,7 +81,7 @@ class _OpticalDepth(torch.autograd.Function):
                 shape, dtype = ctx.ray_like[2]
                 gtm = g_t * gt
                 rays[2] = (gtm if gtm.numel() == int(np.prod(shape)) else gtm.sum()).reshape(shape).to(dtype)
-        return out + (None,) + tuple(rays) + (None, None)
+        return out + (None,) + tuple(rays) + (None, None, None)
 
 
 def optical_depth(mean, cov6, density, albedo, origins, directions, tmax=float("inf"), device=0, moving_bounds=True):
@@ -77,4 +90,11 @@ def optical_depth(mean, cov6, density, albedo, origins, directions, tmax=float("
     albedo (N,) (tensors on any device). Differentiable with respect to mean, cov6 and density, and with respect to
     origins, directions (through the library's normalisation v / |v|) and a tensor tmax; the other arguments get
     None. moving_bounds=False differentiates with each Gaussian's 3-sigma entry / exit distances held fixed."""
-    return _OpticalDepth.apply(mean, cov6, density, albedo, origins, directions, tmax, device, moving_bounds)
+    return _OpticalDepth.apply(mean, cov6, density, albedo, origins, directions, tmax, device, moving_bounds, False)
+
+
+def optical_depth_resident(mean, cov6, density, albedo, origins, directions, tmax=float("inf"), device=0, moving_bounds=True):
+    """optical_depth for parameters that never leave the GPU: mean, cov6, density and albedo must be on the rays'
+    device (ValueError otherwise), and forward uploads them with Device.upload_gaussians instead of copying them to
+    the host. Same arguments, same gradients."""
+    return _OpticalDepth.apply(mean, cov6, density, albedo, origins, directions, tmax, device, moving_bounds, True)

@@ -229,6 +229,34 @@ vr_status vr_get_rank_stats(vr_ctx* ctx, int32_t rank, vr_render_stats* out);
 void vr_destroy(vr_ctx* ctx);
 /* Prepare (BVH build) and upload the scene; replaces any previous one. Host copies are not kept. */
 vr_status vr_upload_scene(vr_ctx* ctx, const vr_scene* s);
+/* A Gaussian scene straight from device memory: d_mean (3 n), d_cov6 (6 n: xx xy xz yy yz zz), d_density (n) and
+ * d_albedo (n) are float arrays on the context's GPU (an optimiser's parameters, say); lights (n_lights of them)
+ * and env_color (NULL: scene.h:29's default) are host memory. Records, boxes and scene statistics are computed on
+ * the device and handed to the device BVH builder: nothing goes through the host. The context ends up in the state
+ * vr_upload_scene leaves it in under VR_OPT_DEVICE_BVH = 1 for a vr_scene built by vr_scene_add_gaussians from the
+ * same floats, lights and environment (emission is not taken: nothing reads it): every record word, every box and
+ * so the scene bounds, the half-tree decision and every tree array are that upload's bit for bit, with one
+ * deviation, the records' `norm`. The host computes (float)(K * (double)powf(det, -0.5f)), K = (2 pi)^-1.5 in
+ * double, and libm's powf is not reproducible on the device; this call computes
+ *     (float)(K * (double)(float)(1.0 / sqrt((double)det)))
+ * with the same f32 determinant det and the host's K: IEEE operations only, so it can be restated exactly
+ * anywhere. Both inverse square roots are faithful (within one ulp of each other) and the product is rounded once
+ * more: the two norms differ by at most 2 f32 ulp (against glibc's powf on 0.06-0.07 % of seeded covariances).
+ * Synchronous: it begins with the device synchronise vr_upload_scene begins with, so arrays written on any
+ * stream are complete, and on return the scene is current and the caller may overwrite its arrays (nothing of
+ * them is kept). It replaces the previous scene, collects its last report and resets what vr_upload_scene resets;
+ * on a failure after the arguments were accepted the context holds no scene. VR_OPT_HALF_NODES and VR_OPT_SEC_TIGHT apply as at any upload;
+ * VR_OPT_DEVICE_BVH is not consulted. Two cases copy the arrays to the host and take vr_upload_scene's host path
+ * (such a scene is the host upload's in every bit, norm included; vr_tree_info.built_on_device tells): fewer than
+ * 256 Gaussians (n = 0 included), and a radix tree deeper than the traversal stacks, as vr_upload_scene falls
+ * back. The scene heuristics (first window, shadow-ray refill, free-flight kernel choice) are the host's; the
+ * overlap estimate is a double sum reduced in a fixed order, so it is the same on every run but may differ from
+ * the host loop's in its last bits (it feeds a threshold only; results do not depend on it).
+ * VR_ERR_INVALID: NULL ctx, a NULL array with n > 0, NULL lights with n_lights > 0. VR_ERR_UNSUPPORTED: more than
+ * 16 lights, n >= 2^27, or a vr_init_multi context (the arrays live on one device). */
+vr_status vr_upload_gaussians_device(vr_ctx* ctx, const float* d_mean, const float* d_cov6, const float* d_density,
+                                     const float* d_albedo, size_t n, const vr_light* lights, size_t n_lights,
+                                     const float env_color[3]);
 /* Integrator::render(scene, image): full W x H frame into rgb_host (3*W*H floats, row-major,
  * idx = 3*(y*W + x) as image.h:13-17). Synchronous. */
 vr_status vr_render(vr_ctx* ctx, const vr_camera* cam, const vr_render_params* p, uint32_t width,

@@ -6,12 +6,18 @@ rays packed on the device), every query is warmed up, and the figure is the medi
 events on torch's current stream. Prints one JSON line and, with --out, writes it to a file.
 
     python tools/query_bench.py [--gaussians 1000000] [--rays 4194304] [--points 4194304] [--repeats 5] [--out F]
-                                [--flight-scene FILE] [--only all|mixture|flight|grad|raygrad]
+                                [--flight-scene FILE] [--only all|mixture|flight|grad|raygrad|upload]
 
 --only grad times the optical-depth gradient query (Device.query_transmittance_grad, unit weights, moving and frozen
 bounds) beside the tau query on the same rays, on --flight-scene and on the make_random scene (--gaussians 0 skips it).
 --only raygrad does the same for the ray gradient (Device.query_transmittance_ray_grad, moving and frozen bounds, and
 with unit=True on the same stored directions).
+--only upload times getting a scene whose parameters live in torch tensors on the GPU onto the device, on --flight-scene
+and on make_random scenes of 100 000 and --gaussians Gaussians: (a) a copy to the host, Scene.from_gaussians and
+Device.upload with the host builder, (b) the same with device_bvh = 1, (c) Device.upload_gaussians. A host clock
+around each call (every one ends in a synchronise), one warm-up, the median of --repeats; (b) and (c) alternate in
+one process. Then autograd's optical depth, forward plus backward on 2^20 of the rays at --gaussians Gaussians, with
+the parameters copied to the host (optical_depth) and resident (optical_depth_resident).
 """
 import argparse
 import json
@@ -54,7 +60,7 @@ def main():
     ap.add_argument("--seed", type=int, default=2025)
     ap.add_argument("--out", default=None)
     ap.add_argument("--flight-scene", default=os.path.join(ROOT, "tests", "golden", "scenes", "1000_random.txt"))
-    ap.add_argument("--only", choices=("all", "mixture", "flight", "grad", "raygrad"), default="all")
+    ap.add_argument("--only", choices=("all", "mixture", "flight", "grad", "raygrad", "upload"), default="all")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -83,6 +89,9 @@ def main():
     if args.only == "raygrad":
         res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
         res.update(raygrad(args, dev, o, d, timed))
+    if args.only == "upload":
+        res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
+        res.update(upload(args, dev, o, d))
     if args.only in ("all", "mixture"):
         res.update(mixture(args, dev, o, d, timed))
     if args.only in ("all", "flight"):
@@ -112,6 +121,68 @@ def grad(args, dev, o, d, timed):
                     "gaussians_hit": int((g[:, 9] != 0).sum()), "mean_tau": float(tau[1].mean()),
                     "all_ms": {"tau": tau_all, "grad": g_all, "grad_frozen": f_all}})
     return {"grad": out, "timing": "median of HIP-event intervals on torch's current stream, inputs on the device"}
+
+
+def upload(args, dev, o, d):
+    """Three ways of getting device-resident parameters onto the device as a scene, and what they cost autograd."""
+    import time
+
+    import torch
+    from vr_amd import autograd
+
+    def clock(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def params(scene):
+        g = scene.gaussians()
+        return [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (g[:, 0:3], g[:, 3:9], g[:, 9], g[:, 10])]
+
+    def from_host(p, device_bvh):
+        dev.set_option("device_bvh", device_bvh)
+        dev.upload(vr.Scene.from_gaussians(*(t.cpu().numpy() for t in p)), force=True)
+
+    scenes = [(os.path.basename(args.flight_scene), vr.Scene.load_GMM(args.flight_scene))]
+    for n in sorted({min(100_000, args.gaussians), args.gaussians} - {0}):
+        big = vr.Scene(vr.Scene.GAUSSIANS)
+        big.add_random_gaussians(n, seed=args.seed, variant=0)
+        scenes.append((f"make_random_{n}", big))
+    saved = dev.get_option("device_bvh")
+    out = []
+    for name, scene in scenes:
+        p = params(scene)
+        a = [clock(lambda: from_host(p, 0)) for _ in range(args.warmup + args.repeats)][args.warmup:]
+        b, c = [], []
+        for _ in range(args.warmup + args.repeats):  # alternated: they share the session
+            b.append(clock(lambda: from_host(p, 1)))
+            c.append(clock(lambda: dev.upload_gaussians(*p)))
+        b, c = b[args.warmup:], c[args.warmup:]
+        out.append({"scene": name, "gaussians": scene.get_num_primitives(), "host_builder_ms": statistics.median(a),
+                    "device_bvh_ms": statistics.median(b), "upload_gaussians_ms": statistics.median(c),
+                    "device_bvh_spread_ms": max(b) - min(b), "built_on_device": bool(dev.debug_tree([])["info"]["built_on_device"]),
+                    "all_ms": {"host_builder": a, "device_bvh": b, "upload_gaussians": c}})
+    dev.set_option("device_bvh", saved)
+    res = {"upload": out, "timing": "host clock around each call (each ends in a synchronise), median after one warm-up"}
+    if args.gaussians > 0:
+        p = params(scenes[-1][1])
+        n = min(1 << 20, o.shape[0])
+        ro, rd = o[:n].contiguous(), d[:n].contiguous()
+
+        def step(fn):
+            q = [t.clone().requires_grad_() for t in p[:3]]
+            fn(*q, p[3], ro, rd).sum().backward()
+
+        fb = {}
+        for key, fn in (("optical_depth", autograd.optical_depth), ("optical_depth_resident", autograd.optical_depth_resident)):
+            ms = [clock(lambda: step(fn)) for _ in range(args.warmup + args.repeats)][args.warmup:]
+            fb[key + "_ms"] = statistics.median(ms)
+            fb.setdefault("all_ms", {})[key] = ms
+        fb.update({"rays": n, "gaussians": scenes[-1][1].get_num_primitives()})
+        res["forward_backward"] = fb
+    return res
 
 
 def raygrad(args, dev, o, d, timed):

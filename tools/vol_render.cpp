@@ -27,6 +27,9 @@
 // one line `tg <scene index> <10 hex words>` per Gaussian (d/d mean[3], cov[6], density).
 // --query-ray-grad RAYS.bin (the same file) prints MixtureQuery::transmittance_ray_gradient of the file's rays: one line
 // `rg <ray index> <8 hex words>` per ray (d/d origin[3], d/d tmax, d/d direction[3], tau).
+// --upload-device (Gaussian scenes, one GPU): copies the loaded scene's rows to device memory and uploads them with
+// HipIntegrator::upload_device (vr_upload_gaussians_device: records, boxes and tree computed on the device), then
+// renders the scene the context holds.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -36,6 +39,8 @@
 #include <numbers>
 #include <string>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "vr/integrator.h"
 #include "vr/query.h"
@@ -124,6 +129,43 @@ static int run_query_ray_grad(const Scene& scene, const std::string& path) {
     return 0;
 }
 
+// --upload-device: the scene's rows as four device arrays, uploaded from there.
+static void upload_from_device_memory(vr_ctx* ctx, const Scene& scene) {
+    if (scene.volume_type != Scene::VolumeType::GAUSSIANS) throw std::runtime_error("--upload-device needs a Gaussian scene");
+    std::vector<float> host[4];  // mean, cov6, density, albedo
+    if (scene.gmm && !scene.gmm->empty())
+        for (const Gaussian& x : (*scene.gmm)[0].gaussians) {
+            const vr_gaussian g = x.to_record();
+            host[0].insert(host[0].end(), g.mean, g.mean + 3);
+            host[1].insert(host[1].end(), g.cov, g.cov + 6);
+            host[2].push_back(g.density);
+            host[3].push_back(g.albedo);
+        }
+    const size_t n = host[2].size();
+    float* dev[4] = {nullptr, nullptr, nullptr, nullptr};
+    auto release = [&] {
+        for (float* p : dev)
+            if (p) (void)hipFree(p);
+    };
+    for (int k = 0; k < 4 && n > 0; ++k)
+        if (hipMalloc((void**)&dev[k], host[k].size() * sizeof(float)) != hipSuccess ||
+            hipMemcpy(dev[k], host[k].data(), host[k].size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+            release();
+            throw std::runtime_error("--upload-device: could not copy the scene to the device");
+        }
+    std::vector<vr_light> ls;
+    for (const Light& l : scene.lights)
+        ls.push_back(vr_light{{l.position[0], l.position[1], l.position[2]}, {l.intensity[0], l.intensity[1], l.intensity[2]}});
+    const float env[3] = {scene.env_color[0], scene.env_color[1], scene.env_color[2]};
+    try {
+        HipIntegrator::upload_device(ctx, dev[0], dev[1], dev[2], dev[3], n, ls.data(), ls.size(), env);
+    } catch (...) {
+        release();
+        throw;
+    }
+    release();
+}
+
 static Eigen::Vector3f parse3(const char* s) {
     float a = 0, b = 0, c = 0;
     if (std::sscanf(s, "%f,%f,%f", &a, &b, &c) != 3) throw std::runtime_error(std::string("bad vector: ") + s);
@@ -137,7 +179,7 @@ int main(int argc, char** argv) try {
     float step = 0.01f, fov = 0.25f * std::numbers::pi_v<float>;
     int env = -1, dump = 0, spp = -1;
     std::vector<int> devices;
-    bool record = false;
+    bool record = false, upload_device = false;
     int inverse = 0, stoch = 4, final_spp = 0;
     uint64_t seed = 0;
     float lr = 1e-2f;
@@ -166,6 +208,7 @@ int main(int argc, char** argv) try {
         else if (a == "--out") out = next();
         else if (a == "--dump-rays") dump = std::atoi(next());
         else if (a == "--record") record = true;
+        else if (a == "--upload-device") upload_device = true;
         else if (a == "--query") query_path = next();
         else if (a == "--query-grad") query_grad_path = next();
         else if (a == "--query-ray-grad") query_ray_grad_path = next();
@@ -288,6 +331,9 @@ int main(int argc, char** argv) try {
         size_t pairs = 0;
         for (const auto& l : per_pixel) pairs += l.size();
         std::printf("recorded pairs %zu\n", pairs);
+    } else if (upload_device) {
+        upload_from_device_memory(integrator->context(), scene);
+        integrator->render_uploaded(image);
     } else {
         integrator->render(scene, image);
     }
