@@ -133,6 +133,8 @@ struct vr_ctx {
     vr::DevBuf<std::byte> q_tmp;                // scan + sort scratch
     vr::DevBuf<std::byte> q_ctl;      // words [0..3], [6] ray counters of the five persistent walks, [4..5] the 64-bit event total
     vr::DevBuf<double> q_grad;        // gradient query: 10 doubles of staging per Gaussian (tree order), zeroed per call
+    vr::DevBuf<double> q_sgrad;       // sigma gradient query: 11 doubles of staging per Gaussian, its own (the two
+                                      // gradient queries may be queued on different streams)
     // free-flight query (kernels/vr_query_flight.hip): its own scratch rows (the layouts of ff_scratch and of
     // ff_fb's rows), so a frame queued on another stream never shares them; counters + queue of rays over the rows
     vr::DevBuf<std::byte> q_ff_rows, q_ff_big;

@@ -47,6 +47,10 @@ hipError_t query_transmittance_grad(const RenderArgs& A, const vr_ray* rays, con
 // (out: one vr_ray_grad row per ray)
 hipError_t query_transmittance_ray_grad(const RenderArgs& A, const vr_ray* rays, uint32_t n, bool moving, vr_ray_grad* out,
                                         uint32_t* next, int refill, int cus, hipStream_t s);
+// (stage: 11 doubles per Gaussian of staging, zeroed by the call; grad: 11 floats per Gaussian; grad_xyz: 3 floats per
+// point; either output may be nullptr, and without grad the staging is not touched)
+hipError_t query_sigma_grad(const RenderArgs& A, const float* xyz, const float* weight_as, uint32_t n, double* stage, float* grad,
+                            float* grad_xyz, hipStream_t s);
 hipError_t query_pack_rays(const float* o, const float* d, const float* tmax, uint32_t tmax_stride, uint32_t n, vr_ray* rays,
                            hipStream_t s);
 

@@ -1,5 +1,5 @@
 // Mixture queries (vr_query_*, kernels/vr_query.hip, kernels/vr_query_flight.hip): batched transmittance and its
-// gradients with respect to the Gaussians and to the rays, ray events, sigma and free-flight distances.
+// gradients with respect to the Gaussians and to the rays, ray events, sigma and its gradient, and free-flight distances.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -170,6 +170,54 @@ vr_status vr_query_sigma(vr_ctx* c, const float* xyz, size_t n, float* sigma_as,
     HIP_TRY(hipStreamSynchronize(c->stream), "query_sigma_kernel");
     HIP_TRY(hipMemcpy(sigma_as, c->q_out.get(), n * 2 * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
     if (n_active) HIP_TRY(hipMemcpy(n_active, c->q_out2.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    return VR_OK;
+}
+
+vr_status vr_query_sigma_grad_device(vr_ctx* c, const float* d_xyz, const float* d_weight_as, size_t n, float* d_grad,
+                                     float* d_grad_xyz, void* stream) {
+    c = first_device(c);
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_sigma_grad", n, A));
+    const size_t words = (size_t)std::max(A.num_prims, 0) * 11;
+    if (n == 0) {
+        if (d_grad && words) HIP_TRY(hipMemsetAsync(d_grad, 0, words * sizeof(float), (hipStream_t)stream), "hipMemset(sigma gradient)");
+        return VR_OK;
+    }
+    if (!d_xyz) return fail(VR_ERR_INVALID, "vr_query_sigma_grad: NULL argument");
+    if (!d_grad && !d_grad_xyz) return fail(VR_ERR_INVALID, "vr_query_sigma_grad: both outputs are NULL");
+    // the staging rows are the query's own: a frame or another gradient query queued on another stream never sees them
+    if (d_grad) VR_TRY(c->q_sgrad.grow(std::max<size_t>(words, 11), "hipMalloc(gradient staging)"));
+    HIP_TRY(query_sigma_grad(A, d_xyz, d_weight_as, (uint32_t)n, d_grad ? c->q_sgrad.get() : nullptr, d_grad, d_grad_xyz,
+                             (hipStream_t)stream),
+            "query_sigma_grad_kernel");
+    return VR_OK;
+}
+
+vr_status vr_query_sigma_grad(vr_ctx* c, const float* xyz, const float* weight_as, size_t n, float* grad, float* grad_xyz) {
+    c = first_device(c);
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_sigma_grad", n, A));
+    const size_t words = (size_t)std::max(A.num_prims, 0) * 11;
+    if (n == 0) {
+        if (grad) std::memset(grad, 0, words * sizeof(float));
+        return VR_OK;
+    }
+    if (!xyz) return fail(VR_ERR_INVALID, "vr_query_sigma_grad: NULL argument");
+    if (!grad && !grad_xyz) return fail(VR_ERR_INVALID, "vr_query_sigma_grad: both outputs are NULL");
+    const bool gauss = grad && words > 0;
+    VR_TRY(c->q_in.grow(n * 3 * sizeof(float), "hipMalloc(query points)"));
+    if (weight_as) VR_TRY(c->q_tau.grow(n * 2, "hipMalloc(query weights)"));
+    if (gauss) VR_TRY(c->q_out.grow(words, "hipMalloc(query results)"));
+    if (grad_xyz) VR_TRY(c->q_out2.grow(n * 3 * sizeof(float), "hipMalloc(query results)"));
+    HIP_TRY(hipMemcpy(c->q_in.get(), xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(query points)");
+    if (weight_as) HIP_TRY(hipMemcpy(c->q_tau.get(), weight_as, n * 2 * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(query weights)");
+    if (gauss || grad_xyz) {
+        VR_TRY(vr_query_sigma_grad_device(c, (const float*)c->q_in.get(), weight_as ? c->q_tau.get() : nullptr, n,
+                                          gauss ? c->q_out.get() : nullptr, grad_xyz ? (float*)c->q_out2.get() : nullptr, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream), "query_sigma_grad_kernel");
+    }
+    if (gauss) HIP_TRY(hipMemcpy(grad, c->q_out.get(), words * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    if (grad_xyz) HIP_TRY(hipMemcpy(grad_xyz, c->q_out2.get(), n * 3 * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
     return VR_OK;
 }
 

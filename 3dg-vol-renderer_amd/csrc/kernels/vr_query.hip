@@ -6,7 +6,10 @@
 //                                                            holding pos, the set the integrators pass)
 // and, for the first of them, the gradient of its optical depth with respect to the Gaussians
 // (query_grad_kernel / query_grad_finish_kernel: f32 decisions, double arithmetic per hit, double atomic adds)
-// and with respect to the ray (query_ray_grad_kernel: the same per-hit arithmetic, summed per ray in registers).
+// and with respect to the ray (query_ray_grad_kernel: the same per-hit arithmetic, summed per ray in registers);
+// for the last, the gradient of sigma with respect to the Gaussians (albedo included) and to the points
+// (query_sigma_grad_kernel / query_sigma_grad_points_kernel / query_sigma_grad_finish_kernel: the forward's walk and
+// f32 decision, double per active Gaussian, double atomic adds per Gaussian, register sums per point).
 //
 // Floating point: a query is an API for fidelity, so every Gaussian is tested with the exact forms of
 // vr_march.h (quad / intersect / optical_depth / mu_t: the reference's evaluation order, correctly rounded
@@ -497,6 +500,16 @@ __global__ void __launch_bounds__(256) query_events_unpack_kernel(const unsigned
 // in its box: the leaf boxes are the 3-sigma boxes grown by 5 % (gaussian_bounds), and the f16 boxes of the
 // 4-wide tree are rounded outward from them (f16_directed, host and device builders), so every ellipsoid
 // holding x is reached. Sums in double (see the head of this file).
+// The decision itself: the forward query's and the gradient query's, so their active sets are the same bit for bit.
+__device__ __forceinline__ bool sigma_active(const GRec& g, float x, float y, float z) {
+    const float px = x - g.mx, py = y - g.my, pz = z - g.mz;
+    const float mpx = g.m00 * px + (g.m01 * py + g.m02 * pz);
+    const float mpy = g.m01 * px + (g.m11 * py + g.m12 * pz);
+    const float mpz = g.m02 * px + (g.m12 * py + g.m22 * pz);
+    const float C = dot3(px, py, pz, mpx, mpy, mpz) - 9.0f;
+    return C <= 0.0f;
+}
+
 struct SigmaAcc {
     double sum, sum_alb;
     uint32_t cnt;
@@ -508,12 +521,7 @@ struct SigmaAcc {
         const uint32_t first = leaf_first(ref), end = first + leaf_count(ref);
         for (uint32_t j = first; j < end; ++j) {
             const GRec g = load_rec(A.gauss, (int)j);
-            const float px = x - g.mx, py = y - g.my, pz = z - g.mz;
-            const float mpx = g.m00 * px + (g.m01 * py + g.m02 * pz);
-            const float mpy = g.m01 * px + (g.m11 * py + g.m12 * pz);
-            const float mpz = g.m02 * px + (g.m12 * py + g.m22 * pz);
-            const float C = dot3(px, py, pz, mpx, mpy, mpz) - 9.0f;
-            if (C <= 0.0f) {
+            if (sigma_active(g, x, y, z)) {
                 const float m = mu_t(g, x, y, z);
                 sum += (double)m;
                 sum_alb += (double)(m * g.albedo);
@@ -522,6 +530,144 @@ struct SigmaAcc {
         }
     }
 };
+
+// The gradient of sigma at the point (include/vr_hip.h, vr_query_sigma_grad, has the formulas): on every active
+// Gaussian (sigma_active, f32) the record and the point are read as doubles, p = x - mean, q = p.Mp,
+// e = norm exp(-q / 2), m = rho e, c = w_a (1 - alpha) + w_s alpha.
+//   GAUSS:  eleven atomic adds into the staging row acc[11 j .. 11 j + 10] of record j (tree order): g_mean = c m M p,
+//           G_M {00, 01, 02, 11, 12, 22} = -c m p p^T / 2, U = c e and g_albedo = (w_s - w_a) m, each times `sg`
+//           (global_atomic_add_f64, arrival order, as GradOp::add). sg = -1 takes a walk's adds back: the walk
+//           hands the same Gaussians out again, see query_sigma_grad_kernel.
+//   POINTS: g_x = -c m M p summed in registers.
+// `mass` is the double sum of m (the point contributes iff it is > 0), cnt the Gaussians added.
+// The points-only instantiation has no staging pointer to carry and no atomics.
+template <bool GAUSS>
+struct SigmaGradStage {};
+template <>
+struct SigmaGradStage<true> {
+    double* acc;
+    double sg;
+};
+template <bool POINTS>
+struct SigmaGradSum {};
+template <>
+struct SigmaGradSum<true> {
+    double gx, gy, gz;
+};
+template <bool GAUSS, bool POINTS>
+struct SigmaGradAcc : SigmaGradStage<GAUSS>, SigmaGradSum<POINTS> {
+    double wa, ws, mass;
+    uint32_t cnt;
+    __device__ __forceinline__ void reset() {
+        this->mass = 0.0;
+        this->cnt = 0;
+        if constexpr (POINTS) this->gx = this->gy = this->gz = 0.0;
+    }
+    __device__ __forceinline__ void leaf(const RenderArgs& A, int32_t ref, float x, float y, float z) {
+        const uint32_t first = leaf_first(ref), end = first + leaf_count(ref);
+        for (uint32_t j = first; j < end; ++j) {
+            const GRec g = load_rec(A.gauss, (int)j);
+            if (!sigma_active(g, x, y, z)) continue;
+            const double px = (double)x - (double)g.mx, py = (double)y - (double)g.my, pz = (double)z - (double)g.mz;
+            const double m00 = g.m00, m01 = g.m01, m02 = g.m02, m11 = g.m11, m12 = g.m12, m22 = g.m22;
+            const double mpx = m00 * px + m01 * py + m02 * pz, mpy = m01 * px + m11 * py + m12 * pz,
+                         mpz = m02 * px + m12 * py + m22 * pz;
+            const double q = px * mpx + py * mpy + pz * mpz;
+            const double e = (double)g.norm * exp(-0.5 * q), m = (double)g.density * e;
+            const double alpha = g.albedo;
+            const double c = this->wa * (1.0 - alpha) + this->ws * alpha, cm = c * m;
+            this->mass += m;
+            ++this->cnt;
+            if constexpr (POINTS) {
+                this->gx -= cm * mpx;
+                this->gy -= cm * mpy;
+                this->gz -= cm * mpz;
+            }
+            if constexpr (GAUSS) {
+                const double s = this->sg * cm, h = -0.5 * s;
+                double* row = this->acc + 11 * (size_t)j;
+                atomicAdd(row + 0, s * mpx);
+                atomicAdd(row + 1, s * mpy);
+                atomicAdd(row + 2, s * mpz);
+                atomicAdd(row + 3, h * px * px);
+                atomicAdd(row + 4, h * px * py);
+                atomicAdd(row + 5, h * px * pz);
+                atomicAdd(row + 6, h * py * py);
+                atomicAdd(row + 7, h * py * pz);
+                atomicAdd(row + 8, h * pz * pz);
+                atomicAdd(row + 9, this->sg * (c * e));
+                atomicAdd(row + 10, this->sg * ((this->ws - this->wa) * m));
+            }
+        }
+    }
+};
+
+// The containment walk of the 4-wide f16 tree, shared by query_sigma_kernel and query_sigma_grad_kernel through the
+// leaf accumulator: acc.leaf(A, ref, x, y, z) for every leaf whose box holds the point. True: the LDS stack could
+// overflow and the walk broke off (some leaves were handed out already); the caller walks the child-pair tree.
+template <class Acc>
+__device__ __forceinline__ bool sigma_walk_wide(const RenderArgs& A, float x, float y, float z, int* stack, Acc& acc) {
+    float ux = x, uy = y, uz = z;
+    node_space<true>(A, ux, uy, uz);
+    int sp = 0, node = 0;
+    for (;;) {
+        const uint4* np = reinterpret_cast<const uint4*>(A.hnodes4 + node);
+        const uint4 q0 = np[0], q1 = np[1], q2 = np[2], rf = np[3];
+        const uint32_t w[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
+        const int32_t ref[4] = {(int32_t)rf.x, (int32_t)rf.y, (int32_t)rf.z, (int32_t)rf.w};
+        if (sp + 4 > kStackSize) return true;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {  // child c: halves 6c .. 6c + 5 = min xyz, max xyz
+            float b[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                const int h = 6 * c + k;
+                const uint32_t word = w[h >> 1];
+                b[k] = (float)__builtin_bit_cast(_Float16, (uint16_t)((h & 1) ? (word >> 16) : (word & 0xffffu)));
+            }
+            const bool in = ref[c] != 0 && ux >= b[0] && ux <= b[3] && uy >= b[1] && uy <= b[4] && uz >= b[2] && uz <= b[5];
+            if (in) {
+                if (ref[c] < 0) acc.leaf(A, ref[c], x, y, z);
+                else stack[(sp++) * kQBlock] = ref[c];
+            }
+        }
+        if (sp == 0) return false;
+        node = stack[(--sp) * kQBlock];
+    }
+}
+
+// The same walk on the f32 child-pair tree: one push per level at most. True: the tree is deeper than the builder
+// allows and the walk broke off.
+template <class Acc>
+__device__ __forceinline__ bool sigma_walk_pair(const RenderArgs& A, float x, float y, float z, int* stack, Acc& acc) {
+    int sp = 0, node = 0;
+    for (;;) {
+        float f[12];
+        int2 nc;
+        load_pair<false>(A, node, f, nc);
+        int32_t go[2] = {0, 0};
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const float* b = f + 6 * s;
+            const int32_t c = s == 0 ? nc.x : nc.y;
+            const bool in = c != 0 && x >= b[0] && x <= b[3] && y >= b[1] && y <= b[4] && z >= b[2] && z <= b[5];
+            if (in) {
+                if (c < 0) acc.leaf(A, c, x, y, z);
+                else go[s] = c;
+            }
+        }
+        if (go[0] > 0 && go[1] > 0) {
+            if (sp >= kStackSize) return true;  // (deeper than the builder allows)
+            stack[(sp++) * kQBlock] = go[1];
+            node = go[0];
+        } else if (go[0] > 0 || go[1] > 0) {
+            node = go[0] > 0 ? go[0] : go[1];
+        } else {
+            if (sp == 0) return false;
+            node = stack[(--sp) * kQBlock];
+        }
+    }
+}
 
 __global__ void __launch_bounds__(kQBlock) query_sigma_kernel(RenderArgs A, const float* __restrict__ xyz, uint32_t n,
                                                               float* __restrict__ out, uint32_t* __restrict__ n_active) {
@@ -533,72 +679,10 @@ __global__ void __launch_bounds__(kQBlock) query_sigma_kernel(RenderArgs A, cons
     SigmaAcc acc;
     acc.reset();
     bool redo = A.hnodes4 == nullptr;
-    if (A.num_prims > 0 && !redo) {
-        float ux = x, uy = y, uz = z;
-        node_space<true>(A, ux, uy, uz);
-        int sp = 0, node = 0;
-        for (;;) {
-            const uint4* np = reinterpret_cast<const uint4*>(A.hnodes4 + node);
-            const uint4 q0 = np[0], q1 = np[1], q2 = np[2], rf = np[3];
-            const uint32_t w[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
-            const int32_t ref[4] = {(int32_t)rf.x, (int32_t)rf.y, (int32_t)rf.z, (int32_t)rf.w};
-            if (sp + 4 > kStackSize) {
-                redo = true;
-                break;
-            }
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {  // child c: halves 6c .. 6c + 5 = min xyz, max xyz
-                float b[6];
-#pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    const int h = 6 * c + k;
-                    const uint32_t word = w[h >> 1];
-                    b[k] = (float)__builtin_bit_cast(_Float16, (uint16_t)((h & 1) ? (word >> 16) : (word & 0xffffu)));
-                }
-                const bool in = ref[c] != 0 && ux >= b[0] && ux <= b[3] && uy >= b[1] && uy <= b[4] && uz >= b[2] && uz <= b[5];
-                if (in) {
-                    if (ref[c] < 0) acc.leaf(A, ref[c], x, y, z);
-                    else stack[(sp++) * kQBlock] = ref[c];
-                }
-            }
-            if (sp == 0) break;
-            node = stack[(--sp) * kQBlock];
-        }
-    }
-    if (A.num_prims > 0 && redo) {  // f32 child-pair tree: one push per level at most
+    if (A.num_prims > 0 && !redo) redo = sigma_walk_wide(A, x, y, z, stack, acc);
+    if (A.num_prims > 0 && redo) {
         acc.reset();
-        int sp = 0, node = 0;
-        bool bad = false;
-        for (;;) {
-            float f[12];
-            int2 nc;
-            load_pair<false>(A, node, f, nc);
-            int32_t go[2] = {0, 0};
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const float* b = f + 6 * s;
-                const int32_t c = s == 0 ? nc.x : nc.y;
-                const bool in = c != 0 && x >= b[0] && x <= b[3] && y >= b[1] && y <= b[4] && z >= b[2] && z <= b[5];
-                if (in) {
-                    if (c < 0) acc.leaf(A, c, x, y, z);
-                    else go[s] = c;
-                }
-            }
-            if (go[0] > 0 && go[1] > 0) {
-                if (sp >= kStackSize) {  // (deeper than the builder allows)
-                    bad = true;
-                    break;
-                }
-                stack[(sp++) * kQBlock] = go[1];
-                node = go[0];
-            } else if (go[0] > 0 || go[1] > 0) {
-                node = go[0] > 0 ? go[0] : go[1];
-            } else {
-                if (sp == 0) break;
-                node = stack[(--sp) * kQBlock];
-            }
-        }
-        if (bad) {
+        if (sigma_walk_pair(A, x, y, z, stack, acc)) {
             out[2 * i] = out[2 * i + 1] = __builtin_nanf("");
             if (n_active) n_active[i] = 0;
             return;
@@ -615,6 +699,120 @@ __global__ void __launch_bounds__(kQBlock) query_sigma_kernel(RenderArgs A, cons
     out[2 * i] = sa;
     out[2 * i + 1] = ss;
     if (n_active) n_active[i] = acc.cnt;
+}
+
+// One point of the sigma gradient: query_sigma_kernel's walks with the gradient's leaf accumulator. The adds to the
+// staging rows happen while a walk runs, so a walk whose adds must not stand is taken back by walking it again with
+// sg = -1: the walk is a function of the point and the tree alone, so it hands out the same Gaussians and breaks off
+// at the same node. That happens to a 4-wide walk that broke off for its stack (the child-pair walk then adds the
+// whole active set), to a child-pair walk deeper than the builder allows (the forward's NaN case) and to a point whose
+// summed m is <= 0 (the forward's (0, 0): non-positive densities only). None of it is on the path of an ordinary
+// point, and the loop keeps one inlined copy of each walk. The points-only form has nothing to take back.
+template <bool GAUSS, bool POINTS>
+__device__ __forceinline__ void sigma_grad_point(const RenderArgs& A, const float* __restrict__ xyz,
+                                                 const float* __restrict__ weight_as, uint32_t n,
+                                                 SigmaGradAcc<GAUSS, POINTS>& acc, float* __restrict__ grad_xyz) {
+    __shared__ int s_stack[kStackSize * kQBlock];
+    int* stack = s_stack + threadIdx.x;
+    const uint64_t i = (uint64_t)blockIdx.x * kQBlock + threadIdx.x;
+    if (i >= n) return;
+    const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
+    acc.wa = weight_as ? (double)weight_as[2 * i] : 1.0;
+    acc.ws = weight_as ? (double)weight_as[2 * i + 1] : 1.0;
+    acc.reset();
+    if constexpr (GAUSS) acc.sg = 1.0;
+    bool wide = A.hnodes4 != nullptr, bad = false, dead = true;
+    int undo = 0;  // 1: taking a broken-off 4-wide walk back, the child-pair walk follows; 2: taking the point back
+    while (A.num_prims > 0) {
+        const bool broke = wide ? sigma_walk_wide(A, x, y, z, stack, acc) : sigma_walk_pair(A, x, y, z, stack, acc);
+        if constexpr (GAUSS) {
+            if (undo == 2) break;
+            if (undo == 1) {
+                undo = 0;
+                acc.sg = 1.0;
+                wide = false;
+                acc.reset();
+                continue;
+            }
+        }
+        if (wide && broke) {
+            if (GAUSS && acc.cnt > 0) {
+                undo = 1;
+                if constexpr (GAUSS) acc.sg = -1.0;
+                continue;
+            }
+            wide = false;
+            acc.reset();
+            continue;
+        }
+        bad = broke;
+        dead = bad || acc.mass <= 0.0;
+        if (GAUSS && dead && acc.cnt > 0) {
+            undo = 2;
+            if constexpr (GAUSS) acc.sg = -1.0;
+            continue;
+        }
+        break;
+    }
+    if constexpr (POINTS) {
+        float ox = 0.0f, oy = 0.0f, oz = 0.0f;
+        if (bad) ox = oy = oz = __builtin_nanf("");
+        else if (!dead) ox = (float)acc.gx, oy = (float)acc.gy, oz = (float)acc.gz;
+        grad_xyz[3 * i] = ox;
+        grad_xyz[3 * i + 1] = oy;
+        grad_xyz[3 * i + 2] = oz;
+    }
+}
+
+template <bool POINTS>
+__global__ void __launch_bounds__(kQBlock) query_sigma_grad_kernel(RenderArgs A, const float* __restrict__ xyz,
+                                                                   const float* __restrict__ weight_as, uint32_t n,
+                                                                   double* __restrict__ stage, float* __restrict__ grad_xyz) {
+    SigmaGradAcc<true, POINTS> acc;
+    acc.acc = stage;
+    sigma_grad_point<true, POINTS>(A, xyz, weight_as, n, acc, grad_xyz);
+}
+
+// grad sigma at the points alone: no staging, no atomics.
+__global__ void __launch_bounds__(kQBlock) query_sigma_grad_points_kernel(RenderArgs A, const float* __restrict__ xyz,
+                                                                          const float* __restrict__ weight_as, uint32_t n,
+                                                                          float* __restrict__ grad_xyz) {
+    SigmaGradAcc<false, true> acc;
+    sigma_grad_point<false, true>(A, xyz, weight_as, n, acc, grad_xyz);
+}
+
+// Staging row j (tree order, in M's space) -> the caller's row gauss_order[j]: d/d mean[3], d/d cov {xx, xy, xz, yy,
+// yz, zz}, d/d density, d/d albedo. query_grad_finish_kernel's arithmetic (the staged g_mean and G_M carry the density
+// already): T = rho U, G_Sigma = -M G_M M - T M / 2, all in double and rounded to f32 once.
+__global__ void __launch_bounds__(256) query_sigma_grad_finish_kernel(const GaussianRecord* __restrict__ gauss,
+                                                                      const uint32_t* __restrict__ order,
+                                                                      const double* __restrict__ acc, uint32_t n,
+                                                                      float* __restrict__ grad) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= n) return;
+    const GRec g = load_rec(gauss, (int)j);
+    const double* a = acc + 11 * (size_t)j;
+    const double U = a[9], T = (double)g.density * U;
+    const double M[3][3] = {{g.m00, g.m01, g.m02}, {g.m01, g.m11, g.m12}, {g.m02, g.m12, g.m22}};
+    const double G[3][3] = {{a[3], a[4], a[5]}, {a[4], a[6], a[7]}, {a[5], a[7], a[8]}};
+    double MG[3][3], S[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) MG[r][c] = M[r][0] * G[0][c] + M[r][1] * G[1][c] + M[r][2] * G[2][c];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) S[r][c] = -(MG[r][0] * M[0][c] + MG[r][1] * M[1][c] + MG[r][2] * M[2][c]) - 0.5 * T * M[r][c];
+    float* out = grad + 11 * (size_t)order[j];
+    // (+ 0.0: a Gaussian holding no point gets +0, not the -0 of -(0) - 0)
+    out[0] = (float)(a[0] + 0.0);
+    out[1] = (float)(a[1] + 0.0);
+    out[2] = (float)(a[2] + 0.0);
+    out[3] = (float)(S[0][0] + 0.0);
+    out[4] = (float)(2.0 * S[0][1] + 0.0);
+    out[5] = (float)(2.0 * S[0][2] + 0.0);
+    out[6] = (float)(S[1][1] + 0.0);
+    out[7] = (float)(2.0 * S[1][2] + 0.0);
+    out[8] = (float)(S[2][2] + 0.0);
+    out[9] = (float)(U + 0.0);
+    out[10] = (float)(a[10] + 0.0);
 }
 
 // Device-side packing of the Python mirror's torch inputs into vr_ray rows (tmax: one value per ray, or one
@@ -677,6 +875,27 @@ hipError_t query_transmittance_ray_grad(const RenderArgs& A, const vr_ray* rays,
 hipError_t query_sigma(const RenderArgs& A, const float* xyz, uint32_t n, float* out, uint32_t* n_active, hipStream_t s) {
     hipLaunchKernelGGL(dev::query_sigma_kernel, dim3((n + dev::kQBlock - 1) / dev::kQBlock), dim3(dev::kQBlock), 0, s, A, xyz, n,
                        out, n_active);
+    return hipGetLastError();
+}
+
+// stage: 11 doubles per Gaussian of staging, zeroed here; grad: 11 floats per Gaussian, every one written; grad_xyz: 3
+// floats per point, every one written. Either output may be nullptr: without grad there is no staging and no atomic.
+hipError_t query_sigma_grad(const RenderArgs& A, const float* xyz, const float* weight_as, uint32_t n, double* stage, float* grad,
+                            float* grad_xyz, hipStream_t s) {
+    const dim3 grid((n + dev::kQBlock - 1) / dev::kQBlock), block(dev::kQBlock);
+    hipError_t e;
+    if (!grad || A.num_prims <= 0) {  // (an empty scene: grad has no entries)
+        if (grad_xyz && n > 0) hipLaunchKernelGGL(dev::query_sigma_grad_points_kernel, grid, block, 0, s, A, xyz, weight_as, n, grad_xyz);
+        return hipGetLastError();
+    }
+    if ((e = hipMemsetAsync(stage, 0, (size_t)A.num_prims * 11 * sizeof(double), s)) != hipSuccess) return e;
+    if (n > 0) {
+        if (grad_xyz) hipLaunchKernelGGL(dev::query_sigma_grad_kernel<true>, grid, block, 0, s, A, xyz, weight_as, n, stage, grad_xyz);
+        else hipLaunchKernelGGL(dev::query_sigma_grad_kernel<false>, grid, block, 0, s, A, xyz, weight_as, n, stage, grad_xyz);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(dev::query_sigma_grad_finish_kernel, dim3(((uint32_t)A.num_prims + 255u) / 256u), dim3(256), 0, s, A.gauss,
+                       A.gauss_order, stage, (uint32_t)A.num_prims, grad);
     return hipGetLastError();
 }
 

@@ -124,6 +124,26 @@ public:
         }
     }
 
+    // The gradient of those sigmas with respect to the Gaussians (vr_query_sigma_grad): row g of the result (11 floats
+    // per scene Gaussian) is sum_i (w_a d sigma_a + w_s d sigma_s)(pos_i) / d (mean[3], cov[6] = {xx, xy, xz, yy, yz, zz},
+    // density, albedo), weights_as = (w_a, w_s) per point; an empty `weights_as` means (1, 1) for every point, the
+    // gradient of sigma_t. *grad_pos (if given) receives 3 floats per point, the same weighted gradient with respect to
+    // the point itself.
+    std::vector<float> sigma_gradient(const std::vector<Eigen::Vector3f>& pos, const std::vector<float>& weights_as = {},
+                                      std::vector<float>* grad_pos = nullptr) const {
+        if (!weights_as.empty() && weights_as.size() != 2 * pos.size()) throw std::runtime_error("sigma_gradient: two weights per point");
+        vr_ctx* ctx = ready();
+        std::vector<float> xyz(3 * pos.size() + 1, 0.0f);  // (+ 1: never a NULL pointer)
+        for (size_t i = 0; i < pos.size(); ++i)
+            for (int k = 0; k < 3; ++k) xyz[3 * i + k] = pos[i][k];
+        std::vector<float> grad(11 * scene_.get_num_primitives() + 1, 0.0f);
+        if (grad_pos) grad_pos->assign(3 * pos.size(), 0.0f);
+        vr_cpp::check(vr_query_sigma_grad(ctx, xyz.data(), weights_as.empty() ? nullptr : weights_as.data(), pos.size(), grad.data(),
+                                          grad_pos && !pos.empty() ? grad_pos->data() : nullptr));
+        grad.pop_back();
+        return grad;
+    }
+
     // integrator.h:422-498 MultiScatterGaussians::get_free_flight_distance(ray, events, target_tau) per ray, the
     // events being the ray's own: the collision distance, or -1 where the ray leaves the mixture before the
     // target is reached. *albedo (if given) receives evaluate_albedo (gmm.h:128-143) over the critical segment's

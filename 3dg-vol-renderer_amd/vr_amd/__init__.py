@@ -653,6 +653,48 @@ class Device:
             act = cnt.astype(np.int32) if return_active else None
         return (sig, act) if return_active else sig
 
+    def query_sigma_grad(self, scene, points, weights=None, gaussians=True, positions=False):
+        """The gradient of query_sigma's sigma (vr_query_sigma_grad) at n points (n, 3) float32. weights (n, 2) float32
+        = (dL/d sigma_a, dL/d sigma_s) per point; None: (1, 1) everywhere, the gradient of sigma_t, whose albedo
+        column is exactly 0. gaussians=True: the (N, 11) float32 array sum_i w_i . d sigma(x_i) / d (mean[3], cov6 [xx xy
+        xz yy yz zz], density, albedo) of scene Gaussian g (an off-diagonal cov6 entry is the derivative with respect
+        to the stored number). positions=True: the (n, 3) array whose row i is w_i . d sigma(x_i) / d x_i. Returns the
+        one asked for, or (gaussians, positions) for both; positions alone runs without a single atomic add. The active
+        set is query_sigma's bit for bit; a point in no ellipsoid, or with a non-finite coordinate, contributes nothing
+        and gets a zero row. The per-Gaussian sums are double atomics: reproducible to the rounding of a double sum."""
+        torch_in = _query_point_args(points)
+        n = points.shape[0]
+        if not (gaussians or positions):
+            raise ValueError("query_sigma_grad: ask for gaussians, positions or both")
+        if weights is not None:
+            if _query_f32(weights, "weights", (2,)) != torch_in:
+                raise ValueError("weights must be of the same kind as points")
+            if weights.shape[0] != n:
+                raise ValueError(f"weights has {weights.shape[0]} rows for {n} points")
+        self.upload(scene)
+        N = scene.get_num_primitives()
+        if torch_in:
+            import torch
+            self._check_torch(points, *([] if weights is None else [weights]))
+            pts = points.contiguous()
+            wt = None if weights is None else weights.contiguous()
+            grad = torch.zeros((N, 11), dtype=torch.float32, device=points.device) if gaussians else None
+            gx = torch.zeros((n, 3), dtype=torch.float32, device=points.device) if positions else None
+            if n > 0 and (N > 0 or positions):
+                check(lib().vr_query_sigma_grad_device(self._h, pts.data_ptr(), None if wt is None else wt.data_ptr(), n,
+                                                       grad.data_ptr() if gaussians and N > 0 else None,
+                                                       gx.data_ptr() if positions else None,
+                                                       torch.cuda.current_stream(points.device).cuda_stream))
+        else:
+            pts = np.ascontiguousarray(points)
+            wt = None if weights is None else np.ascontiguousarray(weights)
+            grad = np.zeros((N, 11), np.float32) if gaussians else None
+            gx = np.zeros((n, 3), np.float32) if positions else None
+            if n > 0 and (N > 0 or positions):
+                check(lib().vr_query_sigma_grad(self._h, fptr(pts), None if wt is None else fptr(wt), n,
+                                                fptr(grad) if gaussians and N > 0 else None, fptr(gx) if positions else None))
+        return (grad, gx) if gaussians and positions else grad if gaussians else gx
+
     def query_events(self, scene, origins, directions):
         """GaussianMixtureModel::intersect_events (gmm.h:457-515) for n rays. Returns (offsets, t, gaussian,
         entering): ray i's events are the slice offsets[i]:offsets[i + 1] (offsets: (n + 1,) int64) of t

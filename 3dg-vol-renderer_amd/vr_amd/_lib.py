@@ -190,7 +190,9 @@ SIGNATURES = {
     "vr_query_transmittance_ray_grad_device": (ST, [P, P, ctypes.c_size_t, ctypes.c_uint32, P, P]),
     "vr_query_sigma": (ST, [P, FP, ctypes.c_size_t, FP, U32P]),
     "vr_query_sigma_device": (ST, [P, P, ctypes.c_size_t, P, P, P]),
-    "vr_query_events_count_device": (ST, [P, P, ctypes.c_size_t, P, ctypes.POINTER(ctypes.c_uint64)]),
+    "vr_query_sigma_grad": (ST, [P, FP, FP, ctypes.c_size_t, FP, FP]),
+    "vr_query_sigma_grad_device": (ST, [P, P, P, ctypes.c_size_t, P, P, P]),
+    "vr_query_events_count_device":(ST, [P, P, ctypes.c_size_t, P, ctypes.POINTER(ctypes.c_uint64)]),
     "vr_query_events_fill_device": (ST, [P, P, ctypes.c_size_t, P, P, P, ctypes.c_uint64, P]),
     "vr_query_events": (ST, [P, P, ctypes.c_size_t, U32P, FP, U32P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     "vr_query_free_flight": (ST, [P, P, FP, ctypes.c_size_t, FP, FP, U32P]),

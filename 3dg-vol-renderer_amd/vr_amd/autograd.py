@@ -20,8 +20,23 @@ forward runs the ray-gradient query instead of the transmittance query: one walk
 seven columns d tau_i / d (origin_i, direction_i, tmax_i), which forward saves and backward multiplies by grad_output.
 That is the exact Jacobian product, since tau_i depends on ray i only. The directions are normalised by the library,
 so directions.grad is the gradient through v / |v|. Both gradients are exact (closed form, float64 per hit); they are
-not differentiable a second time, and no gradient flows to albedo. When no ray input requires grad, forward and
-backward issue the calls they issue for the Gaussians alone.
+not differentiable a second time. The optical depth does not depend on albedo, so optical_depth gives it no gradient
+(sigma, below, does). When no ray input requires grad, forward and backward issue the calls they issue for the
+Gaussians alone.
+
+The extinction field itself, at the caller's points (Device.query_sigma / Device.query_sigma_grad):
+
+    sig = sigma(mean, cov6, density, albedo, points)                             # (n, 2) = (sigma_a, sigma_s)
+    loss = (sig.sum(1) - grid_density).square().mean()                           # fitting a CT / VDB grid, occupancy and
+    loss.backward()                                                              # sparsity terms, sigma_s L of a quadrature
+                                                                                 # mean.grad, cov6.grad, density.grad,
+                                                                                 # albedo.grad and points.grad
+
+sigma_resident is sigma for parameters on the points' device, as optical_depth_resident is. Backward is one
+Device.query_sigma_grad call with grad_output as the (w_a, w_s) weights; it asks for the Gaussians' rows only when a
+parameter requires grad and for the points' rows only when points does. The gradient is that of sigma_s = sum alpha m,
+sigma_a = sum (1 - alpha) m over the forward's active set (exact, float64 per active Gaussian); the 3-sigma cut-off is
+not differentiated, and the result is not differentiable a second time.
 """
 import numpy as np
 import torch
@@ -98,3 +113,55 @@ def optical_depth_resident(mean, cov6, density, albedo, origins, directions, tma
     device (ValueError otherwise), and forward uploads them with Device.upload_gaussians instead of copying them to
     the host. Same arguments, same gradients."""
     return _OpticalDepth.apply(mean, cov6, density, albedo, origins, directions, tmax, device, moving_bounds, True)
+
+
+class _Sigma(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mean, cov6, density, albedo, points, device, resident):
+        if resident:
+            for t, name in ((mean, "mean"), (cov6, "cov6"), (density, "density"), (albedo, "albedo")):
+                if t.device != points.device:
+                    raise ValueError(f"{name} is on {t.device}, the points on {points.device}: a resident scene's "
+                                     "parameters live on the points' device")
+        dev = Device.get(device)
+        if resident:
+            scene = dev.upload_gaussians(*(t.detach().to(torch.float32).contiguous() for t in (mean, cov6, density, albedo)))
+        else:
+            host = [t.detach().to("cpu", torch.float32).contiguous().numpy() for t in (mean, cov6, density, albedo)]
+            scene = Scene.from_gaussians(*host)
+        pts = points.detach().contiguous()
+        ctx.dev, ctx.scene, ctx.pts = dev, scene, pts
+        ctx.like = (mean, cov6, density, albedo)
+        ctx.pts_dtype = points.dtype
+        return dev.query_sigma(scene, pts)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_sigma):
+        need_g, need_x = any(ctx.needs_input_grad[:4]), ctx.needs_input_grad[4]
+        out, gx = (None,) * 4, None
+        if need_g or need_x:
+            got = ctx.dev.query_sigma_grad(ctx.scene, ctx.pts, grad_sigma.to(torch.float32).contiguous(),
+                                           gaussians=need_g, positions=need_x)
+            g, gx = got if need_g and need_x else (got, None) if need_g else (None, got)
+            if need_g:
+                cols = (g[:, 0:3], g[:, 3:9], g[:, 9], g[:, 10])
+                out = tuple(x.reshape(p.shape).to(device=p.device, dtype=p.dtype) if need else None
+                            for x, p, need in zip(cols, ctx.like, ctx.needs_input_grad[:4]))
+            if need_x:
+                gx = gx.to(ctx.pts_dtype)
+        return out + (gx, None, None)
+
+
+def sigma(mean, cov6, density, albedo, points, device=0):
+    """sigma (n, 2) float32 = (sigma_a, sigma_s) at points ((n, 3) float32 tensor on cuda:`device`) of the mixture of
+    Gaussians mean (N, 3), cov6 (N, 6) [xx xy xz yy yz zz], density (N,), albedo (N,) (tensors on any device): the values
+    of Device.query_sigma. Differentiable with respect to mean, cov6, density, albedo and points."""
+    return _Sigma.apply(mean, cov6, density, albedo, points, device, False)
+
+
+def sigma_resident(mean, cov6, density, albedo, points, device=0):
+    """sigma for parameters that never leave the GPU: mean, cov6, density and albedo must be on the points' device
+    (ValueError otherwise), and forward uploads them with Device.upload_gaussians instead of copying them to the
+    host. Same arguments, same gradients."""
+    return _Sigma.apply(mean, cov6, density, albedo, points, device, True)

@@ -624,6 +624,42 @@ vr_status vr_query_sigma(vr_ctx* ctx, const float* xyz, size_t n, float* sigma_a
 vr_status vr_query_sigma_device(vr_ctx* ctx, const float* d_xyz, size_t n, float* d_sigma_as, uint32_t* d_n_active,
                                 void* stream);
 
+/* The gradient of sigma at the points of vr_query_sigma, with respect to the Gaussians (albedo included) and to the
+ * points themselves. weight_as[2n] = (w_a, w_s)_i is dL/d sigma_a and dL/d sigma_s at point i; NULL: every weight is
+ * (1, 1), the gradient of sigma_t = sigma_a + sigma_s, whose albedo column is exactly 0.
+ *   grad[11 g + k] = sum_i (w_a d sigma_a(x_i) + w_s d sigma_s(x_i)) / d theta_{g,k}
+ * g the SCENE index and theta the vr_gaussian row in its own order: mean[3], cov[6] = {xx, xy, xz, yy, yz, zz}, density,
+ * albedo (the order of vr_query_transmittance_grad, plus albedo). An off-diagonal cov component is the derivative with
+ * respect to the stored number, 2 G_Sigma[i][j], as there. Every entry of grad (11 * num_primitives floats) is written;
+ * a Gaussian holding no point gets eleven +0.
+ *   grad_xyz[3 i + k] = (w_a d sigma_a + w_s d sigma_s)(x_i) / d x_{i,k}     (with NULL weights: grad sigma_t)
+ * Either output may be NULL: grad == NULL is the gradient at the points alone (no staging, no atomic add); both NULL with
+ * n > 0 is VR_ERR_INVALID. n == 0 is VR_OK: it zeroes grad if given and touches nothing else. The common errors above
+ * apply (xyz == NULL with n > 0: VR_ERR_INVALID).
+ * Definition. The function differentiated is sigma_s = sum alpha_g m_g, sigma_a = sum (1 - alpha_g) m_g over the active
+ * set (what the forward's a_mix * sum and (1 - a_mix) * sum are, up to rounding). The active set is the forward query's
+ * bit for bit: p.(M p) - 9 <= 0 in f32, in its arithmetic. The 3-sigma cut-off itself is not differentiated (a point on
+ * it has measure zero). Per active (i, g), from the record's f32 mean, M, norm, rho, alpha and the point read as doubles:
+ * p = x - mean, q = p.Mp, e = norm exp(-q / 2), m = rho e, c = w_a (1 - alpha) + w_s alpha, and
+ *   g_mean += c m M p      G_M += -c m p p^T / 2      U += c e (the density component)
+ *   g_albedo += (w_s - w_a) m      g_x(i) += -c m M p.
+ * Per Gaussian, as for the optical depth: T = rho U, G_Sigma = -M G_M M - T M / 2 (the second term is the derivative of
+ * norm through |Sigma|^(-1/2)).
+ * A point whose double sum of m over its active set is <= 0 (non-positive densities only; the forward gives (0, 0)) and
+ * a point with a non-finite coordinate (it lies in no box) contribute nothing and get a zero grad_xyz row. A point whose
+ * child-pair walk is deeper than the builder allows (the forward's NaN) contributes nothing and gets a NaN row. (The
+ * adds to grad happen while a point's walk runs; those of a point that turns out not to contribute are added again
+ * with the opposite sign, so "nothing" holds to the rounding of a double sum.)
+ * Arithmetic: the decisions are f32, everything on a decided (i, g) is double, the sums per Gaussian are double atomic
+ * adds in arrival order, the sums per point stay in registers, and each result is rounded to f32 once. A result is
+ * reproducible to the rounding of a double sum (grad_xyz bit for bit) and does not depend on VR_OPT_HALF_NODES /
+ * VR_OPT_DEVICE_BVH beyond that. The staging (88 bytes per Gaussian) is the query's own and is zeroed on `stream` by
+ * each call that asks for grad. */
+vr_status vr_query_sigma_grad(vr_ctx* ctx, const float* xyz, const float* weight_as, size_t n, float* grad,
+                              float* grad_xyz);
+vr_status vr_query_sigma_grad_device(vr_ctx* ctx, const float* d_xyz, const float* d_weight_as, size_t n, float* d_grad,
+                                     float* d_grad_xyz, void* stream);
+
 /* GaussianMixtureModel::intersect_events (gmm.h:457-515; tmax is not read): per ray the events of every
  * Gaussian it hits, an entry at t_enter (clamped to 0 for an origin inside) and an exit at t_exit, sorted by
  * t. Ray i's events are t[offsets[i] .. offsets[i + 1]) and ev[..] = scene_index << 1 | entering

@@ -6,12 +6,15 @@ rays packed on the device), every query is warmed up, and the figure is the medi
 events on torch's current stream. Prints one JSON line and, with --out, writes it to a file.
 
     python tools/query_bench.py [--gaussians 1000000] [--rays 4194304] [--points 4194304] [--repeats 5] [--out F]
-                                [--flight-scene FILE] [--only all|mixture|flight|grad|raygrad|upload]
+                                [--flight-scene FILE] [--only all|mixture|flight|grad|raygrad|upload|sigmagrad]
 
 --only grad times the optical-depth gradient query (Device.query_transmittance_grad, unit weights, moving and frozen
 bounds) beside the tau query on the same rays, on --flight-scene and on the make_random scene (--gaussians 0 skips it).
 --only raygrad does the same for the ray gradient (Device.query_transmittance_ray_grad, moving and frozen bounds, and
 with unit=True on the same stored directions).
+--only sigmagrad times the sigma gradient query (Device.query_sigma_grad, weights None: both outputs, positions only,
+Gaussians only) beside query_sigma on the same points, on a make_random scene of --gaussians Gaussians: --points points,
+point i in or just outside Gaussian i mod N (mean + chol(cov) r u, u a uniform direction, r uniform in [0, 3.3]).
 --only upload times getting a scene whose parameters live in torch tensors on the GPU onto the device, on --flight-scene
 and on make_random scenes of 100 000 and --gaussians Gaussians: (a) a copy to the host, Scene.from_gaussians and
 Device.upload with the host builder, (b) the same with device_bvh = 1, (c) Device.upload_gaussians. A host clock
@@ -60,7 +63,7 @@ def main():
     ap.add_argument("--seed", type=int, default=2025)
     ap.add_argument("--out", default=None)
     ap.add_argument("--flight-scene", default=os.path.join(ROOT, "tests", "golden", "scenes", "1000_random.txt"))
-    ap.add_argument("--only", choices=("all", "mixture", "flight", "grad", "raygrad", "upload"), default="all")
+    ap.add_argument("--only", choices=("all", "mixture", "flight", "grad", "raygrad", "upload", "sigmagrad"), default="all")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -89,6 +92,9 @@ def main():
     if args.only == "raygrad":
         res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
         res.update(raygrad(args, dev, o, d, timed))
+    if args.only == "sigmagrad":
+        res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
+        res.update(sigmagrad(args, dev, timed))
     if args.only == "upload":
         res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
         res.update(upload(args, dev, o, d))
@@ -121,6 +127,35 @@ def grad(args, dev, o, d, timed):
                     "gaussians_hit": int((g[:, 9] != 0).sum()), "mean_tau": float(tau[1].mean()),
                     "all_ms": {"tau": tau_all, "grad": g_all, "grad_frozen": f_all}})
     return {"grad": out, "timing": "median of HIP-event intervals on torch's current stream, inputs on the device"}
+
+
+def sigmagrad(args, dev, timed):
+    """The sigma gradient query in its three forms and the sigma query on the same points."""
+    import torch
+    scene = vr.Scene(vr.Scene.GAUSSIANS)
+    scene.add_random_gaussians(args.gaussians, seed=args.seed, variant=0)
+    g = scene.gaussians().astype(np.float64)
+    c6 = g[:, 3:9]
+    cov = np.stack([c6[:, [0, 1, 2]], c6[:, [1, 3, 4]], c6[:, [2, 4, 5]]], 1)
+    rng = np.random.default_rng(7)
+    u = rng.normal(size=(args.points, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    r = rng.uniform(0.0, 3.3, args.points)
+    k = np.arange(args.points) % len(g)
+    p = torch.tensor((g[k, 0:3] + np.einsum("nij,nj->ni", np.linalg.cholesky(cov)[k], r[:, None] * u)).astype(np.float32)).cuda()
+    dev.upload(scene)
+    s_ms, s_all, sg = timed(lambda: dev.query_sigma(scene, p, return_active=True))
+    b_ms, b_all, both = timed(lambda: dev.query_sigma_grad(scene, p, gaussians=True, positions=True))
+    x_ms, x_all, _ = timed(lambda: dev.query_sigma_grad(scene, p, gaussians=False, positions=True))
+    g_ms, g_all, _ = timed(lambda: dev.query_sigma_grad(scene, p))
+    out = {"scene": f"make_random_{args.gaussians}", "gaussians": scene.get_num_primitives(), "points": args.points,
+           "sigma_ms": s_ms, "both_ms": b_ms, "positions_ms": x_ms, "gaussians_ms": g_ms,
+           "both_over_sigma": b_ms / s_ms, "positions_over_sigma": x_ms / s_ms, "gaussians_over_sigma": g_ms / s_ms,
+           "both_mpoints_s": args.points / b_ms / 1e3, "mean_active": float(sg[1].float().mean()),
+           "max_active": int(sg[1].max()), "gaussians_holding_points": int((both[0][:, 9] != 0).sum()),
+           "all_ms": {"sigma": s_all, "both": b_all, "positions": x_all, "gaussians": g_all}}
+    return {"sigmagrad": out, "timing": "median of HIP-event intervals on torch's current stream, inputs on the device; "
+                                        "each call allocates its result tensors"}
 
 
 def upload(args, dev, o, d):

@@ -27,6 +27,9 @@
 // one line `tg <scene index> <10 hex words>` per Gaussian (d/d mean[3], cov[6], density).
 // --query-ray-grad RAYS.bin (the same file) prints MixtureQuery::transmittance_ray_gradient of the file's rays: one line
 // `rg <ray index> <8 hex words>` per ray (d/d origin[3], d/d tmax, d/d direction[3], tau).
+// --query-sigma-grad RAYS.bin (the same file) prints MixtureQuery::sigma_gradient at the file's points, all weights (1, 1):
+// one line `sg <scene index> <11 hex words>` per Gaussian (d/d mean[3], cov[6], density, albedo), then one line
+// `sx <point index> <3 hex words>` per point (the gradient with respect to the point).
 // --upload-device (Gaussian scenes, one GPU): copies the loaded scene's rows to device memory and uploads them with
 // HipIntegrator::upload_device (vr_upload_gaussians_device: records, boxes and tree computed on the device), then
 // renders the scene the context holds.
@@ -129,6 +132,23 @@ static int run_query_ray_grad(const Scene& scene, const std::string& path) {
     return 0;
 }
 
+// --query-sigma-grad: the gradient of sigma_t at the file's points, per Gaussian and per point.
+static int run_query_sigma_grad(const Scene& scene, const std::string& path) {
+    std::vector<Ray> rays;
+    std::vector<float> tmax, gx;
+    std::vector<Eigen::Vector3f> pos;
+    read_query_file(path, rays, tmax, pos);
+    const std::vector<float> g = MixtureQuery(scene).sigma_gradient(pos, {}, &gx);
+    for (size_t i = 0; i < g.size() / 11; ++i) {
+        std::printf("sg %zu", i);
+        for (int k = 0; k < 11; ++k) std::printf(" %08x", fbits(g[11 * i + k]));
+        std::printf("\n");
+    }
+    for (size_t i = 0; i < gx.size() / 3; ++i)
+        std::printf("sx %zu %08x %08x %08x\n", i, fbits(gx[3 * i]), fbits(gx[3 * i + 1]), fbits(gx[3 * i + 2]));
+    return 0;
+}
+
 // --upload-device: the scene's rows as four device arrays, uploaded from there.
 static void upload_from_device_memory(vr_ctx* ctx, const Scene& scene) {
     if (scene.volume_type != Scene::VolumeType::GAUSSIANS) throw std::runtime_error("--upload-device needs a Gaussian scene");
@@ -183,7 +203,7 @@ int main(int argc, char** argv) try {
     int inverse = 0, stoch = 4, final_spp = 0;
     uint64_t seed = 0;
     float lr = 1e-2f;
-    std::string ref_path, sfd_out, gif_path, query_path, query_grad_path, query_ray_grad_path;
+    std::string ref_path, sfd_out, gif_path, query_path, query_grad_path, query_ray_grad_path, query_sigma_grad_path;
     int frames = 120;
     float fps = 30.0f;
     Eigen::Vector3f pos(0, 1, 6), lookat(0, 1, 0);
@@ -212,6 +232,7 @@ int main(int argc, char** argv) try {
         else if (a == "--query") query_path = next();
         else if (a == "--query-grad") query_grad_path = next();
         else if (a == "--query-ray-grad") query_ray_grad_path = next();
+        else if (a == "--query-sigma-grad") query_sigma_grad_path = next();
         else if (a == "--gif") gif_path = next();
         else if (a == "--frames") frames = std::atoi(next());
         else if (a == "--fps") fps = std::strtof(next(), nullptr);
@@ -270,6 +291,7 @@ int main(int argc, char** argv) try {
     if (!query_path.empty()) return run_queries(scene, query_path);
     if (!query_grad_path.empty()) return run_query_grad(scene, query_grad_path);
     if (!query_ray_grad_path.empty()) return run_query_ray_grad(scene, query_ray_grad_path);
+    if (!query_sigma_grad_path.empty()) return run_query_sigma_grad(scene, query_sigma_grad_path);
 
     if (!gif_path.empty()) {  // main.cpp:81-114
         const float radius = 6.0f, height_pos = 1.0f;
