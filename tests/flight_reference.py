@@ -89,19 +89,35 @@ CASES = {
     "comb_back": (comb_gaussians, O.PINHOLE, COMB_FOV, *_comb_camera(-1.0)),
 }
 # scattering rays of the 256 (the oracle's own counts, ANALYTIC_PLUS_NEWTON)
+# Elongated Gaussians (aniso_cases.py), kept out of CASES: the tests that run over CASES hold the float64 model to bars
+# sized at kappa <= 12; test_aniso_reference.py asserts the same conditions of these two on the CPU. The camera looks
+# at the origin from 4 units.
+ANISO_CAMERA = (np.float32([0.0, 0.0, 4.0]), np.float32([0.0, 0.0, -1.0]))
+
+
+def _aniso(shape, ratio):
+    def src():
+        import aniso_cases as A
+        return A.arrays(A.gaussians(shape, ratio))
+    return (src, O.PINHOLE, FOV, *ANISO_CAMERA)
+
+
+ANISO_CASES = {"disc10": _aniso("disc", 10), "disc30": _aniso("disc", 30)}
+ALL_CASES = {**CASES, **ANISO_CASES}
 SCATTERING = {"250_random": 222, "1000_random": 246, "many_gaussians": 44, "250_random_ortho": 256, "slab": 235,
-              "coincident200": 115, "comb": 214, "comb_back": 214}
+              "coincident200": 115, "comb": 214, "comb_back": 214,
+              "disc10": 213, "disc30": 210}
 
 
 def camera_of(name):
     """(position, view direction) of the case's camera."""
-    case = CASES[name]
+    case = ALL_CASES[name]
     return (case[3], case[4]) if len(case) > 3 else (CAM_POS, main_view_dir())
 
 
 @functools.lru_cache(maxsize=None)
 def oracle_scene(name):
-    src = CASES[name][0]
+    src = ALL_CASES[name][0]
     if callable(src):
         return O.OracleScene.from_gaussians(*src(), [LIGHT[0]], [LIGHT[1]])
     return O.OracleScene.load_gmm(scene_path(src))
@@ -109,7 +125,7 @@ def oracle_scene(name):
 
 @functools.lru_cache(maxsize=None)
 def device_scene(name):
-    src = CASES[name][0]
+    src = ALL_CASES[name][0]
     if callable(src):
         return vr.Scene.from_gaussians(*src(), lights=[vr.Light(*LIGHT)])
     return vr.Scene.load_GMM(scene_path(src))
@@ -119,7 +135,7 @@ def device_scene(name):
 def record(name, solver=0):
     """(256, 8) f32: the oracle's record under distance solver `solver` (distance_solvers.h:143-187; 0 is the
     reference's ANALYTIC_PLUS_NEWTON), NaN where the first flight escapes."""
-    _, cam, fov = CASES[name][:3]
+    _, cam, fov = ALL_CASES[name][:3]
     pos, view = camera_of(name)
     L = O.lib()
     L.orc_ff_debug.argtypes = [ctypes.POINTER(ctypes.c_float)]
@@ -141,7 +157,7 @@ def record(name, solver=0):
 @functools.lru_cache(maxsize=None)
 def rays(name):
     """(origins (256, 3), unit directions (256, 3), targets (256,)) f32 of the case's paths, pixel y * W + x."""
-    _, cam_type, fov = CASES[name][:3]
+    _, cam_type, fov = ALL_CASES[name][:3]
     pos, view = camera_of(name)
     cam = vr.Pinhole_Camera(pos, view, fov) if cam_type == O.PINHOLE else vr.Orthographic_Camera(pos, view)
     f = np.float32

@@ -23,6 +23,7 @@ TINY_SHARE = 0.01  # ... and at most this share of a pixel's rows
 SPREAD = (0.05, 0.95)
 MIN_SPREAD_SHARE = 0.25
 BUDGET = 1.2e-6    # test_secondary_cut_off_stays_within_its_pixel_budget's figure
+FAIR_E_REF = 0.5e-4  # a ray whose oracle Tr is this close to the float64 model's is a fair one (compare_rows' tr_f64)
 STEP = 0.01
 ENV = (0.53, 0.81, 0.92)
 
@@ -44,6 +45,11 @@ class Report:
         self.tr_min = 1.0
         self.budget = 0.0
         self.one_sided = 0  # steps on one side only that pass as underflow decisions
+        # with a float64 ray model (compare_rows' tr_f64): fair rays, and the two rules' largest figures
+        self.fair_rays = 0
+        self.max_fair = 0.0    # |Tr_dev - Tr_oracle| over the fair rays
+        self.max_other = 0.0   # |Tr_dev - Tr_f64| - e_ref over the other rays
+        self.max_e_ref = 0.0   # the oracle's own distance from float64
 
     def kinds(self):
         return {f.kind for f in self.findings}
@@ -61,7 +67,15 @@ class Report:
         self.tr_min = min(self.tr_min, other.tr_min)
         self.budget = max(self.budget, other.budget)
         self.one_sided += other.one_sided
+        self.fair_rays += other.fair_rays
+        self.max_fair = max(self.max_fair, other.max_fair)
+        self.max_other = max(self.max_other, other.max_other)
+        self.max_e_ref = max(self.max_e_ref, other.max_e_ref)
         return self
+
+    @property
+    def fair_share(self):
+        return self.fair_rays / self.rays if self.rays else 0.0
 
     @property
     def spread_share(self):
@@ -91,10 +105,16 @@ def ray_weights(pos, light_pos, light_int, env, n_env):
     return np.concatenate([li / d2[:, None], w_env]) if len(lp) else w_env
 
 
-def compare_rows(dev, orc, light_pos, light_int, env, budget=False):
+def compare_rows(dev, orc, light_pos, light_int, env, budget=False, tr_f64=None):
     """Device rows against oracle rows of one pixel, matched by step index. Returns a Report whose findings name
     every row, column and ray over its bar. budget=True is the t_eps > 0 form: rows up to the device's last
-    step, every ray's |dTr| weighted into the pixel budget instead of held to TR_TOL."""
+    step, every ray's |dTr| weighted into the pixel budget instead of held to TR_TOL.
+
+    tr_f64 ({step: float64 Tr of the row's rays}, ray_model_f64) is for scenes on which the oracle's own f32 Tr is far
+    from float64 (elongated Gaussians): with e_ref = |Tr_oracle - Tr_f64|, a fair ray (e_ref <= FAIR_E_REF) is held to
+    |Tr_dev - Tr_oracle| <= TR_TOL as ever, any other ray to |Tr_dev - Tr_f64| <= e_ref + TR_TOL (the device is never
+    further from the truth than the reference, plus the bar; finding kind "tr_f64"). Li + Le against the oracle's
+    then gets what the two rules leave a ray: TR_TOL, plus 2 e_ref where the ray is not fair."""
     dev = np.asarray(dev, np.float32)
     orc = np.asarray(orc, np.float32)
     rep = Report()
@@ -150,10 +170,26 @@ def compare_rows(dev, orc, light_pos, light_int, env, budget=False):
             rep.budget += ts_o * STEP * INV4PI * float((w.max(axis=1) * np.nan_to_num(dtr, nan=np.inf)).sum())
             continue
         rep.max_dtr = max(rep.max_dtr, float(np.nanmax(dtr)) if len(dtr) else 0.0)
-        for s in np.nonzero(~(dtr < TR_TOL))[0]:
-            rep.findings.append(Finding("tr", k, int(s), float(tr_d[s]), float(tr_o[s])))
+        slack = np.zeros(3)
+        if tr_f64 is None:
+            for s in np.nonzero(~(dtr < TR_TOL))[0]:
+                rep.findings.append(Finding("tr", k, int(s), float(tr_d[s]), float(tr_o[s])))
+        else:
+            t64 = np.asarray(tr_f64[k], np.float64)
+            e_ref = np.abs(tr_o - t64)
+            fair = e_ref <= FAIR_E_REF
+            over = np.abs(tr_d - t64) - e_ref
+            rep.fair_rays += int(fair.sum())
+            rep.max_e_ref = max(rep.max_e_ref, float(e_ref.max()) if len(e_ref) else 0.0)
+            rep.max_fair = max(rep.max_fair, float(np.nanmax(dtr[fair])) if fair.any() else 0.0)
+            rep.max_other = max(rep.max_other, float(np.nanmax(over[~fair])) if (~fair).any() else 0.0)
+            for s in np.nonzero(fair & ~(dtr < TR_TOL))[0]:
+                rep.findings.append(Finding("tr", k, int(s), float(tr_d[s]), float(tr_o[s])))
+            for s in np.nonzero(~fair & ~(over <= TR_TOL))[0]:
+                rep.findings.append(Finding("tr_f64", k, int(s), float(tr_d[s]), (float(tr_o[s]), float(t64[s]))))
+            slack = (np.where(fair, 0.0, 2.0 * e_ref)[:, None] * w).sum(axis=0)
         for c in range(3):
-            if not abs(float(a[5 + c]) - float(b[5 + c])) <= TR_TOL * s_one[c]:
+            if not abs(float(a[5 + c]) - float(b[5 + c])) <= TR_TOL * s_one[c] + slack[c]:
                 rep.findings.append(Finding("s_oracle", k, c, float(a[5 + c]), float(b[5 + c])))
     if budget and not rep.budget <= BUDGET:
         rep.findings.append(Finding("budget", None, None, rep.budget, BUDGET))
@@ -167,29 +203,33 @@ def pixel_from_rows(rows, step=STEP):
     return terms.sum(axis=0), len(rows) * 2.0 ** -23 * np.abs(terms).sum(axis=0)
 
 
-def oracle_rows(osc, x, y, W, H, env_samples, step=STEP):
-    """The oracle's rows of pixel (x, y) under the device's tie rule (stable event order)."""
+def oracle_rows(osc, x, y, W, H, env_samples, step=STEP, cam=None):
+    """The oracle's rows of pixel (x, y) under the device's tie rule (stable event order). cam: (position, view
+    direction) of the pinhole camera, the main view's by default."""
+    pos, view = cam if cam is not None else (CAM_POS, main_view_dir())
     with O.stable_ties():
-        return O.debug_pixel_records(osc, CAM_POS, main_view_dir(), FOV, x, y, W, H, step, env_samples)
+        return O.debug_pixel_records(osc, pos, view, FOV, x, y, W, H, step, env_samples)
 
 
-def oracle_rows_many(osc, pixels, W, H, env_samples, step=STEP):
+def oracle_rows_many(osc, pixels, W, H, env_samples, step=STEP, cam=None):
     """oracle_rows of several pixels, one thread each (the trace buffer is per thread; a pixel of the 200-deep
     nested scene costs seconds)."""
     from concurrent.futures import ThreadPoolExecutor
     O.lib()
+    pos, view = cam if cam is not None else (CAM_POS, main_view_dir())
     pixels = [(int(x), int(y)) for x, y in pixels]
     with O.stable_ties(), ThreadPoolExecutor(max_workers=max(1, min(8, len(pixels)))) as pool:
-        rows = list(pool.map(lambda p: O.debug_pixel_records(osc, CAM_POS, main_view_dir(), FOV, p[0], p[1], W, H, step,
+        rows = list(pool.map(lambda p: O.debug_pixel_records(osc, pos, view, FOV, p[0], p[1], W, H, step,
                                                              env_samples), pixels))
     return dict(zip(pixels, rows))
 
 
-def record_active(osc, x, y, W, H, env_samples, k, step=STEP):
+def record_active(osc, x, y, W, H, env_samples, k, step=STEP, cam=None):
     """orc_debug_record_active: the scene indices active at scattering step k of pixel (x, y) (None: no such
-    step), for a failure message."""
+    step), for a failure message and for ray_model_f64."""
+    pos, view = cam if cam is not None else (CAM_POS, main_view_dir())
     with O.stable_ties():
-        return O.debug_record_active(osc, CAM_POS, main_view_dir(), FOV, x, y, W, H, k, step, env_samples)
+        return O.debug_record_active(osc, pos, view, FOV, x, y, W, H, k, step, env_samples)
 
 
 # ---- the cases of test_gpu_records.py; test_records_reference.py evaluates their oracle side without a GPU ----
@@ -215,7 +255,7 @@ NESTED_LIGHT = ([0.0, 5.0, 0.0], [1.0, 1.0, 1.0])
 # 48 x 48, env_samples 8: every first-light ray of these pixels is one of the slow ones
 LIGHT_INSIDE_PIXELS = [(24, 3), (27, 3), (21, 6), (21, 15)]
 # 32 x 32, env_samples 8: each has three environment rays with a chord in the f32 error band (band_chords)
-BAND_PIXELS = [(21, 17), (19, 14), (17, 11), (16, 22), (16, 11), (15, 20)]
+BAND_PIXELS = [(15, 17), (14, 16), (16, 18), (14, 13), (14, 12), (17, 9)]
 CHORD_BAND = 8.0 * 2.0 ** -23  # vr_gauss_common.h kChordBand
 # (scene file, W, env_samples, pixels) at t_eps = 1e-6
 CUTOFF_CASES = {
@@ -280,12 +320,79 @@ def band_shell_gaussians(n_shell=1500, sigma=0.02, radius=2.5):
     return mean, cov, dens, alb, np.float32([[0.0, 5.0, 0.5]]), np.float32([[20, 20, 20]])
 
 
+def _pcg32_textbook(seed, seq, n):
+    """n outputs of PCG32(seed, seq) with the textbook output function (a rotation by the top five state bits): the
+    oracle's uniform_env. O.pcg32 returns next_u32's outputs, whose rotation differs (the path sampler's)."""
+    m64 = (1 << 64) - 1
+    inc = ((seq << 1) | 1) & m64
+    state = inc  # the constructor: one step from state 0, add the seed, one more step
+    state = ((state + seed) * 6364136223846793005 + inc) & m64
+    out = np.zeros(n, np.uint32)
+    for i in range(n):
+        old = state
+        state = (old * 6364136223846793005 + inc) & m64
+        shifted = (((old >> 18) ^ old) >> 27) & 0xFFFFFFFF
+        rot = old >> 59
+        out[i] = ((shifted >> rot) | (shifted << ((-rot) & 31))) & 0xFFFFFFFF
+    return out
+
+
 def env_directions(x, y, k, env_samples):
     """The environment directions of step k of pixel (x, y), as the oracle draws them (PCG32 keyed by pixel and
-    step, 24-bit uniforms)."""
-    out = O.pcg32(O.derive_path_seed(x, y, k), 1, 2 * env_samples)
-    xi = (out >> 8).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    step, its textbook output, 24-bit uniforms): secondary_rays' float64 model reproduces the oracle's own Tr along
+    them to 5e-5 at kappa 9 (test_aniso_reference.py), which pins them."""
+    xi = (_pcg32_textbook(O.derive_path_seed(x, y, k), 1, 2 * env_samples) >> 8).astype(np.float32) * np.float32(1.0 / 16777216.0)
     return np.array([O.env_dir(xi[2 * i], xi[2 * i + 1]) for i in range(env_samples)], np.float64)
+
+
+def secondary_rays(row, x, y, light_pos, env_samples):
+    """(origins, unit directions (m, 3) f32, ends (m,) f32) of the secondary rays of one oracle row of pixel (x, y), in
+    the row's order, as the reference forms them in f32: towards light l, Ray(pos, normalized(l - pos)) up to
+    norm(l - pos) (the Ray constructor normalises once more); then Ray(pos, env_dir(xi1, xi2)) without end."""
+    f = np.float32
+    pos = np.asarray(row[1:4], f)
+    lp = np.asarray(light_pos, f).reshape(-1, 3)
+
+    def unit(v):
+        s = v[:, 0] * v[:, 0] + (v[:, 1] * v[:, 1] + v[:, 2] * v[:, 2])
+        return (v / np.sqrt(s)[:, None]).astype(f), np.sqrt(s)
+
+    v = (lp - pos[None]).astype(f)
+    wi, dist = unit(v) if len(lp) else (v, np.zeros(0, f))
+    env = np.asarray(env_directions(x, y, int(row[0]), env_samples), f).reshape(-1, 3)
+    d = unit(np.concatenate([wi, env]).astype(f))[0]
+    end = np.concatenate([dist.astype(f), np.full(len(env), np.inf, f)])
+    return np.tile(pos, (len(d), 1)), d, end
+
+
+def ray_model_f64(rec, rows, x, y, light_pos, env_samples, active=None):
+    """{step: float64 Tr of the row's rays}: aniso_cases.Pairs64 (float64 decisions, bounds and closed-form optical depth
+    on the f32 records `rec`) along secondary_rays of every oracle row of pixel (x, y), each ray cut at its end.
+    active ({step: scene indices}, record_active) is the row's active list, a decision the primary march took in f32
+    from the camera's distance: the reference pre-activates those Gaussians at t = 0 whatever p.M.p says at the row's
+    position (test_integrators.h:209-211), so a member the ray crosses counts over [0, t_exit] and a member it misses
+    stays active to the ray's end, the light's distance or an environment ray's last event (:220-235, :258-271).
+    Without it the float64 p.M.p <= 9 at the origin decides, which is the same set but for members within the
+    march's f32 error of their 3-sigma surface."""
+    import aniso_cases as A
+    out = {}
+    for row in rows:
+        o, d, end = secondary_rays(row, x, y, light_pos, env_samples)
+        pairs = A.Pairs64(rec, o, d, unit=True)
+        end = end.astype(np.float64)[:, None]
+        a, b = np.maximum(pairs.t0, 0.0), np.minimum(pairs.t1, end)
+        use = pairs.hit & (b > a)
+        if active is not None:
+            member = np.zeros(len(rec), bool)
+            member[np.asarray(active[int(row[0])], np.int64)] = True
+            last = np.where(pairs.hit, pairs.t1, 0.0).max(1, keepdims=True)  # an environment ray's last event
+            stop = np.where(np.isfinite(end), end, last)
+            a = np.where(member[None, :], 0.0, a)
+            b = np.where(member[None, :] & ~pairs.hit, stop, b)
+            use = np.where(member[None, :], b > a, use)
+        tau = np.where(use, pairs.tau(a, b), 0.0).sum(1)
+        out[int(row[0])] = np.exp(-tau)
+    return out
 
 
 def band_chords(arrays, rows, x, y, env_samples):

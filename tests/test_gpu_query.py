@@ -417,7 +417,8 @@ def test_sigma_matches_float64_model(name):
     n = 1024
     p = points(name, n)
     ref, ref_act, q = sigma_model(name, p)
-    near = np.any(np.abs(q - 9.0) <= 9e-4, axis=1)  # f32 error of q: a few eps * kappa, kappa <= 12
+    # f32 error of q: a few eps * kappa, kappa <= 12 (beyond: test_gpu_aniso_query.py, whose margin grows with kappa)
+    near = np.any(np.abs(q - 9.0) <= 9e-4, axis=1)
     print(f"sigma {name}: {int(near.sum())} points excluded, nearest |q - 9| = {np.min(np.abs(q - 9.0)):.2e}")
     assert near.mean() <= 0.01
     keep = ~near
