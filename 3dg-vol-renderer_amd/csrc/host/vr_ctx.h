@@ -131,10 +131,15 @@ struct vr_ctx {
     vr::DevBuf<uint32_t> q_off, q_cnt;          // events: offsets (host form), counts,
     vr::DevBuf<unsigned long long> q_keys, q_keys2;  // sort keys (in / out),
     vr::DevBuf<std::byte> q_tmp;                // scan + sort scratch
-    vr::DevBuf<std::byte> q_ctl;      // words [0..3], [6] ray counters of the five persistent walks, [4..5] the 64-bit event total
+    vr::DevBuf<std::byte> q_ctl;      // words [0..3], [6] ray counters of the five persistent walks, [4..5] the 64-bit event total,
+                                      // [8], [9] the counters of the profile query's two walks
     vr::DevBuf<double> q_grad;        // gradient query: 10 doubles of staging per Gaussian (tree order), zeroed per call
     vr::DevBuf<double> q_sgrad;       // sigma gradient query: 11 doubles of staging per Gaussian, its own (the two
                                       // gradient queries may be queued on different streams)
+    // profile query (kernels/vr_query_profile.hip): the host forms' samples, weights and results on the device, and the
+    // gradient's 10 doubles of staging per Gaussian, its own for q_sgrad's reason
+    vr::DevBuf<float> q_prof_t, q_prof_w, q_prof_out;
+    vr::DevBuf<double> q_prof_grad;
     // free-flight query (kernels/vr_query_flight.hip): its own scratch rows (the layouts of ff_scratch and of
     // ff_fb's rows), so a frame queued on another stream never shares them; counters + queue of rays over the rows
     vr::DevBuf<std::byte> q_ff_rows, q_ff_big;

@@ -54,6 +54,15 @@ hipError_t query_sigma_grad(const RenderArgs& A, const float* xyz, const float* 
 hipError_t query_pack_rays(const float* o, const float* d, const float* tmax, uint32_t tmax_stride, uint32_t n, vr_ray* rays,
                            hipStream_t s);
 
+// kernels/vr_query_profile.hip
+// (t: n * K samples with t_stride = K, or K with t_stride = 0; tr / tau: n * K floats, either may be nullptr; n * K < 2^31)
+hipError_t query_transmittance_profile(const RenderArgs& A, const vr_ray* rays, const float* t, uint32_t t_stride, uint32_t n,
+                                       uint32_t K, float* tr, float* tau, uint32_t* next, int refill, int cus, hipStream_t s);
+// (weight: n * K floats or nullptr; acc: 10 doubles per Gaussian of staging, zeroed by the call; grad: 10 floats per Gaussian)
+hipError_t query_transmittance_profile_grad(const RenderArgs& A, const vr_ray* rays, const float* t, uint32_t t_stride,
+                                            const float* weight, uint32_t n, uint32_t K, bool moving, double* acc, float* grad,
+                                            uint32_t* next, int refill, int cus, hipStream_t s);
+
 // kernels/vr_query_flight.hip (the sweep, the solvers and the albedo are the path kernels': kernels/vr_ff_bounce.h)
 // (ctl: query_flight_ctl_words(n) words; A.ff_*: the scratch rows, sized as the free-flight frames size theirs)
 size_t query_flight_ctl_words(uint32_t n);

@@ -1,5 +1,6 @@
-// Mixture queries (vr_query_*, kernels/vr_query.hip, kernels/vr_query_flight.hip): batched transmittance and its
-// gradients with respect to the Gaussians and to the rays, ray events, sigma and its gradient, and free-flight distances.
+// Mixture queries (vr_query_*, kernels/vr_query.hip, kernels/vr_query_profile.hip, kernels/vr_query_flight.hip): batched
+// transmittance and its gradients with respect to the Gaussians and to the rays, transmittance profiles and their
+// gradient, ray events, sigma and its gradient, and free-flight distances.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -33,7 +34,7 @@ vr_status query_begin(vr_ctx* c, const char* what, size_t n, RenderArgs& A) {
     A.num_prims = c->num_prims;
     A.bvh_depth = sd.bvh_depth;
     A.gauss_order = sd.order.get();
-    return c->q_ctl.grow(32, "hipMalloc(query counters)");
+    return c->q_ctl.grow(48, "hipMalloc(query counters)");
 }
 int query_refill(const vr_ctx* c) { return std::clamp<int>(c->auto_nee_refill, 1, 64); }
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
@@ -142,6 +143,111 @@ vr_status vr_query_transmittance_ray_grad(vr_ctx* c, const vr_ray* rays, size_t 
                                                   c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream), "query_ray_grad_kernel");
     HIP_TRY(hipMemcpy(out, c->q_out.get(), n * sizeof(vr_ray_grad), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    return VR_OK;
+}
+
+// ---- transmittance profile: K samples per ray from one walk ----
+namespace {
+
+// The checks of the four profile entry points that precede every launch. `what` names the entry point.
+vr_status profile_check(const char* what, size_t t_stride, size_t n, uint32_t K) {
+    if (K == 0 || K > VR_PROFILE_MAX_SAMPLES)
+        return fail(VR_ERR_INVALID, std::string(what) + ": K must lie in [1, " + std::to_string(VR_PROFILE_MAX_SAMPLES) + "]");
+    if (t_stride != 0 && t_stride != K) return fail(VR_ERR_INVALID, std::string(what) + ": t_stride must be 0 (one shared row) or K");
+    if (n >= (1ull << 31) || n * (size_t)K >= (1ull << 31))
+        return fail(VR_ERR_INVALID, std::string(what) + ": more than 2^31 - 1 samples in one call");
+    return VR_OK;
+}
+
+}  // namespace
+
+vr_status vr_query_transmittance_profile_device(vr_ctx* c, const vr_ray* d_rays, const float* d_t, size_t t_stride, size_t n,
+                                                uint32_t K, float* d_tr, float* d_tau, void* stream) {
+    c = first_device(c);
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_transmittance_profile", n, A));
+    VR_TRY(profile_check("vr_query_transmittance_profile", t_stride, n, K));
+    if (!d_tr && !d_tau) return fail(VR_ERR_INVALID, "vr_query_transmittance_profile: both outputs are NULL");
+    if (n == 0) return VR_OK;
+    if (!d_rays || !d_t) return fail(VR_ERR_INVALID, "vr_query_transmittance_profile: NULL argument");
+    if (!aligned16(d_rays)) return fail(VR_ERR_INVALID, "vr_query_transmittance_profile: the device ray array must be 16-byte aligned");
+    HIP_TRY(query_transmittance_profile(A, d_rays, d_t, (uint32_t)t_stride, (uint32_t)n, K, d_tr, d_tau,
+                                        (uint32_t*)c->q_ctl.get() + 8, query_refill(c), c->cus, (hipStream_t)stream),
+            "query_profile_kernel");
+    return VR_OK;
+}
+
+vr_status vr_query_transmittance_profile(vr_ctx* c, const vr_ray* rays, const float* t, size_t t_stride, size_t n, uint32_t K,
+                                         float* tr, float* tau) {
+    c = first_device(c);
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_transmittance_profile", n, A));
+    VR_TRY(profile_check("vr_query_transmittance_profile", t_stride, n, K));
+    if (!tr && !tau) return fail(VR_ERR_INVALID, "vr_query_transmittance_profile: both outputs are NULL");
+    if (n == 0) return VR_OK;
+    if (!rays || !t) return fail(VR_ERR_INVALID, "vr_query_transmittance_profile: NULL argument");
+    const size_t nk = n * (size_t)K, nt = t_stride ? nk : (size_t)K;
+    VR_TRY(c->q_in.grow(n * sizeof(vr_ray), "hipMalloc(query rays)"));
+    VR_TRY(c->q_prof_t.grow(nt, "hipMalloc(profile samples)"));
+    VR_TRY(c->q_prof_out.grow(2 * nk, "hipMalloc(profile results)"));
+    HIP_TRY(hipMemcpy(c->q_in.get(), rays, n * sizeof(vr_ray), hipMemcpyHostToDevice), "hipMemcpy(query rays)");
+    HIP_TRY(hipMemcpy(c->q_prof_t.get(), t, nt * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(profile samples)");
+    float* d_tr = c->q_prof_out.get();
+    float* d_tau = d_tr + nk;
+    VR_TRY(vr_query_transmittance_profile_device(c, (const vr_ray*)c->q_in.get(), c->q_prof_t.get(), t_stride, n, K,
+                                                 tr ? d_tr : nullptr, tau ? d_tau : nullptr, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream), "query_profile_kernel");
+    if (tr) HIP_TRY(hipMemcpy(tr, d_tr, nk * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(profile results)");
+    if (tau) HIP_TRY(hipMemcpy(tau, d_tau, nk * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(profile results)");
+    return VR_OK;
+}
+
+vr_status vr_query_transmittance_profile_grad_device(vr_ctx* c, const vr_ray* d_rays, const float* d_t, size_t t_stride,
+                                                     const float* d_weight, size_t n, uint32_t K, uint32_t flags, float* d_grad,
+                                                     void* stream) {
+    c = first_device(c);
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_transmittance_profile_grad", n, A));
+    VR_TRY(profile_check("vr_query_transmittance_profile_grad", t_stride, n, K));
+    if (flags & ~(uint32_t)VR_GRAD_FROZEN_BOUNDS) return fail(VR_ERR_INVALID, "vr_query_transmittance_profile_grad: unknown flag bits");
+    if (!d_grad || (n > 0 && (!d_rays || !d_t))) return fail(VR_ERR_INVALID, "vr_query_transmittance_profile_grad: NULL argument");
+    if (!aligned16(d_rays))
+        return fail(VR_ERR_INVALID, "vr_query_transmittance_profile_grad: the device ray array must be 16-byte aligned");
+    // the staging rows are this query's own: a frame or another gradient query queued on another stream never sees them
+    VR_TRY(c->q_prof_grad.grow((size_t)std::max(A.num_prims, 1) * 10, "hipMalloc(gradient staging)"));
+    HIP_TRY(query_transmittance_profile_grad(A, d_rays, d_t, (uint32_t)t_stride, d_weight, (uint32_t)n, K,
+                                             !(flags & VR_GRAD_FROZEN_BOUNDS), c->q_prof_grad.get(), d_grad,
+                                             (uint32_t*)c->q_ctl.get() + 9, query_refill(c), c->cus, (hipStream_t)stream),
+            "query_profile_grad_kernel");
+    return VR_OK;
+}
+
+vr_status vr_query_transmittance_profile_grad(vr_ctx* c, const vr_ray* rays, const float* t, size_t t_stride, const float* weight,
+                                              size_t n, uint32_t K, uint32_t flags, float* grad) {
+    c = first_device(c);
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_transmittance_profile_grad", n, A));
+    VR_TRY(profile_check("vr_query_transmittance_profile_grad", t_stride, n, K));
+    if (flags & ~(uint32_t)VR_GRAD_FROZEN_BOUNDS) return fail(VR_ERR_INVALID, "vr_query_transmittance_profile_grad: unknown flag bits");
+    if (!grad || (n > 0 && (!rays || !t))) return fail(VR_ERR_INVALID, "vr_query_transmittance_profile_grad: NULL argument");
+    const size_t words = (size_t)std::max(A.num_prims, 0) * 10;
+    if (n == 0 || words == 0) {
+        std::memset(grad, 0, words * sizeof(float));
+        return VR_OK;
+    }
+    const size_t nk = n * (size_t)K, nt = t_stride ? nk : (size_t)K;
+    VR_TRY(c->q_in.grow(n * sizeof(vr_ray), "hipMalloc(query rays)"));
+    VR_TRY(c->q_prof_t.grow(nt, "hipMalloc(profile samples)"));
+    if (weight) VR_TRY(c->q_prof_w.grow(nk, "hipMalloc(profile weights)"));
+    VR_TRY(c->q_prof_out.grow(words, "hipMalloc(profile results)"));
+    HIP_TRY(hipMemcpy(c->q_in.get(), rays, n * sizeof(vr_ray), hipMemcpyHostToDevice), "hipMemcpy(query rays)");
+    HIP_TRY(hipMemcpy(c->q_prof_t.get(), t, nt * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(profile samples)");
+    if (weight) HIP_TRY(hipMemcpy(c->q_prof_w.get(), weight, nk * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(profile weights)");
+    VR_TRY(vr_query_transmittance_profile_grad_device(c, (const vr_ray*)c->q_in.get(), c->q_prof_t.get(), t_stride,
+                                                      weight ? c->q_prof_w.get() : nullptr, n, K, flags, c->q_prof_out.get(),
+                                                      c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream), "query_profile_grad_kernel");
+    HIP_TRY(hipMemcpy(grad, c->q_prof_out.get(), words * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(profile results)");
     return VR_OK;
 }
 

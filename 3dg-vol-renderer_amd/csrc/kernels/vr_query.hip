@@ -22,59 +22,17 @@
 // Ray walks (transmittance, events) are operations on the persistent ray-queue walk the shadow-ray kernel
 // uses too (ray_queue_walk, vr_walk.h): a walk whose LDS stack could overflow, and every walk of a scene without
 // the 4-wide tree (VR_OPT_HALF_NODES = 0, or boxes too small for f16), is redone on the child-pair tree at the
-// ray's completion.
+// ray's completion. The walk's block shape and the operations' base (QueryOp, query_walk) are in vr_query_common.h,
+// which vr_query_profile.hip shares.
 #include <hipcub/hipcub.hpp>
 #include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 
-#include "vr_dev_common.h"
-#include "vr_walk.h"
+#include "vr_query_common.h"
 
 namespace vr {
 namespace dev {
-
-constexpr int kQBlock = 256;
-#ifndef VR_QUERY_BLOCKS
-#define VR_QUERY_BLOCKS 4  // resident 256-lane blocks per CU (40 KB of LDS each: 4 waves per SIMD)
-#endif
-constexpr int kQQueue = 8, kQSteps = 4;  // leaf FIFO entries; node steps / Gaussians per lane per wave iteration
-
-// ---- per-ray operations of the walk (ray_queue_walk's Op) ----
-// What the three share. vr_ray row i (32 B, 16-B aligned): {origin, tmax}, {direction, unit}. The direction is
-// normalised as the Ray constructor does (make_ray, ray.h:11-12) unless `unit` says it already was (a Ray
-// object's: normalising twice would move it by an ulp). Invalid: a non-finite origin, or a direction whose
-// squared norm is 0, NaN or infinite. PRUNE: rays with tmax <= 0 / NaN finish at once.
-template <class Op, bool PRUNE>
-struct QueryOp {
-    static constexpr bool kPrune = PRUNE;
-    const vr_ray* __restrict__ rays;
-    __device__ __forceinline__ int load(const RenderArgs& A, uint32_t id, Ray& r, float& tmax) {
-        const float4* p = reinterpret_cast<const float4*>(rays) + 2 * (size_t)id;
-        const float4 a = p[0], b = p[1];
-        tmax = a.w;
-        const float s = dot3(b.x, b.y, b.z, b.x, b.y, b.z);
-        const bool ok = isfinite(a.x) && isfinite(a.y) && isfinite(a.z) && s > 0.0f && isfinite(s);
-        r = b.w != 0.0f ? Ray{a.x, a.y, a.z, b.x, b.y, b.z} : make_ray(a.x, a.y, a.z, b.x, b.y, b.z);
-        if (!ok) return kRayInvalid;
-        return (PRUNE && !(tmax > 0.0f)) || A.num_prims <= 0 ? kRayFinish : kRayWalk;  // gmm.h:518-519 / :462: no walk
-    }
-    __device__ __forceinline__ void on_node() {}
-    // The whole walk of the ray on the child-pair tree (half-precision nodes if the scene has them), and its result.
-    __device__ __forceinline__ void redo(const RenderArgs& A, uint32_t id, const Ray& r, float tmax, float lim, int* stack) {
-        Op& op = static_cast<Op&>(*this);
-        op.reset();
-        auto prune = [&](float tmin, float) { return !PRUNE || tmin <= lim; };
-        auto leaf = [&](uint32_t first, uint32_t count) {
-            for (uint32_t j = first; j < first + count; ++j)
-                if (!op.prim(A, r, tmax, j)) return false;
-            return true;
-        };
-        if (A.hnodes) traverse<true>(A, r, stack, kQBlock, prune, leaf);
-        else traverse<false>(A, r, stack, kQBlock, prune, leaf);
-        op.finish(A, id, tmax);
-    }
-};
 
 // gmm.h:539-551: a = max(0, t_enter), b = min(tmax, t_exit), optical_depth(a, b) added if b > a.
 // TAU: the caller wants the optical depth itself, so the sum runs to the end; otherwise it stops at 104,
@@ -378,14 +336,6 @@ struct RayGradOp : QueryOp<RayGradOp, true> {
         p[0] = p[1] = make_float4(q, q, q, q);
     }
 };
-
-// One block of the persistent grid: its LDS stack and leaf FIFO, then the walk.
-template <class Op>
-__device__ __forceinline__ void query_walk(const RenderArgs& A, uint32_t n, uint32_t* next, int refill, Op& op) {
-    __shared__ int s_stack[(kStackSize + kQQueue) * kQBlock];
-    int* stack = s_stack + threadIdx.x;
-    ray_queue_walk<kQQueue, kQSteps>(A, n, next, refill, stack, stack + kStackSize * kQBlock, kQBlock, op);
-}
 
 template <bool TAU>
 __global__ void __launch_bounds__(kQBlock) query_transmittance_kernel(RenderArgs A, const vr_ray* __restrict__ rays, uint32_t n,
@@ -834,8 +784,6 @@ struct ToU64 {
 }  // namespace dev
 
 // ---- launchers (host/vr_device.cpp) ----
-static inline dim3 query_grid(int cus) { return dim3((unsigned)std::max(1, cus) * VR_QUERY_BLOCKS); }
-
 hipError_t query_transmittance(const RenderArgs& A, const vr_ray* rays, uint32_t n, float* tr, float* tau, uint32_t* next,
                                int refill, int cus, hipStream_t s) {
     hipError_t e = hipMemsetAsync(next, 0, sizeof(uint32_t), s);

@@ -87,6 +87,41 @@ public:
         return out;
     }
 
+    // transmittance_up_to at K distances along every ray from one tree walk per ray (vr_query_transmittance_profile):
+    // the result holds Tr row-major, rays.size() * K floats, *tau (if given) the optical depths. `t` holds K distances
+    // shared by all rays, or rays.size() * K, row i for ray i, in any order; entry (i, k) has the bits of
+    // transmittance_up_to(ray i, t[i][k]).
+    std::vector<float> transmittance_profile(const std::vector<Ray>& rays, const std::vector<float>& t, uint32_t K,
+                                             std::vector<float>* tau = nullptr) const {
+        const size_t stride = profile_stride("transmittance_profile", rays.size(), t.size(), K);
+        vr_ctx* ctx = ready();
+        const std::vector<vr_ray> r = pack(rays, nullptr, std::numeric_limits<float>::infinity());
+        std::vector<float> tr(r.size() * K);
+        if (tau) tau->assign(r.size() * K, 0.0f);
+        vr_cpp::check(vr_query_transmittance_profile(ctx, r.data(), t.data(), stride, r.size(), K, tr.data(),
+                                                     tau ? tau->data() : nullptr));
+        return tr;
+    }
+
+    // The gradient of a weighted sum of that profile's optical depths with respect to the Gaussians
+    // (vr_query_transmittance_profile_grad): row g of the result (10 floats per scene Gaussian, transmittance_gradient's
+    // layout) is sum_i sum_k weights[i * K + k] * d tau[i][k] / d theta_g; an empty `weights` means 1 for every sample.
+    // One walk per ray and ten atomic adds per (ray, Gaussian) hit, whatever K is.
+    std::vector<float> transmittance_profile_gradient(const std::vector<Ray>& rays, const std::vector<float>& t, uint32_t K,
+                                                      const std::vector<float>& weights = {}, bool moving_bounds = true) const {
+        const size_t stride = profile_stride("transmittance_profile_gradient", rays.size(), t.size(), K);
+        if (!weights.empty() && weights.size() != rays.size() * K)
+            throw std::runtime_error("transmittance_profile_gradient: one weight per ray and sample");
+        vr_ctx* ctx = ready();
+        const std::vector<vr_ray> r = pack(rays, nullptr, std::numeric_limits<float>::infinity());
+        std::vector<float> grad(10 * scene_.get_num_primitives() + 1, 0.0f);  // (+ 1: never a NULL pointer)
+        vr_cpp::check(vr_query_transmittance_profile_grad(ctx, r.data(), t.data(), stride, weights.empty() ? nullptr : weights.data(),
+                                                          r.size(), K, moving_bounds ? 0u : (uint32_t)VR_GRAD_FROZEN_BOUNDS,
+                                                          grad.data()));
+        grad.pop_back();
+        return grad;
+    }
+
     // gmm.h:457-515 intersect_events(ray, events) per ray: sorted by t; events with equal t in scene order,
     // entry before exit (not the order the reference's std::sort happens to leave).
     std::vector<std::vector<PrimitiveHitEvent>> intersect_events(const std::vector<Ray>& rays) const {
@@ -162,6 +197,13 @@ public:
     }
 
 private:
+    // t of size K is one row shared by all rays (stride 0), of size n * K a row per ray (stride K).
+    static size_t profile_stride(const char* what, size_t n, size_t nt, uint32_t K) {
+        if (K == 0) throw std::runtime_error(std::string(what) + ": K must be positive");
+        if (nt == n * K) return K;
+        if (nt == K) return 0;
+        throw std::runtime_error(std::string(what) + ": t holds K distances, or K per ray");
+    }
     std::vector<float> transmittance(const std::vector<vr_ray>& r, std::vector<float>* tau) const {
         vr_ctx* ctx = ready();
         std::vector<float> tr(r.size());

@@ -628,6 +628,70 @@ class Device:
             check(lib().vr_query_transmittance_ray_grad(self._h, rays.ctypes.data, n, flags, out.ctypes.data))
         return out[:, 0:3], out[:, 4:7], out[:, 3], out[:, 7]
 
+    def query_transmittance_profile(self, scene, origins, directions, t, return_tau=False):
+        """Transmittance at K distances along each of n rays from one tree walk per ray
+        (vr_query_transmittance_profile): origins, directions (n, 3) float32; t float32 of shape (K,), one row of
+        distances shared by all rays, or (n, K), of the same kind (numpy or torch) as the rays. Returns Tr (n, K), or
+        (Tr, tau). Column k has the bits of query_transmittance(..., tmax=t[:, k], return_tau=True). Samples may come
+        in any order; a sample <= 0 or NaN gives tau = 0, Tr = 1, an invalid ray NaN in its whole row."""
+        torch_in = _query_ray_args(origins, directions, 0.0)
+        n = origins.shape[0]
+        K, stride = _query_profile_args(t, "t", n, torch_in, shared_ok=True)
+        self.upload(scene)
+        if torch_in:
+            import torch
+            self._check_torch(origins, directions, t)
+            rays, stream = self._pack_rays_torch(origins, directions, float("inf"))
+            ts = t.contiguous()
+            tr = torch.empty((n, K), dtype=torch.float32, device=origins.device)
+            tau = torch.empty((n, K), dtype=torch.float32, device=origins.device) if return_tau else None
+            check(lib().vr_query_transmittance_profile_device(self._h, rays.data_ptr(), ts.data_ptr(), stride, n, K, tr.data_ptr(),
+                                                              tau.data_ptr() if return_tau else None, stream))
+        else:
+            rays = self._pack_rays_numpy(origins, directions, np.inf)
+            ts = np.ascontiguousarray(t)
+            tr = np.empty((n, K), np.float32)
+            tau = np.empty((n, K), np.float32) if return_tau else None
+            check(lib().vr_query_transmittance_profile(self._h, rays.ctypes.data, fptr(ts), stride, n, K, fptr(tr),
+                                                       fptr(tau) if return_tau else None))
+        return (tr, tau) if return_tau else tr
+
+    def query_transmittance_profile_grad(self, scene, origins, directions, t, weights=None, moving_bounds=True):
+        """The gradient of a weighted sum of a profile's optical depths with respect to the Gaussians
+        (vr_query_transmittance_profile_grad): for the rays and distances of query_transmittance_profile and weights
+        (n, K) float32 (None: all 1), the (N, 10) float32 array sum_i sum_k weights[i, k] * d tau[i, k] / d (mean[3],
+        cov6, density), in query_transmittance_grad's layout and with its moving_bounds. One walk per ray and ten
+        atomic adds per (ray, Gaussian) hit whatever K is; equal to query_transmittance_grad on the n * K expanded rays
+        up to the rounding of double sums."""
+        torch_in = _query_ray_args(origins, directions, 0.0)
+        n = origins.shape[0]
+        K, stride = _query_profile_args(t, "t", n, torch_in, shared_ok=True)
+        if weights is not None and _query_profile_args(weights, "weights", n, torch_in, shared_ok=False)[0] != K:
+            raise ValueError(f"weights has {weights.shape[1]} columns for {K} samples")
+        self.upload(scene)
+        N = scene.get_num_primitives()
+        flags = 0 if moving_bounds else L.VR_GRAD_FROZEN_BOUNDS
+        if N == 0:
+            return origins.new_zeros((0, 10)) if torch_in else np.zeros((0, 10), np.float32)
+        if torch_in:
+            import torch
+            self._check_torch(origins, directions, t, *([] if weights is None else [weights]))
+            rays, stream = self._pack_rays_torch(origins, directions, float("inf"))
+            ts = t.contiguous()
+            wt = None if weights is None else weights.contiguous()
+            grad = torch.empty((N, 10), dtype=torch.float32, device=origins.device)
+            check(lib().vr_query_transmittance_profile_grad_device(self._h, rays.data_ptr(), ts.data_ptr(), stride,
+                                                                   None if wt is None else wt.data_ptr(), n, K, flags,
+                                                                   grad.data_ptr(), stream))
+        else:
+            rays = self._pack_rays_numpy(origins, directions, np.inf)
+            ts = np.ascontiguousarray(t)
+            wt = None if weights is None else np.ascontiguousarray(weights)
+            grad = np.empty((N, 10), np.float32)
+            check(lib().vr_query_transmittance_profile_grad(self._h, rays.ctypes.data, fptr(ts), stride,
+                                                            None if wt is None else fptr(wt), n, K, flags, fptr(grad)))
+        return grad
+
     def query_sigma(self, scene, points, return_active=False):
         """GaussianMixtureModel::evaluate_sigma (gmm.h:98-126) at n points (n, 3) float32, over the Gaussians
         whose 3-sigma ellipsoid holds the point. Returns sigma (n, 2) = (sigma_a, sigma_s), or (sigma,
@@ -864,6 +928,25 @@ def _query_ray_args(origins, directions, tmax):
         except (TypeError, ValueError):
             raise ValueError(f"tmax must be a number or a float32 array, not {type(tmax).__name__}") from None
     return t_o
+
+
+def _query_profile_args(x, name, n, torch_in, shared_ok):
+    """Checks a profile's samples or weights before anything reaches the library: float32, (n, K), or (K,) where one row
+    may be shared, 1 <= K <= VR_PROFILE_MAX_SAMPLES, of the rays' kind. Returns (K, the row stride: K or 0)."""
+    shape = tuple(getattr(x, "shape", ()))
+    shared = shared_ok and len(shape) == 1
+    if not shared and len(shape) != 2:
+        raise ValueError(f"{name} must have shape {'(K,) or ' if shared_ok else ''}(n, K), not {shape}")
+    K = shape[-1]
+    if _query_f32(x, name, () if shared else (K,)) != torch_in:
+        raise ValueError(f"{name} must be of the same kind as origins")
+    if not shared and shape[0] != n:
+        raise ValueError(f"{name} has {shape[0]} rows for {n} rays")
+    if not 1 <= K <= L.VR_PROFILE_MAX_SAMPLES:
+        raise ValueError(f"{name} has {K} samples per ray: 1 to {L.VR_PROFILE_MAX_SAMPLES} are allowed")
+    if n * K >= 2 ** 31:
+        raise ValueError(f"{n} rays of {K} samples: more than 2^31 - 1 samples in one call")
+    return K, 0 if shared else K
 
 
 def _query_point_args(points):

@@ -28,7 +28,8 @@ VR_OPT_SEC_TIGHT = 11
 VR_OPT_MARCH_WIDE_MIN = 12
 VR_OPT_FF_KERNEL = 13
 VR_OPT_SEC_FILTER = 14
-VR_GRAD_FROZEN_BOUNDS = 1  # vr_query_transmittance_grad / _ray_grad flags
+VR_GRAD_FROZEN_BOUNDS = 1  # vr_query_transmittance_grad / _ray_grad / _profile_grad flags
+VR_PROFILE_MAX_SAMPLES = 1024  # vr_query_transmittance_profile: the most samples per ray
 
 f3 = ctypes.c_float * 3
 
@@ -188,6 +189,12 @@ SIGNATURES = {
     "vr_query_transmittance_grad_device": (ST, [P, P, P, ctypes.c_size_t, ctypes.c_uint32, P, P]),
     "vr_query_transmittance_ray_grad": (ST, [P, P, ctypes.c_size_t, ctypes.c_uint32, P]),
     "vr_query_transmittance_ray_grad_device": (ST, [P, P, ctypes.c_size_t, ctypes.c_uint32, P, P]),
+    "vr_query_transmittance_profile": (ST, [P, P, FP, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, FP, FP]),
+    "vr_query_transmittance_profile_device": (ST, [P, P, P, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, P, P, P]),
+    "vr_query_transmittance_profile_grad": (ST, [P, P, FP, ctypes.c_size_t, FP, ctypes.c_size_t, ctypes.c_uint32,
+                                                 ctypes.c_uint32, FP]),
+    "vr_query_transmittance_profile_grad_device": (ST, [P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, ctypes.c_uint32,
+                                                        ctypes.c_uint32, P, P]),
     "vr_query_sigma": (ST, [P, FP, ctypes.c_size_t, FP, U32P]),
     "vr_query_sigma_device": (ST, [P, P, ctypes.c_size_t, P, P, P]),
     "vr_query_sigma_grad": (ST, [P, FP, FP, ctypes.c_size_t, FP, FP]),

@@ -24,6 +24,17 @@ not differentiable a second time. The optical depth does not depend on albedo, s
 (sigma, below, does). When no ray input requires grad, forward and backward issue the calls they issue for the
 Gaussians alone.
 
+The optical depth at K distances along each ray (Device.query_transmittance_profile /
+Device.query_transmittance_profile_grad): one tree walk per ray in forward, one in backward, whatever K is.
+
+    tau = optical_depth_profile(mean, cov6, density, albedo, origins, directions, t)   # (n, K); t is (K,) or (n, K)
+    T = torch.exp(-torch.cat([torch.zeros_like(tau[:, :1]), tau], 1))                   # emission-absorption quadrature:
+    rgb = ((T[:, :-1] - T[:, 1:])[..., None] * colour).sum(1)                           # sum_k (T_k - T_k+1) c_k
+    loss.backward()                                                                     # mean.grad, cov6.grad, density.grad
+
+optical_depth_profile_resident is the same for parameters on the rays' device. Backward is one profile-gradient call
+with grad_output as the (n, K) weights; origins, directions, t and albedo get no gradient.
+
 The extinction field itself, at the caller's points (Device.query_sigma / Device.query_sigma_grad):
 
     sig = sigma(mean, cov6, density, albedo, points)                             # (n, 2) = (sigma_a, sigma_s)
@@ -113,6 +124,59 @@ def optical_depth_resident(mean, cov6, density, albedo, origins, directions, tma
     device (ValueError otherwise), and forward uploads them with Device.upload_gaussians instead of copying them to
     the host. Same arguments, same gradients."""
     return _OpticalDepth.apply(mean, cov6, density, albedo, origins, directions, tmax, device, moving_bounds, True)
+
+
+class _OpticalDepthProfile(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mean, cov6, density, albedo, origins, directions, t, device, moving_bounds, resident):
+        if resident:
+            for p, name in ((mean, "mean"), (cov6, "cov6"), (density, "density"), (albedo, "albedo")):
+                if p.device != origins.device:
+                    raise ValueError(f"{name} is on {p.device}, the rays on {origins.device}: a resident scene's "
+                                     "parameters live on the rays' device")
+        dev = Device.get(device)
+        if resident:
+            scene = dev.upload_gaussians(*(p.detach().to(torch.float32).contiguous() for p in (mean, cov6, density, albedo)))
+        else:
+            host = [p.detach().to("cpu", torch.float32).contiguous().numpy() for p in (mean, cov6, density, albedo)]
+            scene = Scene.from_gaussians(*host)
+        o, d, ts = origins.detach().contiguous(), directions.detach().contiguous(), t.detach().contiguous()
+        _, tau = dev.query_transmittance_profile(scene, o, d, ts, return_tau=True)
+        ctx.dev, ctx.scene, ctx.rays, ctx.moving = dev, scene, (o, d, ts), bool(moving_bounds)
+        ctx.like = (mean, cov6, density)
+        return tau
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_tau):
+        o, d, ts = ctx.rays
+        out = (None,) * 3
+        if any(ctx.needs_input_grad[:3]):
+            g = ctx.dev.query_transmittance_profile_grad(ctx.scene, o, d, ts, grad_tau.to(torch.float32).contiguous(),
+                                                         moving_bounds=ctx.moving)
+            mean, cov6, density = ctx.like
+            out = (g[:, 0:3].reshape(mean.shape), g[:, 3:9].reshape(cov6.shape), g[:, 9].reshape(density.shape))
+            out = tuple(x.to(device=p.device, dtype=p.dtype) if need else None
+                        for x, p, need in zip(out, ctx.like, ctx.needs_input_grad[:3]))
+        return out + (None,) * 7
+
+
+def optical_depth_profile(mean, cov6, density, albedo, origins, directions, t, device=0, moving_bounds=True):
+    """tau (n, K) float32: the optical depth at the distances t ((K,) shared by all rays, or (n, K); a float32 tensor on
+    cuda:`device`, in any order) along rays (origins, directions: (n, 3) float32 tensors there) through the mixture of
+    Gaussians mean (N, 3), cov6 (N, 6) [xx xy xz yy yz zz], density (N,), albedo (N,) (tensors on any device). Column k
+    has the bits of optical_depth(..., tmax=t[:, k]). Differentiable with respect to mean, cov6 and density: backward
+    is one Device.query_transmittance_profile_grad call with grad_output as the weights. origins, directions, t and
+    albedo get None (the profile's gradient with respect to the rays and the distances is not computed).
+    moving_bounds=False differentiates with each Gaussian's 3-sigma entry / exit distances held fixed."""
+    return _OpticalDepthProfile.apply(mean, cov6, density, albedo, origins, directions, t, device, moving_bounds, False)
+
+
+def optical_depth_profile_resident(mean, cov6, density, albedo, origins, directions, t, device=0, moving_bounds=True):
+    """optical_depth_profile for parameters that never leave the GPU: mean, cov6, density and albedo must be on the
+    rays' device (ValueError otherwise), and forward uploads them with Device.upload_gaussians instead of copying them
+    to the host. Same arguments, same gradients; origins, directions, t and albedo get None."""
+    return _OpticalDepthProfile.apply(mean, cov6, density, albedo, origins, directions, t, device, moving_bounds, True)
 
 
 class _Sigma(torch.autograd.Function):

@@ -614,6 +614,47 @@ vr_status vr_query_transmittance_ray_grad(vr_ctx* ctx, const vr_ray* rays, size_
 vr_status vr_query_transmittance_ray_grad_device(vr_ctx* ctx, const vr_ray* d_rays, size_t n, uint32_t flags,
                                                  vr_ray_grad* d_out, void* stream);
 
+/* The transmittance profile: tau and Tr at K distances along each ray, from one tree walk per ray instead of K.
+ * t holds the distances: n * K floats, row i for ray i, with t_stride = K, or one row of K shared by all rays with
+ * t_stride = 0 (any other t_stride: VR_ERR_INVALID). tr and tau are n * K floats, row-major; either may be NULL, not
+ * both (VR_ERR_INVALID).
+ *   tau[i][k] and tr[i][k] are, bit for bit, what vr_query_transmittance returns for ray i with tmax = t[i][k].
+ * So a sample <= 0 or NaN gives tau = 0, tr = 1; +inf is valid; an invalid ray (that query's rule) gets NaN in its whole
+ * row; `unit` means what it means there; the row's own tmax field is not read. Samples may come in any order and may
+ * repeat. Results do not depend on VR_OPT_HALF_NODES / VR_OPT_DEVICE_BVH (the sums are that query's double sums).
+ * How: of optical_depth(a, b) only erf at the upper bound depends on b, so a hit's other factors are computed once for
+ * all samples. The walk's work item is (ray, chunk of samples) and is pruned at the chunk's largest sample (NaN
+ * ignored; no sample > 0: no walk), so with ascending samples the early chunks walk a shorter ray.
+ * K == 0, K > VR_PROFILE_MAX_SAMPLES or n * K >= 2^31: VR_ERR_INVALID before anything is launched; a sphere scene:
+ * VR_ERR_UNSUPPORTED; the common errors above apply. */
+#define VR_PROFILE_MAX_SAMPLES 1024
+vr_status vr_query_transmittance_profile(vr_ctx* ctx, const vr_ray* rays, const float* t, size_t t_stride, size_t n,
+                                         uint32_t K, float* tr, float* tau);
+vr_status vr_query_transmittance_profile_device(vr_ctx* ctx, const vr_ray* d_rays, const float* d_t, size_t t_stride,
+                                                size_t n, uint32_t K, float* d_tr, float* d_tau, void* stream);
+
+/* The gradient of a weighted sum of a profile's optical depths with respect to the Gaussians:
+ *   grad[10 g + c] = sum_i sum_k weight[i][k] * d tau[i][k] / d theta_{g,c}
+ * in the layout, with the flags (VR_GRAD_FROZEN_BOUNDS), the per-hit double arithmetic and the f32 decisions of
+ * vr_query_transmittance_grad: it equals the gradient that query returns for the n * K rays (ray i, tmax = t[i][k],
+ * weight[i][k]) up to the rounding of double sums. weight is n * K floats, row-major, or NULL (all ones). Samples <= 0 or
+ * NaN and invalid rays contribute nothing. Every entry of grad is written; n == 0 zeroes it. grad == NULL, unknown flag
+ * bits and the profile's argument errors: VR_ERR_INVALID.
+ * Folding rule. One walk per ray; per (ray, Gaussian) hit, with a = max(0, t_enter), t1 = t_exit (f32) and the head of
+ * vr_query_transmittance_grad (p, A, B, C, m, c, k, u_a) computed once, the K samples fall into three classes:
+ *   t_k <= a, or not > 0:  nothing;
+ *   t_k >= t1:             the whole chord, W_full += w_k;
+ *   a < t_k < t1:          (S0, S1, S2) += w_k (J0, J1, J2) over [u_a, t_k - m], W_in += w_k;
+ * then once (S0, S1, S2) += W_full (J0, J1, J2) over [u_a, t1 - m]. The hit's ten numbers are that query's with
+ * (S0, S1, S2) for (J0, J1, J2) and weight 1; the exit's moving-bound term (t_exit <= t_k, the second class) carries
+ * W_full, the entry's (t_enter > 0) carries W_full + W_in. So a hit costs ten atomic adds whatever K is.
+ * The staging (80 bytes per Gaussian) is this query's own and is zeroed on `stream` by each call. */
+vr_status vr_query_transmittance_profile_grad(vr_ctx* ctx, const vr_ray* rays, const float* t, size_t t_stride,
+                                              const float* weight, size_t n, uint32_t K, uint32_t flags, float* grad);
+vr_status vr_query_transmittance_profile_grad_device(vr_ctx* ctx, const vr_ray* d_rays, const float* d_t, size_t t_stride,
+                                                     const float* d_weight, size_t n, uint32_t K, uint32_t flags,
+                                                     float* d_grad, void* stream);
+
 /* GaussianMixtureModel::evaluate_sigma (gmm.h:98-126) at n points xyz[3n], with `active` = the Gaussians
  * whose 3-sigma ellipsoid holds the point (p.(M p) - 9 <= 0 in f32, p = x - mean: the sign of
  * intersect_direct's C, gaussian.h:136, for a ray starting there), the set the integrators pass.

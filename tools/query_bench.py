@@ -6,7 +6,7 @@ rays packed on the device), every query is warmed up, and the figure is the medi
 events on torch's current stream. Prints one JSON line and, with --out, writes it to a file.
 
     python tools/query_bench.py [--gaussians 1000000] [--rays 4194304] [--points 4194304] [--repeats 5] [--out F]
-                                [--flight-scene FILE] [--only all|mixture|flight|grad|raygrad|upload|sigmagrad]
+                                [--flight-scene FILE] [--only all|mixture|flight|grad|raygrad|upload|sigmagrad|profile]
 
 --only grad times the optical-depth gradient query (Device.query_transmittance_grad, unit weights, moving and frozen
 bounds) beside the tau query on the same rays, on --flight-scene and on the make_random scene (--gaussians 0 skips it).
@@ -15,6 +15,11 @@ with unit=True on the same stored directions).
 --only sigmagrad times the sigma gradient query (Device.query_sigma_grad, weights None: both outputs, positions only,
 Gaussians only) beside query_sigma on the same points, on a make_random scene of --gaussians Gaussians: --points points,
 point i in or just outside Gaussian i mod N (mean + chol(cov) r u, u a uniform direction, r uniform in [0, 3.3]).
+--only profile times the transmittance profile (Device.query_transmittance_profile, --profile-k samples per ray, ascending
+through the cloud, a row per ray) beside K calls of the tau query on the same rays, and its gradient
+(Device.query_transmittance_profile_grad, unit weights) beside the gradient query on the n K expanded rays, on
+--flight-scene and on the make_random scene (--gaussians 0 skips it); --profile-forward-only leaves the gradients out.
+Each comparison reports the existing query's own spread over the repeats: a difference counts from three times that.
 --only upload times getting a scene whose parameters live in torch tensors on the GPU onto the device, on --flight-scene
 and on make_random scenes of 100 000 and --gaussians Gaussians: (a) a copy to the host, Scene.from_gaussians and
 Device.upload with the host builder, (b) the same with device_bvh = 1, (c) Device.upload_gaussians. A host clock
@@ -63,7 +68,10 @@ def main():
     ap.add_argument("--seed", type=int, default=2025)
     ap.add_argument("--out", default=None)
     ap.add_argument("--flight-scene", default=os.path.join(ROOT, "tests", "golden", "scenes", "1000_random.txt"))
-    ap.add_argument("--only", choices=("all", "mixture", "flight", "grad", "raygrad", "upload", "sigmagrad"), default="all")
+    ap.add_argument("--only", choices=("all", "mixture", "flight", "grad", "raygrad", "upload", "sigmagrad", "profile"),
+                    default="all")
+    ap.add_argument("--profile-k", default="8,64", help="samples per ray of --only profile, comma-separated")
+    ap.add_argument("--profile-forward-only", action="store_true")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -95,6 +103,9 @@ def main():
     if args.only == "sigmagrad":
         res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
         res.update(sigmagrad(args, dev, timed))
+    if args.only == "profile":
+        res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
+        res.update(profile(args, dev, o, d, timed))
     if args.only == "upload":
         res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
         res.update(upload(args, dev, o, d))
@@ -127,6 +138,50 @@ def grad(args, dev, o, d, timed):
                     "gaussians_hit": int((g[:, 9] != 0).sum()), "mean_tau": float(tau[1].mean()),
                     "all_ms": {"tau": tau_all, "grad": g_all, "grad_frozen": f_all}})
     return {"grad": out, "timing": "median of HIP-event intervals on torch's current stream, inputs on the device"}
+
+
+def profile(args, dev, o, d, timed):
+    """The profile against K calls of the tau query, and its gradient against the gradient query on the expanded rays."""
+    import torch
+    scenes = [(os.path.basename(args.flight_scene), vr.Scene.load_GMM(args.flight_scene))]
+    if args.gaussians > 0:
+        big = vr.Scene(vr.Scene.GAUSSIANS)
+        big.add_random_gaussians(args.gaussians, seed=args.seed, variant=0)
+        scenes.append((f"make_random_{args.gaussians}", big))
+    n = o.shape[0]
+    out = []
+    for name, scene in scenes:
+        info = scene.info()
+        lo, hi = np.array(list(info.bounds_min), np.float64), np.array(list(info.bounds_max), np.float64)
+        dist, rad = float(np.linalg.norm(0.5 * (lo + hi) - CAM_POS)), 0.5 * float(np.linalg.norm(hi - lo))
+        dev.upload(scene)
+        for K in (int(k) for k in args.profile_k.split(",")):
+            row = np.linspace(max(dist - rad, 0.0), dist + rad, K + 1)[1:].astype(np.float32)  # ascending, through the cloud
+            t = torch.tensor(np.tile(row, (n, 1))).cuda()
+            cols = [t[:, k].contiguous() for k in range(K)]
+            s_ms, s_all, single = timed(lambda: [dev.query_transmittance(scene, o, d, tmax=c, return_tau=True)[1] for c in cols])
+            p_ms, p_all, prof = timed(lambda: dev.query_transmittance_profile(scene, o, d, t, return_tau=True))
+            same = bool((torch.stack(single, 1).view(torch.int32) == prof[1].view(torch.int32)).all())
+            spread = max(s_all) - min(s_all)
+            r = {"scene": name, "gaussians": scene.get_num_primitives(), "K": K, "t_first": float(row[0]), "t_last": float(row[-1]),
+                 "single_x_K_ms": s_ms, "profile_ms": p_ms, "single_over_profile": s_ms / p_ms, "single_spread_ms": spread,
+                 "profile_not_slower": bool(p_ms <= s_ms + 3.0 * spread), "tau_same_bits": same,
+                 "mean_tau_last": float(prof[1][:, -1].mean()), "all_ms": {"single_x_K": s_all, "profile": p_all}}
+            if not args.profile_forward_only:
+                eo, ed, et = o.repeat_interleave(K, 0), d.repeat_interleave(K, 0), t.reshape(-1).contiguous()
+                e_ms, e_all, ge = timed(lambda: dev.query_transmittance_grad(scene, eo, ed, None, tmax=et))
+                del eo, ed, et
+                g_ms, g_all, gp = timed(lambda: dev.query_transmittance_profile_grad(scene, o, d, t))
+                gspread = max(e_all) - min(e_all)
+                scale = float(ge.abs().max())
+                r.update({"expanded_grad_ms": e_ms, "profile_grad_ms": g_ms, "expanded_over_profile_grad": e_ms / g_ms,
+                          "expanded_grad_spread_ms": gspread, "profile_grad_not_slower": bool(g_ms <= e_ms + 3.0 * gspread),
+                          "grad_max_abs_difference_over_max": float((ge - gp).abs().max()) / scale if scale > 0 else 0.0})
+                r["all_ms"].update({"expanded_grad": e_all, "profile_grad": g_all})
+            out.append(r)
+    return {"profile": out, "library": os.path.basename(vr._lib.LIB_PATH),
+            "timing": "median of HIP-event intervals on torch's current stream after the warm-up, inputs on the device; "
+                      "spread = max - min of the existing query's intervals, a difference counts from 3 spreads"}
 
 
 def sigmagrad(args, dev, timed):

@@ -30,6 +30,10 @@
 // --query-sigma-grad RAYS.bin (the same file) prints MixtureQuery::sigma_gradient at the file's points, all weights (1, 1):
 // one line `sg <scene index> <11 hex words>` per Gaussian (d/d mean[3], cov[6], density, albedo), then one line
 // `sx <point index> <3 hex words>` per point (the gradient with respect to the point).
+// --query-profile RAYS.bin K (the same file) prints MixtureQuery::transmittance_profile of the file's rays at K distances
+// per ray, t[i][k] = tmax_i * (k + 1) / K in f32: one line `tp <ray index> <k> <t, Tr, tau as hex words>` per sample, then
+// MixtureQuery::transmittance_profile_gradient of the same samples, all weights 1: one line `pg <scene index> <10 hex
+// words>` per Gaussian.
 // --upload-device (Gaussian scenes, one GPU): copies the loaded scene's rows to device memory and uploads them with
 // HipIntegrator::upload_device (vr_upload_gaussians_device: records, boxes and tree computed on the device), then
 // renders the scene the context holds.
@@ -149,6 +153,29 @@ static int run_query_sigma_grad(const Scene& scene, const std::string& path) {
     return 0;
 }
 
+// --query-profile: tau and Tr at K distances up to each ray's tmax, and the gradient of the sum of those optical depths.
+static int run_query_profile(const Scene& scene, const std::string& path, int K) {
+    if (K <= 0) throw std::runtime_error("--query-profile: K must be positive");
+    std::vector<Ray> rays;
+    std::vector<float> tmax;
+    std::vector<Eigen::Vector3f> pos;
+    read_query_file(path, rays, tmax, pos);
+    std::vector<float> t(rays.size() * (size_t)K), tau;
+    for (size_t i = 0; i < rays.size(); ++i)
+        for (int k = 0; k < K; ++k) t[i * (size_t)K + k] = tmax[i] * (float)(k + 1) / (float)K;
+    const MixtureQuery q(scene);
+    const std::vector<float> tr = q.transmittance_profile(rays, t, (uint32_t)K, &tau);
+    for (size_t i = 0; i < tr.size(); ++i)
+        std::printf("tp %zu %zu %08x %08x %08x\n", i / (size_t)K, i % (size_t)K, fbits(t[i]), fbits(tr[i]), fbits(tau[i]));
+    const std::vector<float> g = q.transmittance_profile_gradient(rays, t, (uint32_t)K);
+    for (size_t i = 0; i < g.size() / 10; ++i) {
+        std::printf("pg %zu", i);
+        for (int k = 0; k < 10; ++k) std::printf(" %08x", fbits(g[10 * i + k]));
+        std::printf("\n");
+    }
+    return 0;
+}
+
 // --upload-device: the scene's rows as four device arrays, uploaded from there.
 static void upload_from_device_memory(vr_ctx* ctx, const Scene& scene) {
     if (scene.volume_type != Scene::VolumeType::GAUSSIANS) throw std::runtime_error("--upload-device needs a Gaussian scene");
@@ -203,7 +230,8 @@ int main(int argc, char** argv) try {
     int inverse = 0, stoch = 4, final_spp = 0;
     uint64_t seed = 0;
     float lr = 1e-2f;
-    std::string ref_path, sfd_out, gif_path, query_path, query_grad_path, query_ray_grad_path, query_sigma_grad_path;
+    std::string ref_path, sfd_out, gif_path, query_path, query_grad_path, query_ray_grad_path, query_sigma_grad_path, query_profile_path;
+    int profile_k = 0;
     int frames = 120;
     float fps = 30.0f;
     Eigen::Vector3f pos(0, 1, 6), lookat(0, 1, 0);
@@ -233,6 +261,7 @@ int main(int argc, char** argv) try {
         else if (a == "--query-grad") query_grad_path = next();
         else if (a == "--query-ray-grad") query_ray_grad_path = next();
         else if (a == "--query-sigma-grad") query_sigma_grad_path = next();
+        else if (a == "--query-profile") { query_profile_path = next(); profile_k = std::atoi(next()); }
         else if (a == "--gif") gif_path = next();
         else if (a == "--frames") frames = std::atoi(next());
         else if (a == "--fps") fps = std::strtof(next(), nullptr);
@@ -292,6 +321,7 @@ int main(int argc, char** argv) try {
     if (!query_grad_path.empty()) return run_query_grad(scene, query_grad_path);
     if (!query_ray_grad_path.empty()) return run_query_ray_grad(scene, query_ray_grad_path);
     if (!query_sigma_grad_path.empty()) return run_query_sigma_grad(scene, query_sigma_grad_path);
+    if (!query_profile_path.empty()) return run_query_profile(scene, query_profile_path, profile_k);
 
     if (!gif_path.empty()) {  // main.cpp:81-114
         const float radius = 6.0f, height_pos = 1.0f;
