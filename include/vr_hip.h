@@ -113,7 +113,14 @@ typedef struct vr_scene_info {
     float bounds_max[3];
 } vr_scene_info;
 
-/* Statistics of the last vr_render / vr_render_tiles_device call on a context (waits for it). */
+/* Statistics of the last vr_render / vr_render_tiles_device call on a context (waits for it).
+ * A frame's pixels do not depend on what the context did before. The counts of a ray-march frame (pixels,
+ * fallback_pixels, error_pixels, scatter_records, deep_pixels) depend on it in one way: a frame that re-ran 5 % of its
+ * pixels on the large-capacity path makes the context's later frames of that scene march with twice the slots (until
+ * the next upload), and a frame that outgrew the buffers left by earlier frames and was rendered again counts as such a
+ * later frame. A frame therefore reports the counts of a new context's first frame of the scene, or those of its
+ * second: fewer fallback_pixels, and another scatter_records, which counts the records of abandoned marches too.
+ * filtered_rays is 0 on the frames that leave the list filter out. */
 typedef struct vr_render_stats {
     double kernel_ms;         /* device time of the render kernels (HIP events) */
     int64_t pixels;           /* pixels rendered */

@@ -1,4 +1,5 @@
-"""Shared test helpers (camera setups of the reference driver, PPM reading, scene paths)."""
+"""Shared test helpers (camera setups of the reference driver, PPM reading, scene paths, frames on a given context)."""
+import ctypes
 import os
 
 import numpy as np
@@ -20,6 +21,35 @@ def main_view_dir():
 
 def scene_path(name):
     return os.path.join(SCENES, name)
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def render(dev, integ, W, H, slot=None):
+    """One frame of `integ`'s parameters on context `dev` (vr_render; vr_render_record for a slot)."""
+    from vr_amd import _lib as L
+    out = np.empty((H, W, 3), np.float32)
+    cam, par = ctypes.byref(integ.camera.struct), ctypes.byref(integ.params)
+    if slot is None:
+        L.check(L.lib().vr_render(dev._h, cam, par, W, H, L.fptr(out)))
+    else:
+        L.check(L.lib().vr_render_record(dev._h, cam, par, W, H, L.fptr(out), slot))
+    return out
+
+
+def render_rays(dev, integ, origins, directions, unit=False):
+    """A W x H grid of the caller's rays ((H, W, 3) float32 origins and directions) with `integ`'s parameters on
+    context `dev` (vr_render_rays, the host form): (rgb (H, W, 3), transmittance (H, W)). Integrator.render_rays only
+    renders on the cached context."""
+    import vr_amd as vr
+    from vr_amd import _lib as L
+    H, W = origins.shape[:2]
+    rays = vr._pack_ray_grid_numpy(np.asarray(origins, np.float32), np.asarray(directions, np.float32), unit, W, H, W * H)
+    rgb, tr = np.empty((W * H, 3), np.float32), np.empty(W * H, np.float32)
+    L.check(L.lib().vr_render_rays(dev._h, rays.ctypes.data, W, H, ctypes.byref(integ.params), L.fptr(rgb), L.fptr(tr)))
+    return rgb.reshape(H, W, 3), tr.reshape(H, W)
 
 
 def read_ppm(path):

@@ -6,13 +6,12 @@ family, run the three mixture queries and are destroyed (`generations()`, comput
 The integrator classes only take a device index (they render on the cached `Device.get` context), so
 the frames go through the ctypes entry points with the classes' parameter blocks.
 """
-import ctypes
 import functools
 
 import numpy as np
 import pytest
 
-from helpers import CAM_POS, FOV, main_view_dir, scene_path
+from helpers import CAM_POS, FOV, bits, main_view_dir, render, scene_path
 
 pytestmark = pytest.mark.gpu
 
@@ -22,22 +21,6 @@ MIB = 1 << 20
 # (PARENT_DROPS), plus two 2 MiB allocation granules of slack for the runtime's own bookkeeping.
 PARENT_DROPS = (0, 0, 0)
 RELEASE_BOUND = max(PARENT_DROPS) + 4 * MIB
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def render(dev, integ, W, H, slot=None):
-    """One frame of `integ`'s parameters on context `dev` (vr_render; vr_render_record for a slot)."""
-    from vr_amd import _lib as L
-    out = np.empty((H, W, 3), np.float32)
-    cam, par = ctypes.byref(integ.camera.struct), ctypes.byref(integ.params)
-    if slot is None:
-        L.check(L.lib().vr_render(dev._h, cam, par, W, H, L.fptr(out)))
-    else:
-        L.check(L.lib().vr_render_record(dev._h, cam, par, W, H, L.fptr(out), slot))
-    return out
 
 
 def generation(g):
