@@ -126,9 +126,10 @@ struct vr_ctx {
     vr::DevBuf<double> sfd_out, sfd_part;  // the union statistic and its per-chunk partial sums
     // mixture queries (vr_query_*, kernels/vr_query.hip): their own workspaces, grown on demand; nothing of a
     // frame (report, statistics, hints) is touched by a query
-    vr::DevBuf<std::byte> q_in, q_out2;  // host forms: the batch on the device (rays / points) and its second
-    vr::DevBuf<float> q_out;             // result (tau / active counts / events), its first result
-    vr::DevBuf<uint32_t> q_off, q_cnt;          // events: offsets (host form), counts,
+    // host forms (synchronous, one at a time): the batch on the device by role, each sized in 4-byte words: the inputs
+    // (rays / points), the weights / targets / samples / event offsets, the first result and the second
+    vr::DevBuf<float> q_in, q_w, q_out, q_out2;
+    vr::DevBuf<uint32_t> q_cnt;                 // events: counts,
     vr::DevBuf<unsigned long long> q_keys, q_keys2;  // sort keys (in / out),
     vr::DevBuf<std::byte> q_tmp;                // scan + sort scratch
     vr::DevBuf<std::byte> q_ctl;      // words [0..3], [6] ray counters of the five persistent walks, [4..5] the 64-bit event total,
@@ -136,15 +137,12 @@ struct vr_ctx {
     vr::DevBuf<double> q_grad;        // gradient query: 10 doubles of staging per Gaussian (tree order), zeroed per call
     vr::DevBuf<double> q_sgrad;       // sigma gradient query: 11 doubles of staging per Gaussian, its own (the two
                                       // gradient queries may be queued on different streams)
-    // profile query (kernels/vr_query_profile.hip): the host forms' samples, weights and results on the device, and the
-    // gradient's 10 doubles of staging per Gaussian, its own for q_sgrad's reason
-    vr::DevBuf<float> q_prof_t, q_prof_w, q_prof_out;
-    vr::DevBuf<double> q_prof_grad;
+    vr::DevBuf<double> q_prof_grad;   // profile gradient query (kernels/vr_query_profile.hip): 10 doubles of staging per
+                                      // Gaussian, its own for q_sgrad's reason
     // free-flight query (kernels/vr_query_flight.hip): its own scratch rows (the layouts of ff_scratch and of
     // ff_fb's rows), so a frame queued on another stream never shares them; counters + queue of rays over the rows
     vr::DevBuf<std::byte> q_ff_rows, q_ff_big;
     vr::DevBuf<uint32_t> q_ff_ctl;
-    vr::DevBuf<float> q_tau;          // host form: the targets on the device
     // ray grids (vr_render_rays, vr_rays.cpp)
     vr::DevBuf<vr_ray> ray_in;        // host form: the grid on the device,
     vr::DevBuf<float> ray_tr;         //   and its transmittance output

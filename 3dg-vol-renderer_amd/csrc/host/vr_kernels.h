@@ -44,6 +44,9 @@ hipError_t query_events_fill(const RenderArgs& A, const vr_ray* rays, uint32_t n
 // (acc: 10 doubles per Gaussian of staging, zeroed by the call; grad: 10 floats per Gaussian)
 hipError_t query_transmittance_grad(const RenderArgs& A, const vr_ray* rays, const float* weight, uint32_t n, bool moving,
                                     double* acc, float* grad, uint32_t* next, int refill, int cus, hipStream_t s);
+// (the finish of the three gradients' staging rows, width 10 or 11 doubles per Gaussian -> as many floats; the profile
+// gradient's unit calls it too)
+hipError_t query_grad_finish(const RenderArgs& A, const double* acc, int width, float* grad, hipStream_t s);
 // (out: one vr_ray_grad row per ray)
 hipError_t query_transmittance_ray_grad(const RenderArgs& A, const vr_ray* rays, uint32_t n, bool moving, vr_ray_grad* out,
                                         uint32_t* next, int refill, int cus, hipStream_t s);

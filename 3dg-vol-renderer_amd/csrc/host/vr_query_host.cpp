@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 
 #include "vr_ctx.h"
@@ -13,8 +14,10 @@ using namespace vr;
 
 namespace {
 
-// The scene part of the kernel arguments, after the checks every query shares. `n` entries of a batch.
-vr_status query_begin(vr_ctx* c, const char* what, size_t n, RenderArgs& A) {
+// What every entry point does first: the checks they share, then the scene part of the kernel arguments. `n` entries
+// of a batch; c becomes the context's first device.
+vr_status query_begin(vr_ctx*& c, const char* what, size_t n, RenderArgs& A) {
+    c = first_device(c);
     if (!c) return fail(VR_ERR_INVALID, std::string(what) + ": NULL ctx");
     if (!c->has_scene) return fail(VR_ERR_NOSCENE, "no scene uploaded (call vr_upload_scene first)");
     if (c->type != VR_VOLUME_GAUSSIANS) return fail(VR_ERR_UNSUPPORTED, std::string(what) + ": mixture queries need a Gaussian scene");
@@ -39,17 +42,74 @@ vr_status query_begin(vr_ctx* c, const char* what, size_t n, RenderArgs& A) {
 int query_refill(const vr_ctx* c) { return std::clamp<int>(c->auto_nee_refill, 1, 64); }
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
+// Checks of more than one entry point, each with its message. `what` names the entry point.
+vr_status rays_aligned(const char* what, const vr_ray* d_rays) {
+    return aligned16(d_rays) ? VR_OK : fail(VR_ERR_INVALID, std::string(what) + ": the device ray array must be 16-byte aligned");
+}
+vr_status grad_flags(const char* what, uint32_t flags) {
+    return flags & ~(uint32_t)VR_GRAD_FROZEN_BOUNDS ? fail(VR_ERR_INVALID, std::string(what) + ": unknown flag bits") : VR_OK;
+}
+// The four profile entry points' own, before every launch.
+vr_status profile_check(const char* what, size_t t_stride, size_t n, uint32_t K) {
+    if (K == 0 || K > VR_PROFILE_MAX_SAMPLES)
+        return fail(VR_ERR_INVALID, std::string(what) + ": K must lie in [1, " + std::to_string(VR_PROFILE_MAX_SAMPLES) + "]");
+    if (t_stride != 0 && t_stride != K) return fail(VR_ERR_INVALID, std::string(what) + ": t_stride must be 0 (one shared row) or K");
+    if (n >= (1ull << 31) || n * (size_t)K >= (1ull << 31))
+        return fail(VR_ERR_INVALID, std::string(what) + ": more than 2^31 - 1 samples in one call");
+    return VR_OK;
+}
+// The gradient over no entries, or of a scene without Gaussians, is `words` zeros: true, and no launch follows.
+bool grad_is_zero(size_t n, size_t words, float* grad) {
+    if (n != 0 && words != 0) return false;
+    if (grad) std::memset(grad, 0, words * sizeof(float));
+    return true;
+}
+
+// ---- the host forms ----
+// Each is five steps: its checks; its inputs staged in the context's workspaces (q_in, q_w, q_out, q_out2: vr_ctx.h);
+// its `_device` form on c->stream; a synchronise; its results fetched. host_form is the last four. An array is
+// {workspace, host pointer, 4-byte words, its name in a HIP failure's message, first word in the workspace}. One whose
+// host pointer is NULL (an optional input or output) is skipped, and dev() hands the `_device` form NULL for it.
+struct In { DevBuf<float>& buf; const void* host; size_t words; const char* what; };
+struct Out { DevBuf<float>& buf; void* host; size_t words; const char* what; size_t at = 0; };
+constexpr size_t kRayWords = sizeof(vr_ray) / 4;
+
+vr_status room(DevBuf<float>& buf, size_t words, const char* what) {
+    return buf.grow(words, (std::string("hipMalloc(") + what + ")").c_str());
+}
+vr_status copy(void* dst, const void* src, size_t words, hipMemcpyKind kind, const char* what) {
+    return hip_status(hipMemcpy(dst, src, words * 4, kind), (std::string("hipMemcpy(") + what + ")").c_str());
+}
+template <class T>
+T* dev(const DevBuf<float>& buf, const void* host, size_t at = 0) {
+    return host ? reinterpret_cast<T*>(buf.get() + at) : nullptr;
+}
+template <class Call>
+vr_status host_form(vr_ctx* c, std::initializer_list<In> ins, std::initializer_list<Out> outs, const char* kernel, Call call) {
+    for (const In& a : ins)
+        if (a.host) {
+            VR_TRY(room(a.buf, a.words, a.what));
+            VR_TRY(copy(a.buf.get(), a.host, a.words, hipMemcpyHostToDevice, a.what));
+        }
+    for (const Out& a : outs)
+        if (a.host) VR_TRY(room(a.buf, a.at + a.words, a.what));
+    VR_TRY(call());
+    HIP_TRY(hipStreamSynchronize(c->stream), kernel);
+    for (const Out& a : outs)
+        if (a.host) VR_TRY(copy(a.host, a.buf.get() + a.at, a.words, hipMemcpyDeviceToHost, a.what));
+    return VR_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 vr_status vr_query_transmittance_device(vr_ctx* c, const vr_ray* d_rays, size_t n, float* d_tr, float* d_tau, void* stream) {
-    c = first_device(c);
     RenderArgs A;
     VR_TRY(query_begin(c, "vr_query_transmittance", n, A));
     if (n == 0) return VR_OK;
     if (!d_rays || !d_tr) return fail(VR_ERR_INVALID, "vr_query_transmittance: NULL argument");
-    if (!aligned16(d_rays)) return fail(VR_ERR_INVALID, "vr_query_transmittance: the device ray array must be 16-byte aligned");
+    VR_TRY(rays_aligned("vr_query_transmittance", d_rays));
     HIP_TRY(query_transmittance(A, d_rays, (uint32_t)n, d_tr, d_tau, (uint32_t*)c->q_ctl.get(), query_refill(c), c->cus,
                                 (hipStream_t)stream),
             "query_transmittance_kernel");
@@ -57,31 +117,24 @@ vr_status vr_query_transmittance_device(vr_ctx* c, const vr_ray* d_rays, size_t 
 }
 
 vr_status vr_query_transmittance(vr_ctx* c, const vr_ray* rays, size_t n, float* tr, float* tau) {
-    c = first_device(c);
     RenderArgs A;
     vr_status st = query_begin(c, "vr_query_transmittance", n, A);
     if (st != VR_OK || n == 0) return st;
     if (!rays || !tr) return fail(VR_ERR_INVALID, "vr_query_transmittance: NULL argument");
-    VR_TRY(c->q_in.grow(n * sizeof(vr_ray), "hipMalloc(query rays)"));
-    VR_TRY(c->q_out.grow(n, "hipMalloc(query results)"));
-    if (tau) VR_TRY(c->q_out2.grow(n * sizeof(float), "hipMalloc(query results)"));
-    HIP_TRY(hipMemcpy(c->q_in.get(), rays, n * sizeof(vr_ray), hipMemcpyHostToDevice), "hipMemcpy(query rays)");
-    VR_TRY(vr_query_transmittance_device(c, (const vr_ray*)c->q_in.get(), n, c->q_out.get(), tau ? (float*)c->q_out2.get() : nullptr,
-                                       c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream), "query_transmittance_kernel");
-    HIP_TRY(hipMemcpy(tr, c->q_out.get(), n * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
-    if (tau) HIP_TRY(hipMemcpy(tau, c->q_out2.get(), n * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
-    return VR_OK;
+    return host_form(c, {{c->q_in, rays, n * kRayWords, "query rays"}},
+                     {{c->q_out, tr, n, "query results"}, {c->q_out2, tau, n, "query results"}}, "query_transmittance_kernel", [&] {
+                         return vr_query_transmittance_device(c, dev<vr_ray>(c->q_in, rays), n, dev<float>(c->q_out, tr),
+                                                              dev<float>(c->q_out2, tau), c->stream);
+                     });
 }
 
 vr_status vr_query_transmittance_grad_device(vr_ctx* c, const vr_ray* d_rays, const float* d_weight, size_t n, uint32_t flags,
                                              float* d_grad, void* stream) {
-    c = first_device(c);
     RenderArgs A;
     VR_TRY(query_begin(c, "vr_query_transmittance_grad", n, A));
-    if (flags & ~(uint32_t)VR_GRAD_FROZEN_BOUNDS) return fail(VR_ERR_INVALID, "vr_query_transmittance_grad: unknown flag bits");
+    VR_TRY(grad_flags("vr_query_transmittance_grad", flags));
     if (!d_grad || (n > 0 && !d_rays)) return fail(VR_ERR_INVALID, "vr_query_transmittance_grad: NULL argument");
-    if (!aligned16(d_rays)) return fail(VR_ERR_INVALID, "vr_query_transmittance_grad: the device ray array must be 16-byte aligned");
+    VR_TRY(rays_aligned("vr_query_transmittance_grad", d_rays));
     // the staging rows are the query's own: a frame queued on another stream never sees them
     VR_TRY(c->q_grad.grow((size_t)std::max(A.num_prims, 1) * 10, "hipMalloc(gradient staging)"));
     HIP_TRY(query_transmittance_grad(A, d_rays, d_weight, (uint32_t)n, !(flags & VR_GRAD_FROZEN_BOUNDS), c->q_grad.get(), d_grad,
@@ -91,34 +144,24 @@ vr_status vr_query_transmittance_grad_device(vr_ctx* c, const vr_ray* d_rays, co
 }
 
 vr_status vr_query_transmittance_grad(vr_ctx* c, const vr_ray* rays, const float* weight, size_t n, uint32_t flags, float* grad) {
-    c = first_device(c);
     RenderArgs A;
     VR_TRY(query_begin(c, "vr_query_transmittance_grad", n, A));
-    if (flags & ~(uint32_t)VR_GRAD_FROZEN_BOUNDS) return fail(VR_ERR_INVALID, "vr_query_transmittance_grad: unknown flag bits");
+    VR_TRY(grad_flags("vr_query_transmittance_grad", flags));
     if (!grad || (n > 0 && !rays)) return fail(VR_ERR_INVALID, "vr_query_transmittance_grad: NULL argument");
     const size_t words = (size_t)std::max(A.num_prims, 0) * 10;
-    if (n == 0 || words == 0) {
-        std::memset(grad, 0, words * sizeof(float));
-        return VR_OK;
-    }
-    VR_TRY(c->q_in.grow(n * sizeof(vr_ray), "hipMalloc(query rays)"));
-    if (weight) VR_TRY(c->q_tau.grow(n, "hipMalloc(query weights)"));
-    VR_TRY(c->q_out.grow(words, "hipMalloc(query results)"));
-    HIP_TRY(hipMemcpy(c->q_in.get(), rays, n * sizeof(vr_ray), hipMemcpyHostToDevice), "hipMemcpy(query rays)");
-    if (weight) HIP_TRY(hipMemcpy(c->q_tau.get(), weight, n * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(query weights)");
-    VR_TRY(vr_query_transmittance_grad_device(c, (const vr_ray*)c->q_in.get(), weight ? c->q_tau.get() : nullptr, n, flags,
-                                              c->q_out.get(), c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream), "query_grad_kernel");
-    HIP_TRY(hipMemcpy(grad, c->q_out.get(), words * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
-    return VR_OK;
+    if (grad_is_zero(n, words, grad)) return VR_OK;
+    return host_form(c, {{c->q_in, rays, n * kRayWords, "query rays"}, {c->q_w, weight, n, "query weights"}},
+                     {{c->q_out, grad, words, "query results"}}, "query_grad_kernel", [&] {
+                         return vr_query_transmittance_grad_device(c, dev<vr_ray>(c->q_in, rays), dev<float>(c->q_w, weight), n, flags,
+                                                                   c->q_out.get(), c->stream);
+                     });
 }
 
 vr_status vr_query_transmittance_ray_grad_device(vr_ctx* c, const vr_ray* d_rays, size_t n, uint32_t flags, vr_ray_grad* d_out,
                                                  void* stream) {
-    c = first_device(c);
     RenderArgs A;
     VR_TRY(query_begin(c, "vr_query_transmittance_ray_grad", n, A));
-    if (flags & ~(uint32_t)VR_GRAD_FROZEN_BOUNDS) return fail(VR_ERR_INVALID, "vr_query_transmittance_ray_grad: unknown flag bits");
+    VR_TRY(grad_flags("vr_query_transmittance_ray_grad", flags));
     if (n == 0) return VR_OK;
     if (!d_rays || !d_out) return fail(VR_ERR_INVALID, "vr_query_transmittance_ray_grad: NULL argument");
     if (!aligned16(d_rays) || !aligned16(d_out))
@@ -130,47 +173,28 @@ vr_status vr_query_transmittance_ray_grad_device(vr_ctx* c, const vr_ray* d_rays
 }
 
 vr_status vr_query_transmittance_ray_grad(vr_ctx* c, const vr_ray* rays, size_t n, uint32_t flags, vr_ray_grad* out) {
-    c = first_device(c);
     RenderArgs A;
     VR_TRY(query_begin(c, "vr_query_transmittance_ray_grad", n, A));
-    if (flags & ~(uint32_t)VR_GRAD_FROZEN_BOUNDS) return fail(VR_ERR_INVALID, "vr_query_transmittance_ray_grad: unknown flag bits");
+    VR_TRY(grad_flags("vr_query_transmittance_ray_grad", flags));
     if (n == 0) return VR_OK;
     if (!rays || !out) return fail(VR_ERR_INVALID, "vr_query_transmittance_ray_grad: NULL argument");
-    VR_TRY(c->q_in.grow(n * sizeof(vr_ray), "hipMalloc(query rays)"));
-    VR_TRY(c->q_out.grow(n * (sizeof(vr_ray_grad) / sizeof(float)), "hipMalloc(query results)"));
-    HIP_TRY(hipMemcpy(c->q_in.get(), rays, n * sizeof(vr_ray), hipMemcpyHostToDevice), "hipMemcpy(query rays)");
-    VR_TRY(vr_query_transmittance_ray_grad_device(c, (const vr_ray*)c->q_in.get(), n, flags, (vr_ray_grad*)c->q_out.get(),
-                                                  c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream), "query_ray_grad_kernel");
-    HIP_TRY(hipMemcpy(out, c->q_out.get(), n * sizeof(vr_ray_grad), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
-    return VR_OK;
+    return host_form(c, {{c->q_in, rays, n * kRayWords, "query rays"}},
+                     {{c->q_out, out, n * (sizeof(vr_ray_grad) / 4), "query results"}}, "query_ray_grad_kernel", [&] {
+                         return vr_query_transmittance_ray_grad_device(c, dev<vr_ray>(c->q_in, rays), n, flags,
+                                                                       dev<vr_ray_grad>(c->q_out, out), c->stream);
+                     });
 }
 
 // ---- transmittance profile: K samples per ray from one walk ----
-namespace {
-
-// The checks of the four profile entry points that precede every launch. `what` names the entry point.
-vr_status profile_check(const char* what, size_t t_stride, size_t n, uint32_t K) {
-    if (K == 0 || K > VR_PROFILE_MAX_SAMPLES)
-        return fail(VR_ERR_INVALID, std::string(what) + ": K must lie in [1, " + std::to_string(VR_PROFILE_MAX_SAMPLES) + "]");
-    if (t_stride != 0 && t_stride != K) return fail(VR_ERR_INVALID, std::string(what) + ": t_stride must be 0 (one shared row) or K");
-    if (n >= (1ull << 31) || n * (size_t)K >= (1ull << 31))
-        return fail(VR_ERR_INVALID, std::string(what) + ": more than 2^31 - 1 samples in one call");
-    return VR_OK;
-}
-
-}  // namespace
-
 vr_status vr_query_transmittance_profile_device(vr_ctx* c, const vr_ray* d_rays, const float* d_t, size_t t_stride, size_t n,
                                                 uint32_t K, float* d_tr, float* d_tau, void* stream) {
-    c = first_device(c);
     RenderArgs A;
     VR_TRY(query_begin(c, "vr_query_transmittance_profile", n, A));
     VR_TRY(profile_check("vr_query_transmittance_profile", t_stride, n, K));
     if (!d_tr && !d_tau) return fail(VR_ERR_INVALID, "vr_query_transmittance_profile: both outputs are NULL");
     if (n == 0) return VR_OK;
     if (!d_rays || !d_t) return fail(VR_ERR_INVALID, "vr_query_transmittance_profile: NULL argument");
-    if (!aligned16(d_rays)) return fail(VR_ERR_INVALID, "vr_query_transmittance_profile: the device ray array must be 16-byte aligned");
+    VR_TRY(rays_aligned("vr_query_transmittance_profile", d_rays));
     HIP_TRY(query_transmittance_profile(A, d_rays, d_t, (uint32_t)t_stride, (uint32_t)n, K, d_tr, d_tau,
                                         (uint32_t*)c->q_ctl.get() + 8, query_refill(c), c->cus, (hipStream_t)stream),
             "query_profile_kernel");
@@ -179,7 +203,6 @@ vr_status vr_query_transmittance_profile_device(vr_ctx* c, const vr_ray* d_rays,
 
 vr_status vr_query_transmittance_profile(vr_ctx* c, const vr_ray* rays, const float* t, size_t t_stride, size_t n, uint32_t K,
                                          float* tr, float* tau) {
-    c = first_device(c);
     RenderArgs A;
     VR_TRY(query_begin(c, "vr_query_transmittance_profile", n, A));
     VR_TRY(profile_check("vr_query_transmittance_profile", t_stride, n, K));
@@ -187,32 +210,22 @@ vr_status vr_query_transmittance_profile(vr_ctx* c, const vr_ray* rays, const fl
     if (n == 0) return VR_OK;
     if (!rays || !t) return fail(VR_ERR_INVALID, "vr_query_transmittance_profile: NULL argument");
     const size_t nk = n * (size_t)K, nt = t_stride ? nk : (size_t)K;
-    VR_TRY(c->q_in.grow(n * sizeof(vr_ray), "hipMalloc(query rays)"));
-    VR_TRY(c->q_prof_t.grow(nt, "hipMalloc(profile samples)"));
-    VR_TRY(c->q_prof_out.grow(2 * nk, "hipMalloc(profile results)"));
-    HIP_TRY(hipMemcpy(c->q_in.get(), rays, n * sizeof(vr_ray), hipMemcpyHostToDevice), "hipMemcpy(query rays)");
-    HIP_TRY(hipMemcpy(c->q_prof_t.get(), t, nt * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(profile samples)");
-    float* d_tr = c->q_prof_out.get();
-    float* d_tau = d_tr + nk;
-    VR_TRY(vr_query_transmittance_profile_device(c, (const vr_ray*)c->q_in.get(), c->q_prof_t.get(), t_stride, n, K,
-                                                 tr ? d_tr : nullptr, tau ? d_tau : nullptr, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream), "query_profile_kernel");
-    if (tr) HIP_TRY(hipMemcpy(tr, d_tr, nk * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(profile results)");
-    if (tau) HIP_TRY(hipMemcpy(tau, d_tau, nk * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(profile results)");
-    return VR_OK;
+    return host_form(c, {{c->q_in, rays, n * kRayWords, "query rays"}, {c->q_w, t, nt, "profile samples"}},
+                     {{c->q_out, tr, nk, "profile results"}, {c->q_out2, tau, nk, "profile results"}}, "query_profile_kernel", [&] {
+                         return vr_query_transmittance_profile_device(c, dev<vr_ray>(c->q_in, rays), c->q_w.get(), t_stride, n, K,
+                                                                      dev<float>(c->q_out, tr), dev<float>(c->q_out2, tau), c->stream);
+                     });
 }
 
 vr_status vr_query_transmittance_profile_grad_device(vr_ctx* c, const vr_ray* d_rays, const float* d_t, size_t t_stride,
                                                      const float* d_weight, size_t n, uint32_t K, uint32_t flags, float* d_grad,
                                                      void* stream) {
-    c = first_device(c);
     RenderArgs A;
     VR_TRY(query_begin(c, "vr_query_transmittance_profile_grad", n, A));
     VR_TRY(profile_check("vr_query_transmittance_profile_grad", t_stride, n, K));
-    if (flags & ~(uint32_t)VR_GRAD_FROZEN_BOUNDS) return fail(VR_ERR_INVALID, "vr_query_transmittance_profile_grad: unknown flag bits");
+    VR_TRY(grad_flags("vr_query_transmittance_profile_grad", flags));
     if (!d_grad || (n > 0 && (!d_rays || !d_t))) return fail(VR_ERR_INVALID, "vr_query_transmittance_profile_grad: NULL argument");
-    if (!aligned16(d_rays))
-        return fail(VR_ERR_INVALID, "vr_query_transmittance_profile_grad: the device ray array must be 16-byte aligned");
+    VR_TRY(rays_aligned("vr_query_transmittance_profile_grad", d_rays));
     // the staging rows are this query's own: a frame or another gradient query queued on another stream never sees them
     VR_TRY(c->q_prof_grad.grow((size_t)std::max(A.num_prims, 1) * 10, "hipMalloc(gradient staging)"));
     HIP_TRY(query_transmittance_profile_grad(A, d_rays, d_t, (uint32_t)t_stride, d_weight, (uint32_t)n, K,
@@ -224,35 +237,25 @@ vr_status vr_query_transmittance_profile_grad_device(vr_ctx* c, const vr_ray* d_
 
 vr_status vr_query_transmittance_profile_grad(vr_ctx* c, const vr_ray* rays, const float* t, size_t t_stride, const float* weight,
                                               size_t n, uint32_t K, uint32_t flags, float* grad) {
-    c = first_device(c);
     RenderArgs A;
     VR_TRY(query_begin(c, "vr_query_transmittance_profile_grad", n, A));
     VR_TRY(profile_check("vr_query_transmittance_profile_grad", t_stride, n, K));
-    if (flags & ~(uint32_t)VR_GRAD_FROZEN_BOUNDS) return fail(VR_ERR_INVALID, "vr_query_transmittance_profile_grad: unknown flag bits");
+    VR_TRY(grad_flags("vr_query_transmittance_profile_grad", flags));
     if (!grad || (n > 0 && (!rays || !t))) return fail(VR_ERR_INVALID, "vr_query_transmittance_profile_grad: NULL argument");
     const size_t words = (size_t)std::max(A.num_prims, 0) * 10;
-    if (n == 0 || words == 0) {
-        std::memset(grad, 0, words * sizeof(float));
-        return VR_OK;
-    }
+    if (grad_is_zero(n, words, grad)) return VR_OK;
     const size_t nk = n * (size_t)K, nt = t_stride ? nk : (size_t)K;
-    VR_TRY(c->q_in.grow(n * sizeof(vr_ray), "hipMalloc(query rays)"));
-    VR_TRY(c->q_prof_t.grow(nt, "hipMalloc(profile samples)"));
-    if (weight) VR_TRY(c->q_prof_w.grow(nk, "hipMalloc(profile weights)"));
-    VR_TRY(c->q_prof_out.grow(words, "hipMalloc(profile results)"));
-    HIP_TRY(hipMemcpy(c->q_in.get(), rays, n * sizeof(vr_ray), hipMemcpyHostToDevice), "hipMemcpy(query rays)");
-    HIP_TRY(hipMemcpy(c->q_prof_t.get(), t, nt * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(profile samples)");
-    if (weight) HIP_TRY(hipMemcpy(c->q_prof_w.get(), weight, nk * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(profile weights)");
-    VR_TRY(vr_query_transmittance_profile_grad_device(c, (const vr_ray*)c->q_in.get(), c->q_prof_t.get(), t_stride,
-                                                      weight ? c->q_prof_w.get() : nullptr, n, K, flags, c->q_prof_out.get(),
-                                                      c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream), "query_profile_grad_kernel");
-    HIP_TRY(hipMemcpy(grad, c->q_prof_out.get(), words * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(profile results)");
-    return VR_OK;
+    // (three inputs and one result: the weights stand in the second result's workspace)
+    return host_form(c, {{c->q_in, rays, n * kRayWords, "query rays"}, {c->q_w, t, nt, "profile samples"},
+                         {c->q_out2, weight, nk, "profile weights"}},
+                     {{c->q_out, grad, words, "profile results"}}, "query_profile_grad_kernel", [&] {
+                         return vr_query_transmittance_profile_grad_device(c, dev<vr_ray>(c->q_in, rays), c->q_w.get(), t_stride,
+                                                                           dev<float>(c->q_out2, weight), n, K, flags, c->q_out.get(),
+                                                                           c->stream);
+                     });
 }
 
 vr_status vr_query_sigma_device(vr_ctx* c, const float* d_xyz, size_t n, float* d_sigma_as, uint32_t* d_n_active, void* stream) {
-    c = first_device(c);
     RenderArgs A;
     VR_TRY(query_begin(c, "vr_query_sigma", n, A));
     if (n == 0) return VR_OK;
@@ -262,26 +265,18 @@ vr_status vr_query_sigma_device(vr_ctx* c, const float* d_xyz, size_t n, float* 
 }
 
 vr_status vr_query_sigma(vr_ctx* c, const float* xyz, size_t n, float* sigma_as, uint32_t* n_active) {
-    c = first_device(c);
     RenderArgs A;
     vr_status st = query_begin(c, "vr_query_sigma", n, A);
     if (st != VR_OK || n == 0) return st;
     if (!xyz || !sigma_as) return fail(VR_ERR_INVALID, "vr_query_sigma: NULL argument");
-    VR_TRY(c->q_in.grow(n * 3 * sizeof(float), "hipMalloc(query points)"));
-    VR_TRY(c->q_out.grow(n * 2, "hipMalloc(query results)"));
-    if (n_active) VR_TRY(c->q_out2.grow(n * sizeof(uint32_t), "hipMalloc(query results)"));
-    HIP_TRY(hipMemcpy(c->q_in.get(), xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(query points)");
-    VR_TRY(vr_query_sigma_device(c, (const float*)c->q_in.get(), n, c->q_out.get(), n_active ? (uint32_t*)c->q_out2.get() : nullptr,
-                               c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream), "query_sigma_kernel");
-    HIP_TRY(hipMemcpy(sigma_as, c->q_out.get(), n * 2 * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
-    if (n_active) HIP_TRY(hipMemcpy(n_active, c->q_out2.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
-    return VR_OK;
+    return host_form(c, {{c->q_in, xyz, n * 3, "query points"}},
+                     {{c->q_out, sigma_as, n * 2, "query results"}, {c->q_out2, n_active, n, "query results"}}, "query_sigma_kernel", [&] {
+                         return vr_query_sigma_device(c, c->q_in.get(), n, c->q_out.get(), dev<uint32_t>(c->q_out2, n_active), c->stream);
+                     });
 }
 
 vr_status vr_query_sigma_grad_device(vr_ctx* c, const float* d_xyz, const float* d_weight_as, size_t n, float* d_grad,
                                      float* d_grad_xyz, void* stream) {
-    c = first_device(c);
     RenderArgs A;
     VR_TRY(query_begin(c, "vr_query_sigma_grad", n, A));
     const size_t words = (size_t)std::max(A.num_prims, 0) * 11;
@@ -300,42 +295,30 @@ vr_status vr_query_sigma_grad_device(vr_ctx* c, const float* d_xyz, const float*
 }
 
 vr_status vr_query_sigma_grad(vr_ctx* c, const float* xyz, const float* weight_as, size_t n, float* grad, float* grad_xyz) {
-    c = first_device(c);
     RenderArgs A;
     VR_TRY(query_begin(c, "vr_query_sigma_grad", n, A));
     const size_t words = (size_t)std::max(A.num_prims, 0) * 11;
-    if (n == 0) {
-        if (grad) std::memset(grad, 0, words * sizeof(float));
-        return VR_OK;
-    }
+    if (n == 0 && grad_is_zero(n, words, grad)) return VR_OK;
     if (!xyz) return fail(VR_ERR_INVALID, "vr_query_sigma_grad: NULL argument");
     if (!grad && !grad_xyz) return fail(VR_ERR_INVALID, "vr_query_sigma_grad: both outputs are NULL");
-    const bool gauss = grad && words > 0;
-    VR_TRY(c->q_in.grow(n * 3 * sizeof(float), "hipMalloc(query points)"));
-    if (weight_as) VR_TRY(c->q_tau.grow(n * 2, "hipMalloc(query weights)"));
-    if (gauss) VR_TRY(c->q_out.grow(words, "hipMalloc(query results)"));
-    if (grad_xyz) VR_TRY(c->q_out2.grow(n * 3 * sizeof(float), "hipMalloc(query results)"));
-    HIP_TRY(hipMemcpy(c->q_in.get(), xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(query points)");
-    if (weight_as) HIP_TRY(hipMemcpy(c->q_tau.get(), weight_as, n * 2 * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(query weights)");
-    if (gauss || grad_xyz) {
-        VR_TRY(vr_query_sigma_grad_device(c, (const float*)c->q_in.get(), weight_as ? c->q_tau.get() : nullptr, n,
-                                          gauss ? c->q_out.get() : nullptr, grad_xyz ? (float*)c->q_out2.get() : nullptr, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream), "query_sigma_grad_kernel");
-    }
-    if (gauss) HIP_TRY(hipMemcpy(grad, c->q_out.get(), words * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
-    if (grad_xyz) HIP_TRY(hipMemcpy(grad_xyz, c->q_out2.get(), n * 3 * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
-    return VR_OK;
+    if (words == 0) grad = nullptr;  // an empty scene: grad has no entries,
+    if (!grad && !grad_xyz) return VR_OK;  // and nothing else was asked for
+    return host_form(c, {{c->q_in, xyz, n * 3, "query points"}, {c->q_w, weight_as, n * 2, "query weights"}},
+                     {{c->q_out, grad, words, "query results"}, {c->q_out2, grad_xyz, n * 3, "query results"}},
+                     "query_sigma_grad_kernel", [&] {
+                         return vr_query_sigma_grad_device(c, c->q_in.get(), dev<float>(c->q_w, weight_as), n, dev<float>(c->q_out, grad),
+                                                           dev<float>(c->q_out2, grad_xyz), c->stream);
+                     });
 }
 
 vr_status vr_query_events_count_device(vr_ctx* c, const vr_ray* d_rays, size_t n, uint32_t* d_offsets, uint64_t* total) {
-    c = first_device(c);
     RenderArgs A;
     VR_TRY(query_begin(c, "vr_query_events", n, A));
     if (!total) return fail(VR_ERR_INVALID, "vr_query_events: NULL total");
     *total = 0;
     if (n == 0) return VR_OK;
     if (!d_rays || !d_offsets) return fail(VR_ERR_INVALID, "vr_query_events: NULL argument");
-    if (!aligned16(d_rays)) return fail(VR_ERR_INVALID, "vr_query_events: the device ray array must be 16-byte aligned");
+    VR_TRY(rays_aligned("vr_query_events", d_rays));
     c->q_count_valid = false;
     HIP_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");  // d_rays may come from any stream
     VR_TRY(c->q_cnt.grow(n + 1, "hipMalloc(event counts)"));
@@ -362,12 +345,11 @@ vr_status vr_query_events_count_device(vr_ctx* c, const vr_ray* d_rays, size_t n
 
 vr_status vr_query_events_fill_device(vr_ctx* c, const vr_ray* d_rays, size_t n, const uint32_t* d_offsets, float* d_t,
                                       uint32_t* d_ev, uint64_t cap, void* stream) {
-    c = first_device(c);
     RenderArgs A;
     VR_TRY(query_begin(c, "vr_query_events", n, A));
     if (n == 0) return VR_OK;
     if (!d_rays || !d_offsets) return fail(VR_ERR_INVALID, "vr_query_events: NULL argument");
-    if (!aligned16(d_rays)) return fail(VR_ERR_INVALID, "vr_query_events: the device ray array must be 16-byte aligned");
+    VR_TRY(rays_aligned("vr_query_events", d_rays));
     if (!c->q_count_valid || c->q_count_n != n)
         return fail(VR_ERR_INVALID, "vr_query_events_fill_device: no vr_query_events_count_device call for this many rays preceded it");
     const uint64_t tot = c->q_count_total;
@@ -389,9 +371,10 @@ vr_status vr_query_events_fill_device(vr_ctx* c, const vr_ray* d_rays, size_t n,
     return VR_OK;
 }
 
+// The pair's host form: the count (it synchronises itself) and the offsets, which stay in q_w for the fill; then, if
+// the caller gave room, the fill as a host form of its own.
 vr_status vr_query_events(vr_ctx* c, const vr_ray* rays, size_t n, uint32_t* offsets, float* t, uint32_t* ev, uint64_t cap,
                           uint64_t* total) {
-    c = first_device(c);
     RenderArgs A;
     VR_TRY(query_begin(c, "vr_query_events", n, A));
     if (!total) return fail(VR_ERR_INVALID, "vr_query_events: NULL total");
@@ -402,33 +385,29 @@ vr_status vr_query_events(vr_ctx* c, const vr_ray* rays, size_t n, uint32_t* off
     }
     if (!rays || (cap > 0 && (!t || !ev)) || (cap == 0 && ((t == nullptr) != (ev == nullptr))))
         return fail(VR_ERR_INVALID, "vr_query_events: NULL argument");
-    VR_TRY(c->q_in.grow(n * sizeof(vr_ray), "hipMalloc(query rays)"));
-    VR_TRY(c->q_off.grow(n + 1, "hipMalloc(event offsets)"));
-    HIP_TRY(hipMemcpy(c->q_in.get(), rays, n * sizeof(vr_ray), hipMemcpyHostToDevice), "hipMemcpy(query rays)");
-    VR_TRY(vr_query_events_count_device(c, (const vr_ray*)c->q_in.get(), n, c->q_off.get(), total));
-    if (offsets) HIP_TRY(hipMemcpy(offsets, c->q_off.get(), (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy(event offsets)");
+    VR_TRY(room(c->q_in, n * kRayWords, "query rays"));
+    VR_TRY(room(c->q_w, n + 1, "event offsets"));
+    const vr_ray* d_rays = (const vr_ray*)c->q_in.get();
+    uint32_t* d_off = (uint32_t*)c->q_w.get();
+    VR_TRY(copy(c->q_in.get(), rays, n * kRayWords, hipMemcpyHostToDevice, "query rays"));
+    VR_TRY(vr_query_events_count_device(c, d_rays, n, d_off, total));
+    if (offsets) VR_TRY(copy(offsets, d_off, n + 1, hipMemcpyDeviceToHost, "event offsets"));
     if (cap == 0 && !t && !ev) return VR_OK;
     const uint64_t tot = *total;
     if (cap < tot) return fail(VR_ERR_OVERFLOW, "vr_query_events: " + std::to_string(tot) + " events, room for " + std::to_string(cap));
     if (tot == 0) return VR_OK;
-    VR_TRY(c->q_out.grow(tot, "hipMalloc(query results)"));
-    VR_TRY(c->q_out2.grow(tot * sizeof(uint32_t), "hipMalloc(query results)"));
-    VR_TRY(vr_query_events_fill_device(c, (const vr_ray*)c->q_in.get(), n, c->q_off.get(), c->q_out.get(),
-                                     (uint32_t*)c->q_out2.get(), tot, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream), "query_events_fill_kernel");
-    HIP_TRY(hipMemcpy(t, c->q_out.get(), tot * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
-    HIP_TRY(hipMemcpy(ev, c->q_out2.get(), tot * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
-    return VR_OK;
+    return host_form(c, {}, {{c->q_out, t, tot, "query results"}, {c->q_out2, ev, tot, "query results"}}, "query_events_fill_kernel", [&] {
+        return vr_query_events_fill_device(c, d_rays, n, d_off, c->q_out.get(), dev<uint32_t>(c->q_out2, ev), tot, c->stream);
+    });
 }
 
 vr_status vr_query_free_flight_device(vr_ctx* c, const vr_ray* d_rays, const float* d_tau_target, size_t n, float* d_t,
                                       float* d_albedo, uint32_t* d_n_active, void* stream) {
-    c = first_device(c);
     RenderArgs A;
     VR_TRY(query_begin(c, "vr_query_free_flight", n, A));
     if (n == 0) return VR_OK;
     if (!d_rays || !d_tau_target || !d_t) return fail(VR_ERR_INVALID, "vr_query_free_flight: NULL argument");
-    if (!aligned16(d_rays)) return fail(VR_ERR_INVALID, "vr_query_free_flight: the device ray array must be 16-byte aligned");
+    VR_TRY(rays_aligned("vr_query_free_flight", d_rays));
     if (c->opt_ff_solver == 4)
         return fail(VR_ERR_UNSUPPORTED, "vr_query_free_flight: the UNIFORM solver (VR_OPT_FF_SOLVER = 4) draws from a path's seed");
     // the rows of free_flight_pipeline (vr_frame.cpp), in this query's own buffers
@@ -454,25 +433,20 @@ vr_status vr_query_free_flight_device(vr_ctx* c, const vr_ray* d_rays, const flo
 
 vr_status vr_query_free_flight(vr_ctx* c, const vr_ray* rays, const float* tau_target, size_t n, float* t, float* albedo,
                                uint32_t* n_active) {
-    c = first_device(c);
     RenderArgs A;
     vr_status st = query_begin(c, "vr_query_free_flight", n, A);
     if (st != VR_OK || n == 0) return st;
     if (!rays || !tau_target || !t) return fail(VR_ERR_INVALID, "vr_query_free_flight: NULL argument");
-    VR_TRY(c->q_in.grow(n * sizeof(vr_ray), "hipMalloc(query rays)"));
-    VR_TRY(c->q_tau.grow(n, "hipMalloc(query targets)"));
-    VR_TRY(c->q_out.grow(n * 2, "hipMalloc(query results)"));
-    if (n_active) VR_TRY(c->q_out2.grow(n * sizeof(uint32_t), "hipMalloc(query results)"));
-    HIP_TRY(hipMemcpy(c->q_in.get(), rays, n * sizeof(vr_ray), hipMemcpyHostToDevice), "hipMemcpy(query rays)");
-    HIP_TRY(hipMemcpy(c->q_tau.get(), tau_target, n * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(query targets)");
-    VR_TRY(vr_query_free_flight_device(c, (const vr_ray*)c->q_in.get(), c->q_tau.get(), n, c->q_out.get(),
-                                       albedo ? c->q_out.get() + n : nullptr, n_active ? (uint32_t*)c->q_out2.get() : nullptr, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream), "query_flight_kernel");
-    HIP_TRY(hipMemcpy(t, c->q_out.get(), n * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
-    if (albedo) HIP_TRY(hipMemcpy(albedo, c->q_out.get() + n, n * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
-    if (n_active) HIP_TRY(hipMemcpy(n_active, c->q_out2.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    // (t and the albedo share the first result's workspace)
+    VR_TRY(host_form(c, {{c->q_in, rays, n * kRayWords, "query rays"}, {c->q_w, tau_target, n, "query targets"}},
+                     {{c->q_out, t, n, "query results"}, {c->q_out, albedo, n, "query results", n},
+                      {c->q_out2, n_active, n, "query results"}},
+                     "query_flight_kernel", [&] {
+                         return vr_query_free_flight_device(c, dev<vr_ray>(c->q_in, rays), c->q_w.get(), n, c->q_out.get(),
+                                                            dev<float>(c->q_out, albedo, n), dev<uint32_t>(c->q_out2, n_active), c->stream);
+                     }));
     uint32_t failed = 0;  // rays over kFFBigCap Gaussians at one point (ctl word 2): every output is written, those NaN
-    HIP_TRY(hipMemcpy(&failed, c->q_ff_ctl.get() + 2, sizeof(failed), hipMemcpyDeviceToHost), "hipMemcpy(query results)");
+    VR_TRY(copy(&failed, c->q_ff_ctl.get() + 2, 1, hipMemcpyDeviceToHost, "query results"));
     if (failed)
         return fail(VR_ERR_OVERFLOW, "vr_query_free_flight: " + std::to_string(failed) + " rays cross more than " +
                                          std::to_string(kFFBigCap) + " Gaussians overlapping one point (their results are NaN)");

@@ -69,16 +69,23 @@ __device__ __forceinline__ Ray primary_ray(const RenderArgs& A, int x, int y) {
     return make_ray(o0, o1, o2, d0, d1, d2);
 }
 
-// Ray grid (vr_render_rays): the caller's ray of pixel (x, y), a vr_ray row (32 B = two 16-B loads: {origin, tmax},
-// {direction, unit}; tmax is not read). The direction is normalised as the Ray constructor does (make_ray) unless
-// `unit` says it already was, as the queries take their rays (vr_query.hip). False: a non-finite origin, or a
-// direction whose squared norm is 0, NaN or infinite (the pixel gets NaN and spawns nothing).
-__device__ __forceinline__ bool grid_ray(const GridArgs& A, int x, int y, Ray& r) {
-    const float4* p = A.grid.rays + 2 * ((size_t)y * A.width + (size_t)x);
+// A caller's ray, as the ray grids and the mixture queries take theirs: a vr_ray row (32 B = two 16-B loads:
+// {origin, tmax}, {direction, unit}). The direction is normalised as the Ray constructor does (make_ray, ray.h:11-12)
+// unless `unit` says it already was (a Ray object's: normalising twice would move it by an ulp). False: a non-finite
+// origin, or a direction whose squared norm is 0, NaN or infinite.
+__device__ __forceinline__ bool decode_ray(const float4* p, Ray& r, float& tmax) {
     const float4 a = p[0], b = p[1];
+    tmax = a.w;
     const float s = dot3(b.x, b.y, b.z, b.x, b.y, b.z);
     r = b.w != 0.0f ? Ray{a.x, a.y, a.z, b.x, b.y, b.z} : make_ray(a.x, a.y, a.z, b.x, b.y, b.z);
     return isfinite(a.x) && isfinite(a.y) && isfinite(a.z) && s > 0.0f && isfinite(s);
+}
+
+// Ray grid (vr_render_rays): the caller's ray of pixel (x, y) (decode_ray; tmax is not used). False: the pixel gets
+// NaN and spawns nothing.
+__device__ __forceinline__ bool grid_ray(const GridArgs& A, int x, int y, Ray& r) {
+    float tmax;
+    return decode_ray(A.grid.rays + 2 * ((size_t)y * A.width + (size_t)x), r, tmax);
 }
 
 // The ray a pixel marches. The source is a compile-time choice: RAYS = false is the camera (primary_ray, `ok`

@@ -8,7 +8,7 @@
 // (query_grad_kernel / query_grad_finish_kernel: f32 decisions, double arithmetic per hit, double atomic adds)
 // and with respect to the ray (query_ray_grad_kernel: the same per-hit arithmetic, summed per ray in registers);
 // for the last, the gradient of sigma with respect to the Gaussians (albedo included) and to the points
-// (query_sigma_grad_kernel / query_sigma_grad_points_kernel / query_sigma_grad_finish_kernel: the forward's walk and
+// (query_sigma_grad_kernel / query_sigma_grad_points_kernel / query_grad_finish_kernel: the forward's walk and
 // f32 decision, double per active Gaussian, double atomic adds per Gaussian, register sums per point).
 //
 // Floating point: a query is an API for fidelity, so every Gaussian is tested with the exact forms of
@@ -239,6 +239,8 @@ struct GradOp : QueryOp<GradOp, true> {
         }
         return true;
     }
+    // (ProfileGradOp::redo has a copy of the take-back: through a shared helper the resource listing stayed but the
+    // three stack pushes below gained a move each, and this query ran 0.4 % slower on 1000_random, 315.8 against 314.5 ms)
     __device__ __forceinline__ void redo(const RenderArgs& A, uint32_t id, const Ray& r, float tmax, float lim, int* stack) {
         if (cnt > 0) {
             uint32_t left = cnt;
@@ -398,39 +400,57 @@ __global__ void __launch_bounds__(kQBlock) query_ray_grad_kernel(RenderArgs A, c
     query_walk(A, n, next, refill, op);
 }
 
-// Staging row j (tree order, per unit density, in M's space) -> the caller's row gauss_order[j]: d/d mean[3],
-// d/d cov {xx, xy, xz, yy, yz, zz}, d/d density. T = rho sum U, G_Sigma = -M G_M M - T M / 2, all in double and
-// rounded to f32 once; an off-diagonal stored number stands at (i, j) and (j, i), hence twice G_Sigma[i][j].
+// Staging row j (tree order, in M's space, W doubles) -> the caller's row gauss_order[j] (W floats): d/d mean[3],
+// d/d cov {xx, xy, xz, yy, yz, zz}, d/d density and, for W = 11, d/d albedo. T = rho U, G_Sigma = -M G_M M - T M / 2,
+// all in double and rounded to f32 once; an off-diagonal stored number stands at (i, j) and (j, i), hence twice
+// G_Sigma[i][j]. The two widths are the two stagings, each with its own expressions (they decide signed zeros):
+//   W = 10 (the transmittance and profile gradients): g_mean, G_M and U are staged per unit density, rho multiplies here;
+//   W = 11 (the sigma gradient): they carry the density already, and every output gets + 0.0.
+template <int W>
 __global__ void __launch_bounds__(256) query_grad_finish_kernel(const GaussianRecord* __restrict__ gauss,
                                                                 const uint32_t* __restrict__ order,
                                                                 const double* __restrict__ acc, uint32_t n,
                                                                 float* __restrict__ grad) {
+    static_assert(W == 10 || W == 11, "a staging row is 10 or 11 doubles");
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
     if (j >= n) return;
     const GRec g = load_rec(gauss, (int)j);
-    const double* a = acc + 10 * (size_t)j;
+    const double* a = acc + W * (size_t)j;
     const double rho = g.density, U = a[9], T = rho * U;
+    auto staged = [&](int k) {
+        if constexpr (W == 10) return rho * a[k];
+        else return a[k];
+    };
     const double M[3][3] = {{g.m00, g.m01, g.m02}, {g.m01, g.m11, g.m12}, {g.m02, g.m12, g.m22}};
-    const double G[3][3] = {{rho * a[3], rho * a[4], rho * a[5]},
-                            {rho * a[4], rho * a[6], rho * a[7]},
-                            {rho * a[5], rho * a[7], rho * a[8]}};
+    const double G[3][3] = {{staged(3), staged(4), staged(5)}, {staged(4), staged(6), staged(7)}, {staged(5), staged(7), staged(8)}};
     double MG[3][3], S[3][3];
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) MG[r][c] = M[r][0] * G[0][c] + M[r][1] * G[1][c] + M[r][2] * G[2][c];
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) S[r][c] = -(MG[r][0] * M[0][c] + MG[r][1] * M[1][c] + MG[r][2] * M[2][c]) - 0.5 * T * M[r][c];
-    float* out = grad + 10 * (size_t)order[j];
-    // (+ 0.0: a Gaussian no ray hit gets +0, not the -0 of -(0) - 0)
-    out[0] = (float)(rho * a[0]);
-    out[1] = (float)(rho * a[1]);
-    out[2] = (float)(rho * a[2]);
+    float* out = grad + W * (size_t)order[j];
+    // (+ 0.0: a Gaussian that nothing hit gets +0, not the -0 of -(0) - 0)
+    if constexpr (W == 10) {
+        out[0] = (float)(rho * a[0]);
+        out[1] = (float)(rho * a[1]);
+        out[2] = (float)(rho * a[2]);
+    } else {
+        out[0] = (float)(a[0] + 0.0);
+        out[1] = (float)(a[1] + 0.0);
+        out[2] = (float)(a[2] + 0.0);
+    }
     out[3] = (float)(S[0][0] + 0.0);
     out[4] = (float)(2.0 * S[0][1] + 0.0);
     out[5] = (float)(2.0 * S[0][2] + 0.0);
     out[6] = (float)(S[1][1] + 0.0);
     out[7] = (float)(2.0 * S[1][2] + 0.0);
     out[8] = (float)(S[2][2] + 0.0);
-    out[9] = (float)U;
+    if constexpr (W == 10) {
+        out[9] = (float)U;
+    } else {
+        out[9] = (float)(U + 0.0);
+        out[10] = (float)(a[10] + 0.0);
+    }
 }
 
 // Sorted keys -> the caller's arrays: t, and ev = scene_index << 1 | entering.
@@ -731,40 +751,6 @@ __global__ void __launch_bounds__(kQBlock) query_sigma_grad_points_kernel(Render
     sigma_grad_point<false, true>(A, xyz, weight_as, n, acc, grad_xyz);
 }
 
-// Staging row j (tree order, in M's space) -> the caller's row gauss_order[j]: d/d mean[3], d/d cov {xx, xy, xz, yy,
-// yz, zz}, d/d density, d/d albedo. query_grad_finish_kernel's arithmetic (the staged g_mean and G_M carry the density
-// already): T = rho U, G_Sigma = -M G_M M - T M / 2, all in double and rounded to f32 once.
-__global__ void __launch_bounds__(256) query_sigma_grad_finish_kernel(const GaussianRecord* __restrict__ gauss,
-                                                                      const uint32_t* __restrict__ order,
-                                                                      const double* __restrict__ acc, uint32_t n,
-                                                                      float* __restrict__ grad) {
-    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-    if (j >= n) return;
-    const GRec g = load_rec(gauss, (int)j);
-    const double* a = acc + 11 * (size_t)j;
-    const double U = a[9], T = (double)g.density * U;
-    const double M[3][3] = {{g.m00, g.m01, g.m02}, {g.m01, g.m11, g.m12}, {g.m02, g.m12, g.m22}};
-    const double G[3][3] = {{a[3], a[4], a[5]}, {a[4], a[6], a[7]}, {a[5], a[7], a[8]}};
-    double MG[3][3], S[3][3];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) MG[r][c] = M[r][0] * G[0][c] + M[r][1] * G[1][c] + M[r][2] * G[2][c];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) S[r][c] = -(MG[r][0] * M[0][c] + MG[r][1] * M[1][c] + MG[r][2] * M[2][c]) - 0.5 * T * M[r][c];
-    float* out = grad + 11 * (size_t)order[j];
-    // (+ 0.0: a Gaussian holding no point gets +0, not the -0 of -(0) - 0)
-    out[0] = (float)(a[0] + 0.0);
-    out[1] = (float)(a[1] + 0.0);
-    out[2] = (float)(a[2] + 0.0);
-    out[3] = (float)(S[0][0] + 0.0);
-    out[4] = (float)(2.0 * S[0][1] + 0.0);
-    out[5] = (float)(2.0 * S[0][2] + 0.0);
-    out[6] = (float)(S[1][1] + 0.0);
-    out[7] = (float)(2.0 * S[1][2] + 0.0);
-    out[8] = (float)(S[2][2] + 0.0);
-    out[9] = (float)(U + 0.0);
-    out[10] = (float)(a[10] + 0.0);
-}
-
 // Device-side packing of the Python mirror's torch inputs into vr_ray rows (tmax: one value per ray, or one
 // for all with tmax_stride = 0).
 __global__ void __launch_bounds__(256) query_pack_rays_kernel(const float* __restrict__ o, const float* __restrict__ d,
@@ -793,6 +779,15 @@ hipError_t query_transmittance(const RenderArgs& A, const vr_ray* rays, uint32_t
     return hipGetLastError();
 }
 
+// The staging rows of the scene's Gaussians (width 10 or 11 doubles each, query_grad_finish_kernel) -> grad, as many
+// floats per Gaussian. The profile gradient's unit calls it too.
+hipError_t query_grad_finish(const RenderArgs& A, const double* acc, int width, float* grad, hipStream_t s) {
+    const dim3 grid(((uint32_t)A.num_prims + 255u) / 256u), block(256);
+    if (width == 10) hipLaunchKernelGGL(dev::query_grad_finish_kernel<10>, grid, block, 0, s, A.gauss, A.gauss_order, acc, (uint32_t)A.num_prims, grad);
+    else hipLaunchKernelGGL(dev::query_grad_finish_kernel<11>, grid, block, 0, s, A.gauss, A.gauss_order, acc, (uint32_t)A.num_prims, grad);
+    return hipGetLastError();
+}
+
 // acc: 10 doubles per Gaussian of staging, zeroed here; grad: 10 floats per Gaussian, every one written.
 hipError_t query_transmittance_grad(const RenderArgs& A, const vr_ray* rays, const float* weight, uint32_t n, bool moving,
                                     double* acc, float* grad, uint32_t* next, int refill, int cus, hipStream_t s) {
@@ -805,9 +800,7 @@ hipError_t query_transmittance_grad(const RenderArgs& A, const vr_ray* rays, con
                            acc, next, refill);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(dev::query_grad_finish_kernel, dim3(((uint32_t)A.num_prims + 255u) / 256u), dim3(256), 0, s, A.gauss,
-                       A.gauss_order, acc, (uint32_t)A.num_prims, grad);
-    return hipGetLastError();
+    return query_grad_finish(A, acc, 10, grad, s);
 }
 
 // out: one vr_ray_grad row per ray, every one written.
@@ -842,9 +835,7 @@ hipError_t query_sigma_grad(const RenderArgs& A, const float* xyz, const float* 
         else hipLaunchKernelGGL(dev::query_sigma_grad_kernel<false>, grid, block, 0, s, A, xyz, weight_as, n, stage, grad_xyz);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(dev::query_sigma_grad_finish_kernel, dim3(((uint32_t)A.num_prims + 255u) / 256u), dim3(256), 0, s, A.gauss,
-                       A.gauss_order, stage, (uint32_t)A.num_prims, grad);
-    return hipGetLastError();
+    return query_grad_finish(A, stage, 11, grad, s);
 }
 
 // counts: n + 1 words of scratch; offsets: n + 1 words (exclusive scan of the counts, offsets[n] = the

@@ -17,22 +17,14 @@ constexpr int kQBlock = 256;
 constexpr int kQQueue = 8, kQSteps = 4;  // leaf FIFO entries; node steps / Gaussians per lane per wave iteration
 
 // ---- per-ray operations of the walk (ray_queue_walk's Op) ----
-// What the three share. vr_ray row i (32 B, 16-B aligned): {origin, tmax}, {direction, unit}. The direction is
-// normalised as the Ray constructor does (make_ray, ray.h:11-12) unless `unit` says it already was (a Ray
-// object's: normalising twice would move it by an ulp). Invalid: a non-finite origin, or a direction whose
-// squared norm is 0, NaN or infinite. PRUNE: rays with tmax <= 0 / NaN finish at once.
+// What the three share. vr_ray row i (16-B aligned), its normalisation and what makes it invalid: decode_ray
+// (vr_march.h). PRUNE: rays with tmax <= 0 / NaN finish at once.
 template <class Op, bool PRUNE>
 struct QueryOp {
     static constexpr bool kPrune = PRUNE;
     const vr_ray* __restrict__ rays;
     __device__ __forceinline__ int load(const RenderArgs& A, uint32_t id, Ray& r, float& tmax) {
-        const float4* p = reinterpret_cast<const float4*>(rays) + 2 * (size_t)id;
-        const float4 a = p[0], b = p[1];
-        tmax = a.w;
-        const float s = dot3(b.x, b.y, b.z, b.x, b.y, b.z);
-        const bool ok = isfinite(a.x) && isfinite(a.y) && isfinite(a.z) && s > 0.0f && isfinite(s);
-        r = b.w != 0.0f ? Ray{a.x, a.y, a.z, b.x, b.y, b.z} : make_ray(a.x, a.y, a.z, b.x, b.y, b.z);
-        if (!ok) return kRayInvalid;
+        if (!decode_ray(reinterpret_cast<const float4*>(rays) + 2 * (size_t)id, r, tmax)) return kRayInvalid;
         return (PRUNE && !(tmax > 0.0f)) || A.num_prims <= 0 ? kRayFinish : kRayWalk;  // gmm.h:518-519 / :462: no walk
     }
     __device__ __forceinline__ void on_node() {}

@@ -32,7 +32,7 @@ struct FlightOut {
 };
 
 // Ray `id` of the batch on rows S. Returns false if it is over the rows' capacity (nothing written).
-// vr_ray row: {origin, tmax (not read)}, {direction, unit}; validity and normalisation as QueryOp::load (vr_query.hip).
+// The row is decoded as decode_ray does (vr_march.h), in a copy: calling it moves both kernels' VGPRs (166 -> 162, 165 -> 168).
 __device__ __forceinline__ bool flight_ray(const RenderArgs& A, FFScratch<false>& S, const vr_ray* __restrict__ rays,
                                            const float* __restrict__ tau, uint32_t id, const FlightOut& out, int* stack) {
     const float4* p = reinterpret_cast<const float4*>(rays) + 2 * (size_t)id;

@@ -27,6 +27,7 @@
 // The head (p, M d, M p, A, B, C, m, c, k, u_a, erf(u_a sqrt(A / 2)), e^{-A u_a^2 / 2}) is computed once per hit, the
 // samples and weights are read from global memory per hit (a shared row is one address for the wave), and nothing is
 // kept per ray but the pointers. One walk per ray, pruned at the ray's largest sample.
+#include "../host/vr_kernels.h"  // query_grad_finish (vr_query.hip)
 #include "vr_query_common.h"
 
 namespace vr {
@@ -277,42 +278,6 @@ __global__ void __launch_bounds__(kQBlock) query_profile_grad_kernel(RenderArgs 
     query_walk(A, n, next, refill, op);
 }
 
-// Staging row j (tree order, per unit density, in M's space) -> the caller's row gauss_order[j]: the arithmetic of
-// query_grad_finish_kernel (vr_query.hip), whose copy this is (a kernel cannot be launched from another unit).
-// T = rho sum U, G_Sigma = -M G_M M - T M / 2, all in double and rounded to f32 once; an off-diagonal stored number
-// stands at (i, j) and (j, i), hence twice G_Sigma[i][j].
-__global__ void __launch_bounds__(256) query_profile_grad_finish_kernel(const GaussianRecord* __restrict__ gauss,
-                                                                        const uint32_t* __restrict__ order,
-                                                                        const double* __restrict__ acc, uint32_t n,
-                                                                        float* __restrict__ grad) {
-    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-    if (j >= n) return;
-    const GRec g = load_rec(gauss, (int)j);
-    const double* a = acc + 10 * (size_t)j;
-    const double rho = g.density, U = a[9], T = rho * U;
-    const double M[3][3] = {{g.m00, g.m01, g.m02}, {g.m01, g.m11, g.m12}, {g.m02, g.m12, g.m22}};
-    const double G[3][3] = {{rho * a[3], rho * a[4], rho * a[5]},
-                            {rho * a[4], rho * a[6], rho * a[7]},
-                            {rho * a[5], rho * a[7], rho * a[8]}};
-    double MG[3][3], S[3][3];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) MG[r][c] = M[r][0] * G[0][c] + M[r][1] * G[1][c] + M[r][2] * G[2][c];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) S[r][c] = -(MG[r][0] * M[0][c] + MG[r][1] * M[1][c] + MG[r][2] * M[2][c]) - 0.5 * T * M[r][c];
-    float* out = grad + 10 * (size_t)order[j];
-    // (+ 0.0: a Gaussian no ray hit gets +0, not the -0 of -(0) - 0)
-    out[0] = (float)(rho * a[0]);
-    out[1] = (float)(rho * a[1]);
-    out[2] = (float)(rho * a[2]);
-    out[3] = (float)(S[0][0] + 0.0);
-    out[4] = (float)(2.0 * S[0][1] + 0.0);
-    out[5] = (float)(2.0 * S[0][2] + 0.0);
-    out[6] = (float)(S[1][1] + 0.0);
-    out[7] = (float)(2.0 * S[1][2] + 0.0);
-    out[8] = (float)(S[2][2] + 0.0);
-    out[9] = (float)U;
-}
-
 }  // namespace dev
 
 // ---- launchers (host/vr_query_host.cpp) ----
@@ -340,9 +305,7 @@ hipError_t query_transmittance_profile_grad(const RenderArgs& A, const vr_ray* r
                            K, moving ? 1u : 0u, acc, next, refill);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(dev::query_profile_grad_finish_kernel, dim3(((uint32_t)A.num_prims + 255u) / 256u), dim3(256), 0, s, A.gauss,
-                       A.gauss_order, acc, (uint32_t)A.num_prims, grad);
-    return hipGetLastError();
+    return query_grad_finish(A, acc, 10, grad, s);  // (vr_query.hip: GradOp's staging, so its finish)
 }
 
 }  // namespace vr

@@ -538,27 +538,34 @@ class Device:
         rays[:, 4:7] = d
         return rays
 
+    def _check_kind(self, kind, *arrays):
+        """The torch tensors among a query's arguments live on this context's device (checked after the upload)."""
+        if kind.torch:
+            self._check_torch(*(x for x in arrays if _is_torch(x)))
+
+    def _query_rays(self, kind, origins, directions, tmax, unit=False, also=()):
+        """The vr_ray rows of a query's checked ray arguments; `also`: its further arrays, for _check_kind."""
+        self._check_kind(kind, origins, directions, tmax, *also)
+        if kind.torch:
+            rays, _ = self._pack_rays_torch(origins, directions, tmax)
+        else:
+            rays = self._pack_rays_numpy(origins, directions, tmax)
+        if unit:
+            rays[:, 7] = 1.0
+        return rays
+
     def query_transmittance(self, scene, origins, directions, tmax=float("inf"), return_tau=False):
         """GaussianMixtureModel::transmittance_up_to (gmm.h:517-578) for n rays: origins, directions (n, 3)
         float32, tmax a scalar or (n,) float32 (it broadcasts). Returns Tr (n,), or (Tr, tau) with the
         optical depth itself (Tr == expf(-tau) bit for bit). Rays with a non-finite origin or a zero /
         non-finite direction give NaN."""
-        torch_in = _query_ray_args(origins, directions, tmax)
+        kind = _ArrayKind(origins, _query_ray_args(origins, directions, tmax))
         self.upload(scene)
         n = origins.shape[0]
-        if torch_in:
-            import torch
-            self._check_torch(origins, directions, *([tmax] if _is_torch(tmax) else []))
-            rays, stream = self._pack_rays_torch(origins, directions, tmax)
-            tr = torch.empty(n, dtype=torch.float32, device=origins.device)
-            tau = torch.empty(n, dtype=torch.float32, device=origins.device) if return_tau else None
-            check(lib().vr_query_transmittance_device(self._h, rays.data_ptr(), n, tr.data_ptr(),
-                                                      tau.data_ptr() if return_tau else None, stream))
-        else:
-            rays = self._pack_rays_numpy(origins, directions, tmax)
-            tr = np.empty(n, np.float32)
-            tau = np.empty(n, np.float32) if return_tau else None
-            check(lib().vr_query_transmittance(self._h, rays.ctypes.data, n, fptr(tr), fptr(tau) if return_tau else None))
+        rays = self._query_rays(kind, origins, directions, tmax)
+        tr = kind.new(n)
+        tau = kind.new(n) if return_tau else None
+        kind.call("vr_query_transmittance", self._h, kind.ptr(rays), n, kind.ptr(tr), kind.ptr(tau))
         return (tr, tau) if return_tau else tr
 
     def query_transmittance_grad(self, scene, origins, directions, weights=None, tmax=float("inf"), moving_bounds=True):
@@ -569,32 +576,21 @@ class Device:
         respect to the stored number (it stands at (i, j) and (j, i)). moving_bounds=False holds each Gaussian's
         3-sigma entry / exit distances fixed (VR_GRAD_FROZEN_BOUNDS). Invalid rays and rays with tmax <= 0
         contribute nothing. Sums are double atomics: reproducible to the rounding of a double sum, not bit for bit."""
-        torch_in = _query_ray_args(origins, directions, tmax)
+        kind = _ArrayKind(origins, _query_ray_args(origins, directions, tmax))
         n = origins.shape[0]
         if weights is not None:
-            if _query_f32(weights, "weights", ()) != torch_in:
+            if _query_f32(weights, "weights", ()) != kind.torch:
                 raise ValueError("weights must be of the same kind as origins")
             if weights.shape[0] != n:
                 raise ValueError(f"weights has {weights.shape[0]} entries for {n} rays")
         self.upload(scene)
         N = scene.get_num_primitives()
-        flags = 0 if moving_bounds else L.VR_GRAD_FROZEN_BOUNDS
         if N == 0:
-            return origins.new_zeros((0, 10)) if torch_in else np.zeros((0, 10), np.float32)
-        if torch_in:
-            import torch
-            self._check_torch(origins, directions, *([tmax] if _is_torch(tmax) else []), *([] if weights is None else [weights]))
-            rays, stream = self._pack_rays_torch(origins, directions, tmax)
-            wt = None if weights is None else weights.contiguous()
-            grad = torch.empty((N, 10), dtype=torch.float32, device=origins.device)
-            check(lib().vr_query_transmittance_grad_device(self._h, rays.data_ptr(), None if wt is None else wt.data_ptr(), n,
-                                                           flags, grad.data_ptr(), stream))
-        else:
-            rays = self._pack_rays_numpy(origins, directions, tmax)
-            wt = None if weights is None else np.ascontiguousarray(weights)
-            grad = np.empty((N, 10), np.float32)
-            check(lib().vr_query_transmittance_grad(self._h, rays.ctypes.data, None if wt is None else fptr(wt), n, flags,
-                                                    fptr(grad)))
+            return kind.new((0, 10), zero=True)
+        rays = self._query_rays(kind, origins, directions, tmax, also=(weights,))
+        grad = kind.new((N, 10))
+        kind.call("vr_query_transmittance_grad", self._h, kind.ptr(rays), kind.ptr(kind.contiguous(weights)), n,
+                  0 if moving_bounds else L.VR_GRAD_FROZEN_BOUNDS, kind.ptr(grad))
         return grad
 
     def query_transmittance_ray_grad(self, scene, origins, directions, tmax=float("inf"), unit=False, moving_bounds=True):
@@ -608,24 +604,13 @@ class Device:
         moving_bounds=False holds each Gaussian's 3-sigma entry / exit distances fixed (VR_GRAD_FROZEN_BOUNDS).
         Invalid rays give NaN in every output, rays with tmax <= 0 or NaN zeros. Sums are per ray, in double, with
         no atomics. Inputs are numpy arrays or torch tensors on this context's device, never a mix."""
-        torch_in = _query_ray_args(origins, directions, tmax)
+        kind = _ArrayKind(origins, _query_ray_args(origins, directions, tmax))
         self.upload(scene)
         n = origins.shape[0]
-        flags = 0 if moving_bounds else L.VR_GRAD_FROZEN_BOUNDS
-        if torch_in:
-            import torch
-            self._check_torch(origins, directions, *([tmax] if _is_torch(tmax) else []))
-            rays, stream = self._pack_rays_torch(origins, directions, tmax)
-            if unit:
-                rays[:, 7] = 1.0
-            out = torch.empty((n, 8), dtype=torch.float32, device=origins.device)
-            check(lib().vr_query_transmittance_ray_grad_device(self._h, rays.data_ptr(), n, flags, out.data_ptr(), stream))
-        else:
-            rays = self._pack_rays_numpy(origins, directions, tmax)
-            if unit:
-                rays[:, 7] = 1.0
-            out = np.empty((n, 8), np.float32)
-            check(lib().vr_query_transmittance_ray_grad(self._h, rays.ctypes.data, n, flags, out.ctypes.data))
+        rays = self._query_rays(kind, origins, directions, tmax, unit)
+        out = kind.new((n, 8))
+        kind.call("vr_query_transmittance_ray_grad", self._h, kind.ptr(rays), n, 0 if moving_bounds else L.VR_GRAD_FROZEN_BOUNDS,
+                  kind.ptr(out))
         return out[:, 0:3], out[:, 4:7], out[:, 3], out[:, 7]
 
     def query_transmittance_profile(self, scene, origins, directions, t, return_tau=False):
@@ -634,26 +619,15 @@ class Device:
         distances shared by all rays, or (n, K), of the same kind (numpy or torch) as the rays. Returns Tr (n, K), or
         (Tr, tau). Column k has the bits of query_transmittance(..., tmax=t[:, k], return_tau=True). Samples may come
         in any order; a sample <= 0 or NaN gives tau = 0, Tr = 1, an invalid ray NaN in its whole row."""
-        torch_in = _query_ray_args(origins, directions, 0.0)
+        kind = _ArrayKind(origins, _query_ray_args(origins, directions, 0.0))
         n = origins.shape[0]
-        K, stride = _query_profile_args(t, "t", n, torch_in, shared_ok=True)
+        K, stride = _query_profile_args(t, "t", n, kind.torch, shared_ok=True)
         self.upload(scene)
-        if torch_in:
-            import torch
-            self._check_torch(origins, directions, t)
-            rays, stream = self._pack_rays_torch(origins, directions, float("inf"))
-            ts = t.contiguous()
-            tr = torch.empty((n, K), dtype=torch.float32, device=origins.device)
-            tau = torch.empty((n, K), dtype=torch.float32, device=origins.device) if return_tau else None
-            check(lib().vr_query_transmittance_profile_device(self._h, rays.data_ptr(), ts.data_ptr(), stride, n, K, tr.data_ptr(),
-                                                              tau.data_ptr() if return_tau else None, stream))
-        else:
-            rays = self._pack_rays_numpy(origins, directions, np.inf)
-            ts = np.ascontiguousarray(t)
-            tr = np.empty((n, K), np.float32)
-            tau = np.empty((n, K), np.float32) if return_tau else None
-            check(lib().vr_query_transmittance_profile(self._h, rays.ctypes.data, fptr(ts), stride, n, K, fptr(tr),
-                                                       fptr(tau) if return_tau else None))
+        rays = self._query_rays(kind, origins, directions, float("inf"), also=(t,))
+        tr = kind.new((n, K))
+        tau = kind.new((n, K)) if return_tau else None
+        kind.call("vr_query_transmittance_profile", self._h, kind.ptr(rays), kind.ptr(kind.contiguous(t)), stride, n, K,
+                  kind.ptr(tr), kind.ptr(tau))
         return (tr, tau) if return_tau else tr
 
     def query_transmittance_profile_grad(self, scene, origins, directions, t, weights=None, moving_bounds=True):
@@ -663,58 +637,32 @@ class Device:
         cov6, density), in query_transmittance_grad's layout and with its moving_bounds. One walk per ray and ten
         atomic adds per (ray, Gaussian) hit whatever K is; equal to query_transmittance_grad on the n * K expanded rays
         up to the rounding of double sums."""
-        torch_in = _query_ray_args(origins, directions, 0.0)
+        kind = _ArrayKind(origins, _query_ray_args(origins, directions, 0.0))
         n = origins.shape[0]
-        K, stride = _query_profile_args(t, "t", n, torch_in, shared_ok=True)
-        if weights is not None and _query_profile_args(weights, "weights", n, torch_in, shared_ok=False)[0] != K:
+        K, stride = _query_profile_args(t, "t", n, kind.torch, shared_ok=True)
+        if weights is not None and _query_profile_args(weights, "weights", n, kind.torch, shared_ok=False)[0] != K:
             raise ValueError(f"weights has {weights.shape[1]} columns for {K} samples")
         self.upload(scene)
         N = scene.get_num_primitives()
-        flags = 0 if moving_bounds else L.VR_GRAD_FROZEN_BOUNDS
         if N == 0:
-            return origins.new_zeros((0, 10)) if torch_in else np.zeros((0, 10), np.float32)
-        if torch_in:
-            import torch
-            self._check_torch(origins, directions, t, *([] if weights is None else [weights]))
-            rays, stream = self._pack_rays_torch(origins, directions, float("inf"))
-            ts = t.contiguous()
-            wt = None if weights is None else weights.contiguous()
-            grad = torch.empty((N, 10), dtype=torch.float32, device=origins.device)
-            check(lib().vr_query_transmittance_profile_grad_device(self._h, rays.data_ptr(), ts.data_ptr(), stride,
-                                                                   None if wt is None else wt.data_ptr(), n, K, flags,
-                                                                   grad.data_ptr(), stream))
-        else:
-            rays = self._pack_rays_numpy(origins, directions, np.inf)
-            ts = np.ascontiguousarray(t)
-            wt = None if weights is None else np.ascontiguousarray(weights)
-            grad = np.empty((N, 10), np.float32)
-            check(lib().vr_query_transmittance_profile_grad(self._h, rays.ctypes.data, fptr(ts), stride,
-                                                            None if wt is None else fptr(wt), n, K, flags, fptr(grad)))
+            return kind.new((0, 10), zero=True)
+        rays = self._query_rays(kind, origins, directions, float("inf"), also=(t, weights))
+        grad = kind.new((N, 10))
+        kind.call("vr_query_transmittance_profile_grad", self._h, kind.ptr(rays), kind.ptr(kind.contiguous(t)), stride,
+                  kind.ptr(kind.contiguous(weights)), n, K, 0 if moving_bounds else L.VR_GRAD_FROZEN_BOUNDS, kind.ptr(grad))
         return grad
 
     def query_sigma(self, scene, points, return_active=False):
         """GaussianMixtureModel::evaluate_sigma (gmm.h:98-126) at n points (n, 3) float32, over the Gaussians
         whose 3-sigma ellipsoid holds the point. Returns sigma (n, 2) = (sigma_a, sigma_s), or (sigma,
         n_active) with the size of that set per point."""
-        torch_in = _query_point_args(points)
+        kind = _ArrayKind(points, _query_point_args(points))
         self.upload(scene)
         n = points.shape[0]
-        if torch_in:
-            import torch
-            self._check_torch(points)
-            pts = points.contiguous()
-            sig = torch.empty((n, 2), dtype=torch.float32, device=points.device)
-            act = torch.empty(n, dtype=torch.int32, device=points.device) if return_active else None
-            check(lib().vr_query_sigma_device(self._h, pts.data_ptr(), n, sig.data_ptr(),
-                                              act.data_ptr() if return_active else None,
-                                              torch.cuda.current_stream(points.device).cuda_stream))
-        else:
-            pts = np.ascontiguousarray(points)
-            sig = np.empty((n, 2), np.float32)
-            cnt = np.empty(n, np.uint32) if return_active else None
-            check(lib().vr_query_sigma(self._h, fptr(pts), n, fptr(sig),
-                                       cnt.ctypes.data_as(L.U32P) if return_active else None))
-            act = cnt.astype(np.int32) if return_active else None
+        self._check_kind(kind, points)
+        sig = kind.new((n, 2))
+        act = kind.new(n, np.int32) if return_active else None  # (the library's uint32 counts)
+        kind.call("vr_query_sigma", self._h, kind.ptr(kind.contiguous(points)), n, kind.ptr(sig), kind.ptr(act))
         return (sig, act) if return_active else sig
 
     def query_sigma_grad(self, scene, points, weights=None, gaussians=True, positions=False):
@@ -726,37 +674,23 @@ class Device:
         one asked for, or (gaussians, positions) for both; positions alone runs without a single atomic add. The active
         set is query_sigma's bit for bit; a point in no ellipsoid, or with a non-finite coordinate, contributes nothing
         and gets a zero row. The per-Gaussian sums are double atomics: reproducible to the rounding of a double sum."""
-        torch_in = _query_point_args(points)
+        kind = _ArrayKind(points, _query_point_args(points))
         n = points.shape[0]
         if not (gaussians or positions):
             raise ValueError("query_sigma_grad: ask for gaussians, positions or both")
         if weights is not None:
-            if _query_f32(weights, "weights", (2,)) != torch_in:
+            if _query_f32(weights, "weights", (2,)) != kind.torch:
                 raise ValueError("weights must be of the same kind as points")
             if weights.shape[0] != n:
                 raise ValueError(f"weights has {weights.shape[0]} rows for {n} points")
         self.upload(scene)
         N = scene.get_num_primitives()
-        if torch_in:
-            import torch
-            self._check_torch(points, *([] if weights is None else [weights]))
-            pts = points.contiguous()
-            wt = None if weights is None else weights.contiguous()
-            grad = torch.zeros((N, 11), dtype=torch.float32, device=points.device) if gaussians else None
-            gx = torch.zeros((n, 3), dtype=torch.float32, device=points.device) if positions else None
-            if n > 0 and (N > 0 or positions):
-                check(lib().vr_query_sigma_grad_device(self._h, pts.data_ptr(), None if wt is None else wt.data_ptr(), n,
-                                                       grad.data_ptr() if gaussians and N > 0 else None,
-                                                       gx.data_ptr() if positions else None,
-                                                       torch.cuda.current_stream(points.device).cuda_stream))
-        else:
-            pts = np.ascontiguousarray(points)
-            wt = None if weights is None else np.ascontiguousarray(weights)
-            grad = np.zeros((N, 11), np.float32) if gaussians else None
-            gx = np.zeros((n, 3), np.float32) if positions else None
-            if n > 0 and (N > 0 or positions):
-                check(lib().vr_query_sigma_grad(self._h, fptr(pts), None if wt is None else fptr(wt), n,
-                                                fptr(grad) if gaussians and N > 0 else None, fptr(gx) if positions else None))
+        self._check_kind(kind, points, weights)
+        grad = kind.new((N, 11), zero=True) if gaussians else None
+        gx = kind.new((n, 3), zero=True) if positions else None
+        if n > 0 and (N > 0 or positions):
+            kind.call("vr_query_sigma_grad", self._h, kind.ptr(kind.contiguous(points)), kind.ptr(kind.contiguous(weights)), n,
+                      kind.ptr(grad) if N > 0 else None, kind.ptr(gx))
         return (grad, gx) if gaussians and positions else grad if gaussians else gx
 
     def query_events(self, scene, origins, directions):
@@ -765,31 +699,25 @@ class Device:
         (float32, non-decreasing per ray), gaussian (int32 scene index) and entering (bool). Events of a ray with
         equal t come in scene order, entry before exit: deterministic, but not the tie order of the
         reference's std::sort."""
-        torch_in = _query_ray_args(origins, directions, 0.0)
+        kind = _ArrayKind(origins, _query_ray_args(origins, directions, 0.0))
         self.upload(scene)
         n = origins.shape[0]
         total = ctypes.c_uint64()
-        if torch_in:
+        rays = self._query_rays(kind, origins, directions, 0.0)
+        off = kind.new(n + 1, np.int32, zero=True)  # (the library's uint32 words)
+        if kind.torch:  # the device form: a count call, which synchronises, then a fill call on torch's stream
             import torch
-            self._check_torch(origins, directions)
-            rays, stream = self._pack_rays_torch(origins, directions, 0.0)
-            off = torch.zeros(n + 1, dtype=torch.int32, device=origins.device)  # (uint32 words)
-            check(lib().vr_query_events_count_device(self._h, rays.data_ptr(), n, off.data_ptr(), ctypes.byref(total)))
-            t = torch.empty(total.value, dtype=torch.float32, device=origins.device)
-            ev = torch.empty(total.value, dtype=torch.int32, device=origins.device)
-            check(lib().vr_query_events_fill_device(self._h, rays.data_ptr(), n, off.data_ptr(), t.data_ptr(),
-                                                    ev.data_ptr(), total.value, stream))
+            check(lib().vr_query_events_count_device(self._h, kind.ptr(rays), n, kind.ptr(off), ctypes.byref(total)))
+            t, ev = kind.new(total.value), kind.new(total.value, np.int32)
+            kind.call("vr_query_events_fill", self._h, kind.ptr(rays), n, kind.ptr(off), kind.ptr(t), kind.ptr(ev), total.value)
             return off.to(torch.int64) & 0xffffffff, t, ev >> 1, (ev & 1).to(torch.bool)
-        rays = self._pack_rays_numpy(origins, directions, 0.0)
-        off = np.zeros(n + 1, np.uint32)
-        check(lib().vr_query_events(self._h, rays.ctypes.data, n, off.ctypes.data_as(L.U32P), None, None, 0,
-                                    ctypes.byref(total)))
-        t = np.empty(total.value, np.float32)
-        ev = np.empty(total.value, np.uint32)
+        # the host form: one call without room for the events and, if there are any, the same call with room
+        kind.call("vr_query_events", self._h, kind.ptr(rays), n, kind.ptr(off), None, None, 0, ctypes.byref(total))
+        t, ev = kind.new(total.value), kind.new(total.value, np.uint32)
         if total.value:
-            check(lib().vr_query_events(self._h, rays.ctypes.data, n, off.ctypes.data_as(L.U32P), fptr(t),
-                                        ev.ctypes.data_as(L.U32P), total.value, ctypes.byref(total)))
-        return off.astype(np.int64), t, (ev >> 1).astype(np.int32), (ev & 1).astype(bool)
+            kind.call("vr_query_events", self._h, kind.ptr(rays), n, kind.ptr(off), kind.ptr(t), kind.ptr(ev), total.value,
+                      ctypes.byref(total))
+        return off.view(np.uint32).astype(np.int64), t, (ev >> 1).astype(np.int32), (ev & 1).astype(bool)
 
     def query_free_flight(self, scene, origins, directions, tau, unit=False, return_albedo=False, return_active=False):
         """One free-flight step per ray, MultiScatterGaussians::get_free_flight_distance (integrator.h:422-498):
@@ -799,37 +727,20 @@ class Device:
         the mixture first; then, if asked for, the albedo at the collision (gmm.h:128-143; 0 where t < 0) and the
         number of Gaussians active there (int32). Invalid rays and NaN targets give NaN. With query_transmittance
         (next-event estimation) and query_sigma this is a volumetric path tracer's kit."""
-        torch_in = _query_ray_args(origins, directions, tau)
+        kind = _ArrayKind(origins, _query_ray_args(origins, directions, tau))
         self.upload(scene)
         n = origins.shape[0]
-        if torch_in:
-            import torch
-            self._check_torch(origins, directions, *([tau] if _is_torch(tau) else []))
-            rays, stream = self._pack_rays_torch(origins, directions, 0.0)
-            if unit:
-                rays[:, 7] = 1.0
-            if _is_torch(tau):
-                tg = tau.reshape(-1).expand(n).contiguous()
-            else:
-                tg = torch.full((n,), float(tau), dtype=torch.float32, device=origins.device)
-            t = torch.empty(n, dtype=torch.float32, device=origins.device)
-            alb = torch.empty(n, dtype=torch.float32, device=origins.device) if return_albedo else None
-            act = torch.empty(n, dtype=torch.int32, device=origins.device) if return_active else None
-            check(lib().vr_query_free_flight_device(self._h, rays.data_ptr(), tg.data_ptr(), n, t.data_ptr(),
-                                                    alb.data_ptr() if return_albedo else None,
-                                                    act.data_ptr() if return_active else None, stream))
-        else:
-            rays = self._pack_rays_numpy(origins, directions, 0.0)
-            if unit:
-                rays[:, 7] = 1.0
+        rays = self._query_rays(kind, origins, directions, 0.0, unit, also=(tau,))
+        if not kind.torch:
             tg = np.ascontiguousarray(np.broadcast_to(np.asarray(tau, np.float32).reshape(-1), (n,)))
-            t = np.empty(n, np.float32)
-            alb = np.empty(n, np.float32) if return_albedo else None
-            cnt = np.empty(n, np.uint32) if return_active else None
-            check(lib().vr_query_free_flight(self._h, rays.ctypes.data, fptr(tg), n, fptr(t),
-                                             fptr(alb) if return_albedo else None,
-                                             cnt.ctypes.data_as(L.U32P) if return_active else None))
-            act = cnt.astype(np.int32) if return_active else None
+        elif _is_torch(tau):
+            tg = tau.reshape(-1).expand(n).contiguous()
+        else:
+            tg = kind.new(n).fill_(float(tau))
+        t = kind.new(n)
+        alb = kind.new(n) if return_albedo else None
+        act = kind.new(n, np.int32) if return_active else None  # (the library's uint32 counts)
+        kind.call("vr_query_free_flight", self._h, kind.ptr(rays), kind.ptr(tg), n, kind.ptr(t), kind.ptr(alb), kind.ptr(act))
         out = (t,) + ((alb,) if return_albedo else ()) + ((act,) if return_active else ())
         return out if len(out) > 1 else t
 
@@ -889,6 +800,34 @@ class DeviceScene:
 
 def _is_torch(x):
     return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
+
+
+class _ArrayKind:
+    """The kind of a query's arrays, and what a query method needs of it: numpy arrays, which go to the host entry
+    point, or torch tensors on the context's device, which go to its `_device` form on torch's current stream."""
+
+    def __init__(self, like, torch_in):
+        self.torch, self.device = torch_in, like.device if torch_in else None
+
+    def new(self, shape, dtype=np.float32, zero=False):
+        if not self.torch:
+            return (np.zeros if zero else np.empty)(shape, dtype)
+        import torch
+        return (torch.zeros if zero else torch.empty)(shape, dtype=getattr(torch, np.dtype(dtype).name), device=self.device)
+
+    def contiguous(self, x):
+        return None if x is None else x.contiguous() if self.torch else np.ascontiguousarray(x)
+
+    def ptr(self, x):
+        if x is None:
+            return None
+        return x.data_ptr() if self.torch else x.ctypes.data_as(L.FP if x.dtype == np.float32 else L.U32P)
+
+    def call(self, name, *args):
+        if not self.torch:
+            return check(getattr(lib(), name)(*args))
+        import torch
+        check(getattr(lib(), name + "_device")(*args, torch.cuda.current_stream(self.device).cuda_stream))
 
 
 def _query_f32(x, name, shape_tail):

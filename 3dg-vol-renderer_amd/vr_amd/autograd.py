@@ -55,20 +55,32 @@ import torch
 from . import Device, Scene
 
 
+def _scene_of(mean, cov6, density, albedo, batch, what, device, resident):
+    """(Device, scene) of a forward: the parameters uploaded from where they are (resident: they must be on the device
+    of `batch`, "the rays" or "the points") or through a host Scene."""
+    params = (mean, cov6, density, albedo)
+    if resident:
+        for t, name in zip(params, ("mean", "cov6", "density", "albedo")):
+            if t.device != batch.device:
+                raise ValueError(f"{name} is on {t.device}, {what} on {batch.device}: a resident scene's "
+                                 f"parameters live on {what}' device")
+    dev = Device.get(device)
+    if resident:
+        return dev, dev.upload_gaussians(*(t.detach().to(torch.float32).contiguous() for t in params))
+    return dev, Scene.from_gaussians(*(t.detach().to("cpu", torch.float32).contiguous().numpy() for t in params))
+
+
+def _split_grad(g, like, needs):
+    """The (N, 10 or 11) gradient g as one tensor per parameter in `like` (mean, cov6, density[, albedo]), shaped and
+    typed as it; None where `needs` says no gradient is wanted."""
+    cols = (g[:, 0:3], g[:, 3:9], g[:, 9], g[:, 10:11])
+    return tuple(x.reshape(p.shape).to(device=p.device, dtype=p.dtype) if need else None for x, p, need in zip(cols, like, needs))
+
+
 class _OpticalDepth(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mean, cov6, density, albedo, origins, directions, tmax, device, moving_bounds, resident=False):
-        if resident:
-            for t, name in ((mean, "mean"), (cov6, "cov6"), (density, "density"), (albedo, "albedo")):
-                if t.device != origins.device:
-                    raise ValueError(f"{name} is on {t.device}, the rays on {origins.device}: a resident scene's "
-                                     "parameters live on the rays' device")
-        dev = Device.get(device)
-        if resident:
-            scene = dev.upload_gaussians(*(t.detach().to(torch.float32).contiguous() for t in (mean, cov6, density, albedo)))
-        else:
-            host = [t.detach().to("cpu", torch.float32).contiguous().numpy() for t in (mean, cov6, density, albedo)]
-            scene = Scene.from_gaussians(*host)
+        dev, scene = _scene_of(mean, cov6, density, albedo, origins, "the rays", device, resident)
         o, d = origins.detach().contiguous(), directions.detach().contiguous()
         tm = tmax.detach() if torch.is_tensor(tmax) else float(tmax)
         ctx.ray_needs = tuple(ctx.needs_input_grad[4:7])
@@ -91,10 +103,7 @@ class _OpticalDepth(torch.autograd.Function):
         if ctx.ray_jac is None or any(ctx.needs_input_grad[:3]):
             g = ctx.dev.query_transmittance_grad(ctx.scene, o, d, grad_tau.to(torch.float32).contiguous(), tm,
                                                  moving_bounds=ctx.moving)
-            mean, cov6, density = ctx.like
-            out = (g[:, 0:3].reshape(mean.shape), g[:, 3:9].reshape(cov6.shape), g[:, 9].reshape(density.shape))
-            out = tuple(x.to(device=p.device, dtype=p.dtype) if need else None
-                        for x, p, need in zip(out, ctx.like, ctx.needs_input_grad[:3]))
+            out = _split_grad(g, ctx.like, ctx.needs_input_grad[:3])
         rays = [None, None, None]
         if ctx.ray_jac is not None:
             g_o, g_d, g_t = ctx.ray_jac
@@ -129,17 +138,7 @@ def optical_depth_resident(mean, cov6, density, albedo, origins, directions, tma
 class _OpticalDepthProfile(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mean, cov6, density, albedo, origins, directions, t, device, moving_bounds, resident):
-        if resident:
-            for p, name in ((mean, "mean"), (cov6, "cov6"), (density, "density"), (albedo, "albedo")):
-                if p.device != origins.device:
-                    raise ValueError(f"{name} is on {p.device}, the rays on {origins.device}: a resident scene's "
-                                     "parameters live on the rays' device")
-        dev = Device.get(device)
-        if resident:
-            scene = dev.upload_gaussians(*(p.detach().to(torch.float32).contiguous() for p in (mean, cov6, density, albedo)))
-        else:
-            host = [p.detach().to("cpu", torch.float32).contiguous().numpy() for p in (mean, cov6, density, albedo)]
-            scene = Scene.from_gaussians(*host)
+        dev, scene = _scene_of(mean, cov6, density, albedo, origins, "the rays", device, resident)
         o, d, ts = origins.detach().contiguous(), directions.detach().contiguous(), t.detach().contiguous()
         _, tau = dev.query_transmittance_profile(scene, o, d, ts, return_tau=True)
         ctx.dev, ctx.scene, ctx.rays, ctx.moving = dev, scene, (o, d, ts), bool(moving_bounds)
@@ -154,10 +153,7 @@ class _OpticalDepthProfile(torch.autograd.Function):
         if any(ctx.needs_input_grad[:3]):
             g = ctx.dev.query_transmittance_profile_grad(ctx.scene, o, d, ts, grad_tau.to(torch.float32).contiguous(),
                                                          moving_bounds=ctx.moving)
-            mean, cov6, density = ctx.like
-            out = (g[:, 0:3].reshape(mean.shape), g[:, 3:9].reshape(cov6.shape), g[:, 9].reshape(density.shape))
-            out = tuple(x.to(device=p.device, dtype=p.dtype) if need else None
-                        for x, p, need in zip(out, ctx.like, ctx.needs_input_grad[:3]))
+            out = _split_grad(g, ctx.like, ctx.needs_input_grad[:3])
         return out + (None,) * 7
 
 
@@ -182,17 +178,7 @@ def optical_depth_profile_resident(mean, cov6, density, albedo, origins, directi
 class _Sigma(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mean, cov6, density, albedo, points, device, resident):
-        if resident:
-            for t, name in ((mean, "mean"), (cov6, "cov6"), (density, "density"), (albedo, "albedo")):
-                if t.device != points.device:
-                    raise ValueError(f"{name} is on {t.device}, the points on {points.device}: a resident scene's "
-                                     "parameters live on the points' device")
-        dev = Device.get(device)
-        if resident:
-            scene = dev.upload_gaussians(*(t.detach().to(torch.float32).contiguous() for t in (mean, cov6, density, albedo)))
-        else:
-            host = [t.detach().to("cpu", torch.float32).contiguous().numpy() for t in (mean, cov6, density, albedo)]
-            scene = Scene.from_gaussians(*host)
+        dev, scene = _scene_of(mean, cov6, density, albedo, points, "the points", device, resident)
         pts = points.detach().contiguous()
         ctx.dev, ctx.scene, ctx.pts = dev, scene, pts
         ctx.like = (mean, cov6, density, albedo)
@@ -209,9 +195,7 @@ class _Sigma(torch.autograd.Function):
                                            gaussians=need_g, positions=need_x)
             g, gx = got if need_g and need_x else (got, None) if need_g else (None, got)
             if need_g:
-                cols = (g[:, 0:3], g[:, 3:9], g[:, 9], g[:, 10])
-                out = tuple(x.reshape(p.shape).to(device=p.device, dtype=p.dtype) if need else None
-                            for x, p, need in zip(cols, ctx.like, ctx.needs_input_grad[:4]))
+                out = _split_grad(g, ctx.like, ctx.needs_input_grad[:4])
             if need_x:
                 gx = gx.to(ctx.pts_dtype)
         return out + (gx, None, None)
