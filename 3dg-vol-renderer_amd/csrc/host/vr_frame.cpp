@@ -104,10 +104,12 @@ vr_status vr::fill_scene_args(vr_ctx* c, const vr_render_params* p, uint32_t W, 
     A.gauss = sd.gauss.get();
     A.wrec = sd.wrec_pd ? sd.wrec.get() : nullptr;
     A.nodes = sd.nodes.get();
+    // Invariant of both tree builders (upload_half_nodes, lbvh_build under `half`): hnodes and hnodes4 exist together
+    // or not at all, so hnodes4 != nullptr alone says that the scene has its f16 trees (secondary_launch).
     A.hnodes = sd.hnodes.get();
     A.hnodes4 = sd.hnodes4.get();
     A.hnodes4s = sd.hnodes4s ? sd.hnodes4s.get() : sd.hnodes4.get();
-    A.hnodes4t = (VR_SEC_SOA && sd.hnodes4s) ? sd.hnodes4s.get() + sd.num_nodes4 : nullptr;
+    A.hnodes4t = sd.hnodes4s ? sd.hnodes4s.get() + sd.num_nodes4 : nullptr;  // (upload_secondary_tree: 2 n nodes)
     A.hnodes4w = sd.hnodes4w.get();
     A.hn4_parent = sd.parent4.get();
     A.prim_node4 = sd.prim_node4.get();

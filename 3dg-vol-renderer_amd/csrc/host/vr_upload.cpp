@@ -257,14 +257,14 @@ vr_status upload_secondary_tree(vr_ctx* c) {
     DevBuf<uint8_t> depth;
     DevBuf<float> nbox;
     DevBuf<uint32_t> maxd;
-    // n nodes as refit (HNode4), then (VR_SEC_SOA) the same n nodes with their boxes laid out per axis for the
-    // secondary kernel's node step (soa_nodes_kernel)
-    hipError_t e = s.hnodes4s.try_alloc((VR_SEC_SOA ? 2 : 1) * n);
+    // n nodes as refit (HNode4), then the same n nodes with their boxes laid out per axis for the secondary kernel's
+    // node step (soa_nodes_kernel)
+    hipError_t e = s.hnodes4s.try_alloc(2 * n);
     if (e == hipSuccess) e = depth.try_alloc(n);
     if (e == hipSuccess) e = nbox.try_alloc(n * 6);
     if (e == hipSuccess) e = maxd.try_alloc(1);
     if (e == hipSuccess)
-        e = gauss_refit_secondary(s.hnodes4.get(), s.hnodes4s.get(), VR_SEC_SOA ? s.hnodes4s.get() + n : nullptr, (uint32_t)n,
+        e = gauss_refit_secondary(s.hnodes4.get(), s.hnodes4s.get(), s.hnodes4s.get() + n, (uint32_t)n,
                                   s.gauss.get(), s.parent4.get(), depth.get(), nbox.get(), maxd.get(), s.hn_center, s.hn_scale,
                                   (float)std::sqrt(d2), c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -624,7 +624,7 @@ vr_status vr_debug_tree(vr_ctx* c, int32_t array, void* out, size_t cap, size_t*
         case VR_TREE_HNODES4S: src = s.hnodes4s.get(), count = n4, elem = sizeof(HNode4); break;
         case VR_TREE_HNODES4W: src = s.hnodes4w.get(), count = n4, elem = sizeof(HNode4); break;
         case VR_TREE_HNODES4T:  // the second half of the tight tree's allocation (upload_secondary_tree)
-            src = (VR_SEC_SOA && s.hnodes4s) ? s.hnodes4s.get() + n4 : nullptr, count = n4, elem = sizeof(HNode4);
+            src = s.hnodes4s ? s.hnodes4s.get() + n4 : nullptr, count = n4, elem = sizeof(HNode4);
             break;
         case VR_TREE_PARENT4: src = s.parent4.get(), count = n4, elem = sizeof(int32_t); break;
         case VR_TREE_PRIM_NODE4: src = s.prim_node4.get(), count = np, elem = sizeof(int32_t); break;

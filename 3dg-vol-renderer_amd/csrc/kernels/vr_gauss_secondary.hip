@@ -37,49 +37,56 @@
 #define VR_WW_STACK 14  // LDS traversal-stack entries per lane (deeper ones spill to the global overflow)
 #endif
 #ifndef VR_WW_WAVES
-#define VR_WW_WAVES 7  // waves per SIMD (launch bounds: 72 VGPRs at 7; A/B at C4: 7 + 14-entry stack 95.6 ms, 6 + 18 99.2 ms)
+#define VR_WW_WAVES 7  // waves per SIMD of the whitened form (launch bounds: 72 VGPRs at 7; A/B at C4: 7 + 14-entry stack
+                       // 95.6 ms, 6 + 18 99.2 ms)
 #endif
 #ifndef VR_WW_QCAP
 #define VR_WW_QCAP 9  // leaf queue of the persistent kernel: the head entry + an LDS ring of QCAP - 1 (1 + 2^k)
-#endif
-// The ray's dependent load chain: loads whose address is known long before their data is needed are
-// issued early into registers that are dead at that time (A/B at C4, round 7: secondary stage 75.9 -> 74.8 ms with both).
-#ifndef VR_SEC_START_ENTRY
-#define VR_SEC_START_ENTRY 1  // a ray's start node and its first climb from one 8-B gather (RecStart), next to the record's words
-#endif
-#ifndef VR_SEC_UP_AHEAD
-#define VR_SEC_UP_AHEAD 1  // the climb's parent entry is loaded one level ahead (SecRay::up)
 #endif
 
 namespace vr {
 namespace dev {
 
 // ---------------------------------------------------------------------------------------------
-// Stage 2: persistent "while-while" tracing of all secondary rays, per-lane ray refill.
+// The persistent kernel (secondary_ww_kernel): "while-while" tracing of all secondary rays with postponed leaves.
 //
-// Secondary rays have very uneven lengths (the optical-depth cut-off ends a ray after a few
-// dense hits, a ray through empty space walks many nodes), so one ray per lane per round leaves
-// most of a wave idle behind its slowest lane. Here every wave owns a contiguous chunk of ray
-// ids (sample-major: neighbouring pixels, same light / same env sample index) and each lane
-// pulls the next id from it the moment its ray completes; one loop iteration = one BVH node
-// pair (+ the primitives of a leaf child). Light rays whose result depends on the first event
-// past the light (a Gaussian straddling the light, or a pre-activated Gaussian the ray misses
-// through rounding) are rare; they go to a queue served by secondary_slow_kernel's exact
-// three-pass light_transmittance.
+// Secondary rays have very uneven lengths (the optical-depth cut-off ends a ray after a few dense hits, a ray through
+// empty space walks many nodes), so one ray per lane per launch would leave most of a wave idle behind its slowest
+// lane. One resident grid traces them all instead; each lane holds one ray at a time.
+//   * Claim units. The rays are handed out by record chunk (neighbouring records, light rays first, then the
+//     environment rays in env_order_kernel's direction order, so a wave's rays stay coherent). A wave claims the next
+//     unit with one atomic on A.ray_next: a whole chunk, or 1/2, 1/4, 1/8 of one when the launch has few chunks per
+//     resident wave (VR_WW_SPLIT_CPW). Its lanes take consecutive rays of the unit as they fall idle.
+//   * Refill and batched completions. Once VR_WW_REFILL lanes are idle the wave refills them in one pass: the rays
+//     completed since the last refill write their Tr (sec_finish), then every idle lane starts its next ray (sec_init,
+//     list_begin). A completed lane idles until then.
+//   * NODE and PRIM iterations. A wave never runs the node code and the primitive code in the same iteration. In a
+//     NODE iteration the lanes with room in their leaf queue take up to VR_WW_NODE_STEPS tree steps (sec_node4v /
+//     sec_node); leaf children are queued, not tested. In a PRIM iteration the lanes with a list member or a queued
+//     leaf test up to VR_WW_PRIM_STEPS primitives. The kind is whichever more lanes can use (VR_WW_PRIM_BIAS), never one
+//     that no lane can use. So a wave neither waits for its longest ray nor stalls its walking lanes on a leaf visit.
+// Light rays whose result depends on the first event past the light (a Gaussian straddling the light, or a
+// pre-activated Gaussian the ray misses through rounding) are rare; they go to a queue served by
+// secondary_slow_kernel's exact three-pass light_transmittance.
+//
+// The kernel's variants, <S, F, T>: S is the instrumented build (vr_count_work): the same schedule, counting its own
+// work. The form F of the primitive test and the tree T the walk reads are the scene's (secondary_launch).
 // ---------------------------------------------------------------------------------------------
-#ifdef VR_DIAG_LEVELS
-// Diagnostic builds only: VR_DIAG_LEVELS = 1 counts the node steps of the rays that end uncut, 2 those of
-// the rays that reach their cut-off, by tree depth (secondary counters [8 + b]: depths 2b, 2b + 1; b = 7:
-// deeper). Depths of the 4-wide nodes from their parents (depth_kernel, before the secondary stage).
-__device__ uint8_t g_diag_depth[1u << 23];
-__global__ __launch_bounds__(256) void depth_kernel(const int32_t* __restrict__ parent, uint32_t n) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n || i >= (1u << 23)) return;
-    uint32_t d = 0;
-    for (int32_t x = (int32_t)i; x > 0; x = parent[x] & kNodeIndexMask) ++d;
-    g_diag_depth[i] = (uint8_t)min(d, 255u);
-}
-#endif
+enum class SecForm {
+    Whitened,  // RayMarchingGaussians on the whitened records (A.wrec): the credit scheme, no membership lookup
+    MForm,     // RayMarchingGaussians on the records' M forms (a scene with a non-positive-definite M): act_find
+    Pure,      // PureRayMarching: the M forms with the marched optical depth
+};
+enum class SecTree {
+    Wide4,    // the 4-wide f16 tree (per-axis copy, scene-normalised coordinates), from the record's start subtree
+    PairF32,  // the f32 child-pair tree from the root (scenes whose leaf boxes are too small for f16 boxes)
+};
+constexpr int kSecBlock = 256;           // lanes per workgroup
+constexpr int kSecStack = VR_WW_STACK;   // LDS traversal-stack entries per lane
+constexpr int kSecQcap = VR_WW_QCAP;     // leaf-queue entries per lane
+static_assert(kSecQcap >= 5 && ((kSecQcap - 1) & (kSecQcap - 2)) == 0, "VR_WW_QCAP: 1 + 2^k with k >= 2 (ring queue)");
+// Waves per SIMD of the launch bounds: PureRayMarching's marched depth does not fit 6 waves' registers without spills.
+constexpr int sec_waves(SecForm F) { return F == SecForm::Pure ? 5 : F == SecForm::Whitened ? VR_WW_WAVES : 6; }
 
 struct SecRay {
     Ray ray;
@@ -99,11 +106,7 @@ struct SecRay {
     uint32_t nsteps;  // instrumented build only: node steps taken by this ray
     // 4-wide walk: the parent entry of the subtree the ray walks (hn4_parent's form: the subtree's child slot + 1 in
     // bits 28-30), -1 at the root: the node of the next climb, loaded one climb ahead (sec_node4v).
-    // (VR_SEC_UP_AHEAD = 0: the root of that subtree, whose parent entry the climb loads.)
     int32_t up;
-#ifdef VR_DIAG_LEVELS  // diagnostic builds only: this ray's node steps per tree depth (2 levels per bucket)
-    uint32_t lv[8];
-#endif
     uint32_t rec;     // record index
     uint32_t slot;    // result slot s * rec_cap + rec in tr
 };
@@ -171,7 +174,7 @@ constexpr uint32_t kFilterMax = VR_SEC_FILTER_MAX;
 
 // One sorting group per record chunk: counting sort of the chunk's environment rays by direction key
 // (order inside a key is arbitrary: every ray's result is independent of when it is traced). A group
-// is one wave: BLOCK/64 chunks in flight per workgroup, wave-local LDS and no workgroup barriers; the
+// is one wave: 4 chunks in flight per workgroup of 256, wave-local LDS and no workgroup barriers; the
 // chunk's chain of dependent loads is the cost, not its arithmetic (C4: 1.56 ms; a workgroup per chunk 1.91).
 // One more bucket follows the direction cells: the rays the persistent kernel need not trace — those of padding
 // records, of records without a ray to trace (weight <= 0, sec_init) and, with A.sec_filter, those that reach
@@ -180,9 +183,9 @@ constexpr uint32_t kFilterMax = VR_SEC_FILTER_MAX;
 // Tr = 0 here, and A.env_count tells the persistent kernel how many rays come before them.
 // S: the instrumented build (vr_count_work) counts the filter's list tests and the rays it keeps back where the
 // persistent kernel counts its own.
-template <int BLOCK, bool S>
-__global__ __launch_bounds__(BLOCK) void env_order_kernel(RenderArgs A) {
-    constexpr int G = 64, kGroups = BLOCK / G;
+template <bool S>
+__global__ __launch_bounds__(256) void env_order_kernel(RenderArgs A) {
+    constexpr int G = 64, kGroups = 256 / G;
     constexpr uint32_t kKeyCap = 8192 / kGroups;  // keys kept in LDS per group; larger chunks recompute them
     constexpr uint32_t kRecMax = 1u << VR_CHUNK_SHIFT;  // records per chunk (A.chunk_rec)
     constexpr uint32_t kTail = kEnvCells;         // the bucket behind every direction cell
@@ -347,12 +350,14 @@ __global__ __launch_bounds__(BLOCK) void env_order_kernel(RenderArgs A) {
 }
 
 // Start ray `rem` of record chunk `chunk`. Returns false if the ray is already complete (Tr
-// written) or a padding id. norm: slab-test terms in the half nodes' scene-normalised
-// coordinates (HNode). start: the node the tree walk starts at (wide: the 4-wide walk, in the record's start subtree;
-// otherwise the root); the record's start entry is gathered here, next to its other words, so that it is no link
-// of the ray's load chain.
+// written) or a padding id. The 4-wide tree: slab-test terms in the half nodes' scene-normalised
+// coordinates (HNode). start: the node the tree walk starts at (the 4-wide walk: in the record's start subtree;
+// otherwise the root); the record's start entry (its node and that node's parent entry, for the first climb) is
+// gathered here, next to the record's other words, so that it is no link of the ray's load chain.
+template <SecTree T>
 __device__ __forceinline__ bool sec_init(const RenderArgs& A, uint32_t nrec, uint32_t chunk, uint32_t rem, SecRay& R,
-                                         int32_t& start, bool norm = false, bool wide = false) {
+                                         int32_t& start) {
+    constexpr bool norm = T == SecTree::Wide4, wide = T == SecTree::Wide4;
     uint32_t s, r;
     if (!ray_slot(A, chunk, rem, nrec, s, r)) return false;  // padding id
     R.slot = chunk * rays_per_chunk(A) + rem;
@@ -366,14 +371,7 @@ __device__ __forceinline__ bool sec_init(const RenderArgs& A, uint32_t nrec, uin
     }
     const uint4 meta = A.rec_meta[r];
     RecStart st{0, -1};  // (the root)
-    if (wide && A.rec_start != nullptr) {
-#if VR_SEC_START_ENTRY
-        st = A.rec_start[r];
-#else
-        st.node = A.rec_start[r].node;
-        if (VR_SEC_UP_AHEAD) st.up = A.hn4_parent[st.node];
-#endif
-    }
+    if (wide && A.rec_start != nullptr) st = A.rec_start[r];
     start = st.node;
     R.rec = r;
     R.cut = A.tau_cut;  // (a select of the two addresses would make this one flat load)
@@ -386,10 +384,7 @@ __device__ __forceinline__ bool sec_init(const RenderArgs& A, uint32_t nrec, uin
     R.credit = 0.0f;
     R.hitmask = 0;
     R.nsteps = 0;
-    R.up = VR_SEC_UP_AHEAD ? st.up : st.node;
-#ifdef VR_DIAG_LEVELS
-    for (int b = 0; b < 8; ++b) R.lv[b] = 0;
-#endif
+    R.up = st.up;
     R.tau = 0.0f;
     R.needs_stop = false;
     if (s < (uint32_t)A.num_lights) {
@@ -453,7 +448,7 @@ __device__ __forceinline__ float marched_depth(const RenderArgs& A, const GRec& 
 //   RayMarchingGaussians: analytic segment depth; a light ray's Gaussian straddling the light
 //   needs the first event past the light (test_integrators.h:220-235) -> exact slow path.
 //   PureRayMarching: marched to t < dist (light) / t < last event (environment, b <= tlast).
-template <bool S, bool FAST, bool PURE>
+template <bool S, bool PURE>
 __device__ __forceinline__ void sec_add(const RenderArgs& A, SecRay& R, const GRec& g, const Quad& q, float lo, float b,
                                         Ctr& c) {
     if constexpr (S) c.v[kCtrOD]++;
@@ -466,19 +461,11 @@ __device__ __forceinline__ void sec_add(const RenderArgs& A, SecRay& R, const GR
         }
         return;
     }
-    if constexpr (FAST) {  // one optical-depth evaluation for light and environment lanes alike
-        const bool add = !R.light || b < R.lim;
-        R.needs_stop = R.needs_stop || (!add && lo < R.lim);
-        if (!R.light) R.lim = fmaxf(R.lim, b);
-        if (add) R.tau += optical_depth_chord(g, q, lo, b);  // [lo, b] lies on the 3-sigma chord
-    } else if (!R.light) {
-        R.tau += optical_depth(g, q, lo, b);
-        R.lim = fmaxf(R.lim, b);
-    } else if (b < R.lim) {
-        R.tau += optical_depth(g, q, lo, b);
-    } else if (lo < R.lim) {
-        R.needs_stop = true;
-    }
+    // one optical-depth evaluation for light and environment lanes alike
+    const bool add = !R.light || b < R.lim;
+    R.needs_stop = R.needs_stop || (!add && lo < R.lim);
+    if (!R.light) R.lim = fmaxf(R.lim, b);
+    if (add) R.tau += optical_depth_chord(g, q, lo, b);  // [lo, b] lies on the 3-sigma chord
 }
 
 // VR_DIAG_SKIP_TR_STORES: diagnostic builds only (tools_dbg, never the product library): the
@@ -517,22 +504,13 @@ __device__ __forceinline__ void to_fix(const RenderArgs& A, uint32_t slot, float
     }
 }
 
-// Ray complete: write its transmittance (or hand it to the exact slow path). WH: the scene's whitened
-// records (A.wrec); false: the M forms of the records (a scene with a non-positive-definite M).
-template <bool S, bool FAST, bool PURE, bool WH = !PURE>
+// Ray complete: write its transmittance (or hand it to the exact slow path).
+template <bool S, SecForm F>
 __device__ __forceinline__ void sec_finish(const RenderArgs& A, SecRay& R, Ctr& c) {
-#ifdef VR_DIAG_LEVELS
-    if constexpr (S)
-        if ((VR_DIAG_LEVELS == 2) == cut_reached<PURE>(R))
-            for (int b = 0; b < 8; ++b)
-                if (R.lv[b]) atomicAdd(A.work + kNumCtr + b, (unsigned long long)R.lv[b]);
-#elif !defined(VR_DIAG_WAVE_UTIL) && !defined(VR_DIAG_CYCLES)
+    constexpr bool PURE = F == SecForm::Pure, WH = F == SecForm::Whitened;
+#if !defined(VR_DIAG_WAVE_UTIL) && !defined(VR_DIAG_CYCLES)
     if constexpr (S) {  // secondary-stage diagnostics in otherwise unused counter slots
-#ifdef VR_DIAG_LIGHT  // diagnostic builds only: the light rays and their node steps instead of the cut rays'
-        if (R.light) {
-#else
         if (cut_reached<PURE>(R)) {
-#endif
             c.v[kCtrSteps]++;                 // rays ended by the optical-depth cut-off
             c.v[kCtrPrimQueries] += R.nsteps;  // ... and their node steps
         }
@@ -566,12 +544,12 @@ __device__ __forceinline__ void sec_finish(const RenderArgs& A, SecRay& R, Ctr& 
                 continue;
             }
             const GRec g = load_rec(A.gauss, j);
-            const Quad q = FAST ? quad_fast(g, R.ray) : quad(g, R.ray);
+            const Quad q = quad_fast(g, R.ray);
             float a, b;
-            if (FAST ? intersect_fast(q, a, b) : intersect(q, a, b)) continue;
+            if (intersect_fast(q, a, b)) continue;
             any = true;
             if constexpr (PURE) R.tau += marched_depth(A, g, R.ray, 0.0f, R.lim);
-            else if (!R.light) R.tau += FAST ? optical_depth_fast(g, q, 0.0f, R.lim) : optical_depth(g, q, 0.0f, R.lim);
+            else if (!R.light) R.tau += optical_depth_fast(g, q, 0.0f, R.lim);
             else break;
         }
         if (!PURE && R.light && (R.needs_stop || any)) {
@@ -617,70 +595,33 @@ __device__ __forceinline__ void sec_finish(const RenderArgs& A, SecRay& R, Ctr& 
     VR_TR_STORE(A, R.slot, expf(-R.tau));
 }
 
-// ---------------------------------------------------------------------------------------------
-// Stage 2 (default): persistent while-while tracing with postponed leaves.
-//
-// One ray per lane, but a wave never runs the node code and the primitive code in the same
-// iteration: every iteration is either a NODE iteration (lanes with room in their leaf queue take
-// one child-pair step; leaf children are queued, not tested) or a PRIM iteration (lanes with a
-// queued leaf test ONE primitive), whichever more lanes can use. A lane whose ray completes is
-// refilled from the wave's pool of ray ids (64 consecutive ids per atomic fetch: neighbouring
-// records, same light / env-sample index, so a wave's rays stay spatially coherent). This removes
-// the two divergence costs of one-ray-per-lane traversal: a wave no longer waits for its longest
-// ray, and a leaf visit no longer stalls the lanes that are still walking inner nodes.
-// ---------------------------------------------------------------------------------------------
-// FIFO of up to QCAP leaf refs + the leaf being tested. QCAP = 2 or 4: the first two entries live
-// in registers (q0, q1), entries 2 and 3 in the two LDS words per lane just above the traversal
-// stack (ext[0], ext[BLOCK]). QCAP = 1 + 2^k (k >= 2): the head entry in q0, the others in an
-// LDS ring of QCAP - 1 words above the stack, ring head in q1. A lane may take a NODE step while
-// the queue has room for the 2 leaves a step can add, so a lane holding queued leaves keeps
-// walking the tree.
-template <int QCAP>
-constexpr bool kQueueRing = QCAP > 4;
-template <int QCAP>
-constexpr int kQueueLds = kQueueRing<QCAP> ? QCAP - 1 : QCAP - 2;  // LDS words per lane of the queue
-
 // An int in LDS (address space 3). The traversal stack and leaf queue are reached through this type
 // so that a pop that may come from the LDS stack or the global overflow stays two typed loads (a
 // ds_read and a global_load) instead of one flat load whose wait covers every outstanding access.
 using LdsInt = __attribute__((address_space(3))) int;
 
+// FIFO of up to kSecQcap leaf refs + the leaf being tested: the head entry in q0, the others in an LDS ring of
+// kSecQcap - 1 words per lane above the traversal stack (`ext`), ring head in q1. A lane may take a NODE step while
+// the queue has room for the leaves a step can add, so a lane holding queued leaves keeps walking the tree.
+constexpr int kQueueLds = kSecQcap - 1;  // LDS words per lane of the queue
+
 struct LeafQueue {
     int32_t q0, q1;
     int n;
     uint32_t j, end;  // current primitive range [j, end)
-    // branch-free for the register entries: writes r at slot `idx` (no slot matches idx < 0)
-    template <int QCAP, int BLOCK>
+    // branch-free for the register entry: writes r at slot `idx` (no slot matches idx < 0)
     __device__ __forceinline__ void put(int idx, int32_t r, LdsInt* ext) {
-        if constexpr (kQueueRing<QCAP>) {
-            q0 = idx == 0 ? r : q0;
-            if (idx >= 1) ext[((q1 + idx - 1) & (QCAP - 2)) * BLOCK] = r;
-        } else {
-            q0 = idx == 0 ? r : q0;
-            q1 = idx == 1 ? r : q1;
-            if constexpr (QCAP > 2)
-                if (idx >= 2) ext[(idx - 2) * BLOCK] = r;
-        }
+        q0 = idx == 0 ? r : q0;
+        if (idx >= 1) ext[((q1 + idx - 1) & (kSecQcap - 2)) * kSecBlock] = r;
     }
     __device__ __forceinline__ bool has_prim() const { return j < end || n > 0; }
-    template <int QCAP, int BLOCK>
     __device__ __forceinline__ uint32_t next(LdsInt* ext) {  // requires has_prim()
         if (j == end) {
             j = leaf_first(q0);
             end = j + leaf_count(q0);
-            if constexpr (kQueueRing<QCAP>) {
-                if (n > 1) {
-                    q0 = ext[(q1 & (QCAP - 2)) * BLOCK];
-                    q1 = (q1 + 1) & (QCAP - 2);
-                }
-            } else {
-                q0 = q1;
-                if constexpr (QCAP > 2) {
-                    if (n > 2) {
-                        q1 = ext[0];
-                        if (n > 3) ext[0] = ext[BLOCK];
-                    }
-                }
+            if (n > 1) {
+                q0 = ext[(q1 & (kSecQcap - 2)) * kSecBlock];
+                q1 = (q1 + 1) & (kSecQcap - 2);
             }
             --n;
         }
@@ -688,96 +629,75 @@ struct LeafQueue {
     }
 };
 
-// Traversal-stack entries past the STACK held in LDS spill to the global overflow buffer, laid
-// out [depth - STACK][lane of the resident grid]: the lanes of a wave that are at the same depth
+// Traversal-stack entries past the kSecStack held in LDS spill to the global overflow buffer, laid
+// out [depth - kSecStack][lane of the resident grid]: the lanes of a wave that are at the same depth
 // share cache lines, and the shallow overflow levels every deep walk touches stay a small, dense,
 // L2-resident region (a per-lane [lane][depth] layout gives every lane its own line per level).
-template <int BLOCK, int STACK>
 __device__ __forceinline__ uint32_t ovf_slot(const RenderArgs& A, int sp) {
-    return (uint32_t)(sp - STACK) * A.stack_ovf_lanes + blockIdx.x * BLOCK + threadIdx.x;
+    return (uint32_t)(sp - kSecStack) * A.stack_ovf_lanes + blockIdx.x * kSecBlock + threadIdx.x;
 }
 
 // One step of the 4-wide traversal without a sorting network (measured against one with a near-to-far sorting
 // network of the children, round 3: 102.4 -> 99.2 ms at C4): the nearest inner child is walked next
 // (a min-reduction over the inner children's entry distances), the other inner children are pushed
 // and the leaf children queued in the node's child order. Empty slots carry NaN boxes, so the slab
-// test alone rejects them. Ring queues only (QCAP = 1 + 2^k).
-template <int BLOCK, bool S, int QCAP, int STACK, bool SOA = false>
+// test alone rejects them. The node is read from the per-axis copy of the tree (A.hnodes4t, soa_nodes_kernel's layout).
+template <bool S>
 __device__ __forceinline__ void sec_node4v(const RenderArgs& A, SecRay& R, LdsInt* stack, int& sp, int& node, LeafQueue& Q,
                                            Ctr& c) {
-    static_assert(kQueueRing<QCAP>, "sec_node4v: ring leaf queue");
     if constexpr (S) {
         c.v[kCtrNodes]++;
         ++R.nsteps;
     }
     const int skip = node >> 28;  // a climb's node: the finished child's slot + 1 (0: none)
-#ifdef VR_DIAG_LEVELS
-    R.lv[min((int)g_diag_depth[node & kNodeIndexMask] >> 1, 7)]++;
-#endif
-    const uint4* np = reinterpret_cast<const uint4*>((SOA ? A.hnodes4t : A.hnodes4s) + (node & kNodeIndexMask));
+    const uint4* np = reinterpret_cast<const uint4*>(A.hnodes4t + (node & kNodeIndexMask));
     const uint4 q0 = np[0], q1 = np[1], q2 = np[2], rf = np[3];
     const uint32_t w[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
     const int32_t ref[4] = {(int32_t)rf.x, (int32_t)rf.y, (int32_t)rf.z, (int32_t)rf.w};
-    // SOA (soa_nodes_kernel's layout): per axis, the ray's near bound word pair and far bound word pair, picked once
-    // for the four children by the sign of its direction: for 1/d > 0 the near slab is the min (fma is monotone in
-    // the bound), so the slab distances are the min/max of the AoS test bit for bit, without the per-child min/max
-    float smin[4], smax[4];  // SOA: the children's slab entry / exit (a child pair at a time, in the child loop)
-    LdsInt* ext = stack + STACK * BLOCK;
+    // Per axis, the ray's near bound word pair and far bound word pair, picked once for the four children by the sign
+    // of its direction: for 1/d > 0 the near slab is the min (fma is monotone in the bound), so the slab distances are
+    // the min/max of the per-child (HNode4) test bit for bit, without the per-child min/max
+    float smin[4], smax[4];  // the children's slab entry / exit (a child pair at a time, in the child loop)
+    LdsInt* ext = stack + kSecStack * kSecBlock;
     float best = INFINITY;
     int32_t next = 0;  // the nearest inner child
     bool inner[4];
-    // ring cursor: the next leaf goes to ring slot cur & (QCAP - 2); cur == head while the queue is
+    // ring cursor: the next leaf goes to ring slot cur & (kSecQcap - 2); cur == head while the queue is
     // empty (the next leaf is the register head q0). Q.n follows from cur after the four children.
     const int head = Q.q1 - 1;
     int cur = head + Q.n;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        float tmin, tmax;
-        if constexpr (SOA) {
-            // children i, i + 1 from one word pair per axis, just before child i: computing all four children's slabs
-            // up front kept 8 more values live across the step (12 spilled VGPRs at the 72-VGPR limit, twice the
-            // write traffic, 77.5 vs 76.0 ms at C4)
-            if (i == 0 || i == 2) {
-                const int pr = i >> 1;
-                const float inv[3] = {R.ix, R.iy, R.iz}, oi[3] = {R.oxi, R.oyi, R.ozi};
+        // children i, i + 1 from one word pair per axis, just before child i: computing all four children's slabs
+        // up front kept 8 more values live across the step (12 spilled VGPRs at the 72-VGPR limit, twice the
+        // write traffic, 77.5 vs 76.0 ms at C4)
+        if (i == 0 || i == 2) {
+            const int pr = i >> 1;
+            const float inv[3] = {R.ix, R.iy, R.iz}, oi[3] = {R.oxi, R.oyi, R.ozi};
 #pragma unroll
-                for (int ax = 0; ax < 3; ++ax) {
-                    const bool neg = inv[ax] < 0.0f;
-                    const uint32_t nwd = neg ? w[4 * ax + 2 + pr] : w[4 * ax + pr], fwd = neg ? w[4 * ax + pr] : w[4 * ax + 2 + pr];
+            for (int ax = 0; ax < 3; ++ax) {
+                const bool neg = inv[ax] < 0.0f;
+                const uint32_t nwd = neg ? w[4 * ax + 2 + pr] : w[4 * ax + pr], fwd = neg ? w[4 * ax + pr] : w[4 * ax + 2 + pr];
 #pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const float nb = (float)__builtin_bit_cast(_Float16, (uint16_t)(h ? (nwd >> 16) : (nwd & 0xffffu)));
-                        const float fb = (float)__builtin_bit_cast(_Float16, (uint16_t)(h ? (fwd >> 16) : (fwd & 0xffffu)));
-                        const float tn = fmaf(nb, inv[ax], -oi[ax]), tf = fmaf(fb, inv[ax], -oi[ax]);
-                        smin[i + h] = ax == 0 ? tn : fmaxf(smin[i + h], tn);
-                        smax[i + h] = ax == 0 ? tf : fminf(smax[i + h], tf);
-                    }
+                for (int h = 0; h < 2; ++h) {
+                    const float nb = (float)__builtin_bit_cast(_Float16, (uint16_t)(h ? (nwd >> 16) : (nwd & 0xffffu)));
+                    const float fb = (float)__builtin_bit_cast(_Float16, (uint16_t)(h ? (fwd >> 16) : (fwd & 0xffffu)));
+                    const float tn = fmaf(nb, inv[ax], -oi[ax]), tf = fmaf(fb, inv[ax], -oi[ax]);
+                    smin[i + h] = ax == 0 ? tn : fmaxf(smin[i + h], tn);
+                    smax[i + h] = ax == 0 ? tf : fminf(smax[i + h], tf);
                 }
             }
-            tmin = smin[i];
-            tmax = smax[i];
-        } else {
-            float f[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                const uint32_t word = w[(6 * i + k) >> 1];
-                f[k] = (float)__builtin_bit_cast(_Float16, (uint16_t)(((6 * i + k) & 1) ? (word >> 16) : (word & 0xffffu)));
-            }
-            const float tx1 = fmaf(f[0], R.ix, -R.oxi), tx2 = fmaf(f[3], R.ix, -R.oxi);
-            const float ty1 = fmaf(f[1], R.iy, -R.oyi), ty2 = fmaf(f[4], R.iy, -R.oyi);
-            const float tz1 = fmaf(f[2], R.iz, -R.ozi), tz2 = fmaf(f[5], R.iz, -R.ozi);
-            tmin = fmaxf(fmaxf(fminf(tx1, tx2), fminf(ty1, ty2)), fminf(tz1, tz2));
-            tmax = fminf(fminf(fmaxf(tx1, tx2), fmaxf(ty1, ty2)), fmaxf(tz1, tz2));
         }
+        const float tmin = smin[i], tmax = smax[i];
         // [max(tmin, 0), min(tmax, plim)] not empty; a NaN box (empty slot) fails the first compare; the
         // subtree the ray has just finished (child slot skip - 1, right after a climb) is skipped
         const bool hit = (tmin <= fminf(tmax, R.plim)) & (tmax >= 0.0f) & (skip != i + 1);
         const bool leaf = hit & (ref[i] < 0);
         inner[i] = hit & !leaf;  // an empty slot (ref 0) never hits
         // leaf -> the queue's end: branch-free, a non-leaf store lands past the last entry (never
-        // read). A NODE step starts with at most QCAP - 4 entries, so that slot is a free ring word.
+        // read). A NODE step starts with at most kSecQcap - 4 entries, so that slot is a free ring word.
         Q.q0 = (leaf & (cur == head)) ? ref[i] : Q.q0;
-        ext[(cur & (QCAP - 2)) * BLOCK] = ref[i];
+        ext[(cur & (kSecQcap - 2)) * kSecBlock] = ref[i];
         cur += (int)leaf;
         const bool nearer = inner[i] & (tmin < best);
         best = nearer ? tmin : best;
@@ -786,19 +706,19 @@ __device__ __forceinline__ void sec_node4v(const RenderArgs& A, SecRay& R, LdsIn
     Q.n = cur - head;
     // the other inner children -> stack, branch-free while every stepping lane has room for 4: the loop stores at
     // the running sp for every slot, so after three pushes the fourth slot's store, kept or not, lands at sp + 3,
-    // and row STACK is the leaf queue's ring slot 0 (with room for 3 only, a queued leaf there was overwritten)
-    if (__builtin_expect(__ballot(sp > STACK - 4) == 0ull, 1)) {
+    // and row kSecStack is the leaf queue's ring slot 0 (with room for 3 only, a queued leaf there was overwritten)
+    if (__builtin_expect(__ballot(sp > kSecStack - 4) == 0ull, 1)) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            stack[sp * BLOCK] = ref[i];
+            stack[sp * kSecBlock] = ref[i];
             sp += (int)(inner[i] & (ref[i] != next));
         }
     } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             if (inner[i] & (ref[i] != next)) {
-                if (sp < STACK) stack[sp * BLOCK] = ref[i];
-                else A.stack_ovf[ovf_slot<BLOCK, STACK>(A, sp)] = ref[i];
+                if (sp < kSecStack) stack[sp * kSecBlock] = ref[i];
+                else A.stack_ovf[ovf_slot(A, sp)] = ref[i];
                 ++sp;
             }
         }
@@ -807,32 +727,22 @@ __device__ __forceinline__ void sec_node4v(const RenderArgs& A, SecRay& R, LdsIn
         node = next;
     } else if (sp > 0) {
         --sp;
-        node = sp < STACK ? stack[sp * BLOCK] : A.stack_ovf[ovf_slot<BLOCK, STACK>(A, sp)];
+        node = sp < kSecStack ? stack[sp * kSecBlock] : A.stack_ovf[ovf_slot(A, sp)];
     } else {
         // the subtree is done: its parent next, without that child (every node is still visited at most once: the
         // walk from the record's start subtree up to the root covers the tree). The parent entry carries the
         // child's slot in bits 28-30 (slot + 1), which the next step skips.
-#if VR_SEC_UP_AHEAD
         // R.up is that entry, loaded when the ray entered the subtree (-1: the root's subtree is done); the
         // parent's own entry is issued now and read at the next climb, many node steps later
         node = R.up;
         if (R.up >= 0) R.up = A.hn4_parent[R.up & kNodeIndexMask];
-#else
-        if (R.up > 0) {
-            const int32_t up = A.hn4_parent[R.up];
-            R.up = up & kNodeIndexMask;
-            node = up;  // (-1: the root's subtree is done)
-        } else {
-            node = -1;
-        }
-#endif
     }
 }
 
-// One child-pair step of the postponed-leaf traversal: leaf children go to the queue (nearer
+// One step of the f32 child-pair traversal: leaf children go to the queue (nearer
 // first); node < 0 afterwards means the traversal is finished. Written branch-free (bitwise
 // predicates, selects) so a wave does not split inside the step.
-template <int BLOCK, bool S, int QCAP, int STACK, bool H>
+template <bool S>
 __device__ __forceinline__ void sec_node(const RenderArgs& A, SecRay& R, LdsInt* stack, int& sp, int& node, LeafQueue& Q,
                                          Ctr& c) {
     if constexpr (S) {
@@ -841,7 +751,7 @@ __device__ __forceinline__ void sec_node(const RenderArgs& A, SecRay& R, LdsInt*
     }
     float f[12];  // left min xyz, left max xyz, right min xyz, right max xyz
     int2 nc;
-    load_pair<H>(A, node, f, nc);  // H: scene-normalised coordinates (R.ix.. are normalised too)
+    load_pair<false>(A, node, f, nc);  // the f32 nodes
     const float tx1 = fmaf(f[0], R.ix, -R.oxi), tx2 = fmaf(f[3], R.ix, -R.oxi);
     const float ty1 = fmaf(f[1], R.iy, -R.oyi), ty2 = fmaf(f[4], R.iy, -R.oyi);
     const float tz1 = fmaf(f[2], R.iz, -R.ozi), tz2 = fmaf(f[5], R.iz, -R.ozi);
@@ -860,21 +770,21 @@ __device__ __forceinline__ void sec_node(const RenderArgs& A, SecRay& R, LdsInt*
     const int32_t near_ref = r_near ? nc.y : nc.x, far_ref = r_near ? nc.x : nc.y;
     // leaves -> queue, nearer first
     const int32_t first_leaf = (ll & lr) ? near_ref : (ll ? nc.x : nc.y);
-    Q.put<QCAP, BLOCK>((ll | lr) ? Q.n : -1, first_leaf, stack + STACK * BLOCK);
-    Q.put<QCAP, BLOCK>((ll & lr) ? Q.n + 1 : -1, far_ref, stack + STACK * BLOCK);
+    Q.put((ll | lr) ? Q.n : -1, first_leaf, stack + kSecStack * kSecBlock);
+    Q.put((ll & lr) ? Q.n + 1 : -1, far_ref, stack + kSecStack * kSecBlock);
     Q.n += (int)ll + (int)lr;
     // inner children -> continue / stack
     const bool il = hl & !ll, ir = hr & !lr;
     if (il & ir) {
-        if (sp < STACK) stack[sp * BLOCK] = far_ref;
-        else A.stack_ovf[ovf_slot<BLOCK, STACK>(A, sp)] = far_ref;
+        if (sp < kSecStack) stack[sp * kSecBlock] = far_ref;
+        else A.stack_ovf[ovf_slot(A, sp)] = far_ref;
         ++sp;
     }
     if (il | ir) {
         node = (il & ir) ? near_ref : (il ? nc.x : nc.y);
     } else if (sp > 0) {
         --sp;
-        node = sp < STACK ? stack[sp * BLOCK] : A.stack_ovf[ovf_slot<BLOCK, STACK>(A, sp)];
+        node = sp < kSecStack ? stack[sp * kSecBlock] : A.stack_ovf[ovf_slot(A, sp)];
     } else {
         node = -1;
     }
@@ -912,20 +822,13 @@ constexpr int kRefillMin = VR_WW_REFILL, kNodeSteps = VR_WW_NODE_STEPS, kPrimSte
 constexpr int kPrimBias = VR_WW_PRIM_BIAS;
 constexpr int kPrimUnroll = VR_WW_PRIM_UNROLL, kNodeUnroll = VR_WW_NODE_UNROLL;
 
-// 6 waves/SIMD = 80 VGPRs: the ray state is kept small enough for that without scratch spills (a
-// spilling 6-wave build measured 9 % slower than 5 waves; this one is 5 % faster than 5 waves).
-// S = true is the instrumented build (vr_count_work): the same schedule, counting its own work.
-// WH: the whitened records (A.wrec); false (PureRayMarching, or a scene with a non-positive-definite M):
-// the records' M forms with the membership lookup of the record's active list.
-#ifdef VR_DIAG_DRAIN  // diagnostic builds only: the persistent kernel's tail (100 MHz clock ticks, printed by the last wave)
-// [0] ray latencies, [1] latencies of the rays handed out once the claim counter was exhausted (log2 us buckets);
-// wave exits after the exhaustion in 50-us buckets
-__device__ unsigned long long g_dr_t0, g_dr_done, g_dr_end;
-__device__ uint32_t g_dr_hist[2][20], g_dr_max[2], g_dr_exit[64], g_dr_waves;
-#endif
-template <int BLOCK, int STACK, bool S, bool PURE, int WAVES, int QCAP, bool H, bool W, bool WH = !PURE, bool SOA = false>
-__global__ __launch_bounds__(BLOCK, WAVES) void secondary_ww_kernel(RenderArgs A) {
-    __shared__ int s_stack[(STACK + kQueueLds<QCAP>) * BLOCK];
+// The persistent kernel (the header at the top of this unit). Launch bounds, sec_waves(F) waves per SIMD: the whitened
+// form at 7 = 72 VGPRs (the product kernel on the 4-wide tree sits at that limit with 2 spilled VGPRs),
+// the M form at 6 = 80 VGPRs, PureRayMarching at 5 = 96 VGPRs (it needs 81 to 93).
+template <bool S, SecForm F, SecTree T>
+__global__ __launch_bounds__(kSecBlock, sec_waves(F)) void secondary_ww_kernel(RenderArgs A) {
+    constexpr bool PURE = F == SecForm::Pure, WH = F == SecForm::Whitened, W = T == SecTree::Wide4;
+    __shared__ int s_stack[(kSecStack + kQueueLds) * kSecBlock];
     LdsInt* stack = (LdsInt*)(s_stack + threadIdx.x);  // LDS-typed: stack/queue accesses are ds_* ops, never flat
     const uint32_t lane = threadIdx.x & 63u;
     Ctr c{};
@@ -948,8 +851,8 @@ __global__ __launch_bounds__(BLOCK, WAVES) void secondary_ww_kernel(RenderArgs A
     // the counter runs out is the in-flight rays' latency, not the unstarted rays left in a wave's pool. Nor is
     // that latency a few long walks: handing rays past 150/300/600/1200 node steps to the wave-per-ray slow path
     // re-routed 17 k/15/0/0 rays per C4 frame and cost 1.8 ms in spills. A ray waits on its wave's NODE/PRIM
-    // schedule: ~100-250 us typical, up to ~2 ms, over ~30 node steps; VR_DIAG_DRAIN.)
-    const uint32_t waves = gridDim.x * (BLOCK / 64u), cpw = nchunks / max(waves, 1u);
+    // schedule: ~100-250 us typical, up to ~2 ms, over ~30 node steps, measured with a diagnostic build since retired: DESIGN.md.)
+    const uint32_t waves = gridDim.x * (kSecBlock / 64u), cpw = nchunks / max(waves, 1u);
     constexpr uint32_t kSplitCpw = VR_WW_SPLIT_CPW;
     const uint32_t split = cpw >= kSplitCpw ? 0u : cpw >= kSplitCpw / 2u ? 1u : cpw >= kSplitCpw / 4u ? 2u : 3u;
     const uint32_t nunits = nchunks << split;
@@ -965,40 +868,13 @@ __global__ __launch_bounds__(BLOCK, WAVES) void secondary_ww_kernel(RenderArgs A
 #else
     auto diag_lap = [](int) {};
 #endif
-#ifdef VR_DIAG_REFILL  // diagnostic builds only (with VR_DIAG_CYCLES): the refill split into its parts (lane 0's
-    // cycles, written over the work counters kCtrNodes (batch completion), kCtrPrims (chunk claim), kCtrOD
-    // (sec_init, the start node and list_begin, with their loads waited for), kCtrMu (hand-out bookkeeping))
-    uint32_t rf_cyc[4] = {0u, 0u, 0u, 0u};
-    uint64_t rf_t = 0;
-    auto rf_lap = [&](int k, bool wait) {
-        if (wait) __asm__ volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        const uint64_t now = __builtin_amdgcn_s_memtime();
-        rf_cyc[k] += lane == 0u ? (uint32_t)(now - rf_t) : 0u;
-        rf_t = now;
-    };
-#else
-    auto rf_lap = [](int, bool) {};
-#endif
-#ifdef VR_DIAG_DRAIN
-    uint64_t dr_ray0 = 0;
-    bool dr_late = false, dr_seen = false;
-    __shared__ uint32_t s_dr_hist[2][20], s_dr_max[2];  // (workgroup-local: global atomics per ray slow the frame ~90x)
-    if (threadIdx.x < 40u) (&s_dr_hist[0][0])[threadIdx.x] = 0u;
-    if (threadIdx.x < 2u) s_dr_max[threadIdx.x] = 0u;
-    __syncthreads();
-    if (lane == 0u) atomicCAS(&g_dr_t0, 0ull, (unsigned long long)wall_clock64());
-#endif
     for (;;) {
         const uint64_t idle = __ballot(!live);
         if (__popcll(idle) >= kRefillMin) {  // refill once enough lanes are idle (amortises sec_init)
-#ifdef VR_DIAG_REFILL
-            rf_t = __builtin_amdgcn_s_memtime();
-#endif
             if (fin) {  // the completions since the last refill, in one pass
-                sec_finish<S, true, PURE, WH>(A, R, c);
+                sec_finish<S, F>(A, R, c);
                 fin = false;
             }
-            rf_lap(0, true);
             if (pool == pool_end && !counter_done) {  // next unit of a record chunk
                 uint32_t cnext = 0;
                 if (lane == 0) cnext = (uint32_t)atomicAdd(A.ray_next, 1ull);
@@ -1014,36 +890,25 @@ __global__ __launch_bounds__(BLOCK, WAVES) void secondary_ww_kernel(RenderArgs A
                     pool_end = ((part + 1u) * cper) >> split;
                 }
                 counter_done = cnext + 1u >= nunits;
-#ifdef VR_DIAG_DRAIN
-                if (cnext + 1u >= nunits && !dr_seen && lane == 0u) atomicCAS(&g_dr_done, 0ull, (unsigned long long)wall_clock64());
-                dr_seen = dr_seen || cnext + 1u >= nunits;
-#endif
             }
-            rf_lap(1, true);
             const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
             if (!live && pool + rank < pool_end) {
                 t = pool + rank;
                 if constexpr (S) c.v[kCtrSecRays]++;
                 int32_t start;
-                live = sec_init(A, nrec, chunk, t, R, start, H, W);  // false: padding id, or complete already (Tr written)
-#ifdef VR_DIAG_DRAIN
-                dr_ray0 = wall_clock64();
-                dr_late = counter_done;
-#endif
+                live = sec_init<T>(A, nrec, chunk, t, R, start);  // false: padding id, or complete already (Tr written)
                 sp = 0;
                 node = -1;
                 Q.n = 0;
                 Q.j = Q.end = 0;
                 if (live) list_begin(R, Q, node, start);
             }
-            rf_lap(2, true);
             const uint32_t handed = (uint32_t)__popcll(idle);
             pool = pool_end - pool > handed ? pool + handed : pool_end;
-            rf_lap(3, true);
         }
         if (!__any(live)) {
             if (fin) {  // (only if the refill threshold exceeded the wave: every lane idle refills above)
-                sec_finish<S, true, PURE, WH>(A, R, c);
+                sec_finish<S, F>(A, R, c);
                 fin = false;
             }
             if (counter_done && pool == pool_end) break;
@@ -1055,12 +920,12 @@ __global__ __launch_bounds__(BLOCK, WAVES) void secondary_ww_kernel(RenderArgs A
         diag_lap(kCtrPixels);
         const bool has_prim = live && Q.has_prim();
         constexpr int kRoom = W ? 4 : 2;  // leaves one NODE step can queue
-        const bool can_node = live && node >= 0 && (QCAP == 2 ? Q.n == 0 : Q.n <= QCAP - kRoom);
+        const bool can_node = live && node >= 0 && Q.n <= kSecQcap - kRoom;
         const int np = __popcll(__ballot(has_prim)), nn = __popcll(__ballot(can_node));
         // whichever kind more lanes can use; never a kind no lane can use (that would not progress)
         const bool prim_iter = nn == 0 || (np > 0 && np * 100 >= nn * kPrimBias);
         if (prim_iter) {  // PRIM iteration: up to kPrimSteps primitive tests per lane
-            LdsInt* ext = stack + STACK * BLOCK;
+            LdsInt* ext = stack + kSecStack * kSecBlock;
             // next primitive of the lane: a list member (ls = its slot) or a queued leaf's (ls = -1)
             auto fetch = [&](uint32_t& j, int& ls) {
                 if (node <= kNodeList) {
@@ -1069,7 +934,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void secondary_ww_kernel(RenderArgs A
                     list_advance(Q, node);
                 } else {
                     ls = -1;
-                    j = Q.next<QCAP, BLOCK>(ext);
+                    j = Q.next(ext);
                 }
             };
             // one primitive test; ls >= 0: list member ls (pre-activated: optical depth from 0).
@@ -1128,7 +993,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void secondary_ww_kernel(RenderArgs A
                     c.v[kCtrPixels] += cand ? 1u : 0u;  // a list member's depth again (the credit scheme)
 #endif
                 }
-                // sec_add's FAST rule: one optical-depth evaluation for light and environment lanes
+                // sec_add's rule: one optical-depth evaluation for light and environment lanes
                 const bool add = !R.light || t1 < R.lim;
                 R.needs_stop = R.needs_stop | (!add & (lo < R.lim));
                 R.lim = (!R.light && t1 > R.lim) ? t1 : R.lim;
@@ -1167,7 +1032,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void secondary_ww_kernel(RenderArgs A
                         lo = 0.0f;
                         R.hitmask |= slot_bit(slot);
                     }
-                    sec_add<S, true, PURE>(A, R, g, q, lo, b, c);
+                    sec_add<S, PURE>(A, R, g, q, lo, b, c);
                 }
             };
             bool go = has_prim;
@@ -1194,70 +1059,19 @@ __global__ __launch_bounds__(BLOCK, WAVES) void secondary_ww_kernel(RenderArgs A
                 if constexpr (S) c.v[kCtrSteps] += (__ballot(go) != 0ull && lane == 0u) ? 1u : 0u;
 #endif
                 if (go) {
-                    if constexpr (W) sec_node4v<BLOCK, S, QCAP, STACK, SOA>(A, R, stack, sp, node, Q, c);
-                    else sec_node<BLOCK, S, QCAP, STACK, H>(A, R, stack, sp, node, Q, c);
+                    if constexpr (W) sec_node4v<S>(A, R, stack, sp, node, Q, c);
+                    else sec_node<S>(A, R, stack, sp, node, Q, c);
                 }
-                go = go && node >= 0 && Q.n <= QCAP - kRoom;
+                go = go && node >= 0 && Q.n <= kSecQcap - kRoom;
             }
             diag_lap(kCtrSteps);
         }
         if (live && (cut_reached<PURE>(R) || (node == -1 && !Q.has_prim()))) {
             fin = true;  // written at the next refill (the lane idles until then anyway)
             live = false;
-#ifdef VR_DIAG_DRAIN
-            const uint32_t us = (uint32_t)((wall_clock64() - dr_ray0) / 100u);
-            atomicAdd(&s_dr_hist[0][min(31 - __clz(us | 1), 19)], 1u);
-            atomicMax(&s_dr_max[0], us);
-            if (dr_late) {
-                atomicAdd(&s_dr_hist[1][min(31 - __clz(us | 1), 19)], 1u);
-                atomicMax(&s_dr_max[1], us);
-            }
-#endif
         }
     }
-#ifdef VR_DIAG_DRAIN
-    {
-        const unsigned long long now = wall_clock64(), done = atomicAdd(&g_dr_done, 0ull);
-        if (lane == 0u && done != 0ull && now > done) atomicAdd(&g_dr_exit[min((uint32_t)((now - done) / 5000u), 63u)], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < 40u) {
-        const uint32_t v = (&s_dr_hist[0][0])[threadIdx.x];
-        if (v) atomicAdd(&g_dr_hist[0][0] + threadIdx.x, v);
-    }
-    if (threadIdx.x < 2u) atomicMax(&g_dr_max[threadIdx.x], s_dr_max[threadIdx.x]);
-    if (lane == 0u) {
-        const unsigned long long now = wall_clock64();
-        atomicMax(&g_dr_end, now);
-        __threadfence();
-        if (atomicAdd(&g_dr_waves, 1u) == waves - 1u) {
-            const unsigned long long t0 = atomicExch(&g_dr_t0, 0ull), end = atomicExch(&g_dr_end, 0ull);
-            const unsigned long long dn = atomicExch(&g_dr_done, 0ull);
-            printf("drain: waves %u units %u kernel %.1f us, claims exhausted at %.1f us, drain %.1f us; max ray %u us, max late ray %u us\n",
-                   waves, nunits, (end - t0) / 100.0, (dn - t0) / 100.0, (end - dn) / 100.0, atomicExch(&g_dr_max[0], 0u),
-                   atomicExch(&g_dr_max[1], 0u));
-            for (int k = 0; k < 2; ++k)
-                for (int b = 0; b < 20; ++b) {
-                    const uint32_t v = atomicExch(&g_dr_hist[k][b], 0u);
-                    if (v) printf("  %s rays us<%u: %u\n", k ? "late" : "all", 2u << b, v);
-                }
-            for (int b = 0; b < 64; ++b) {
-                const uint32_t v = atomicExch(&g_dr_exit[b], 0u);
-                if (v) printf("  wave exits %u-%u us after exhaustion: %u\n", 50u * b, 50u * b + 50u, v);
-            }
-            atomicExch(&g_dr_waves, 0u);
-        }
-    }
-#endif
-#ifdef VR_DIAG_REFILL
-    c.v[kCtrNodes] = rf_cyc[0];
-    c.v[kCtrPrims] = rf_cyc[1];
-    c.v[kCtrOD] = rf_cyc[2];
-    c.v[kCtrMu] = rf_cyc[3];
-#endif
-#ifndef VR_DIAG_LEVELS
     if constexpr (S) flush_counters(A.work + kNumCtr, c);
-#endif
 }
 
 // Environment rays with one chord in the reference f32 quadratic's error band (to_fix): the band Gaussian's
@@ -1344,50 +1158,38 @@ __global__ __launch_bounds__(256) void record_start_kernel(RenderArgs A) {
 // ---------------------------------------------------------------------------------------------
 // Host launchers
 // ---------------------------------------------------------------------------------------------
-constexpr int kBlockSecondary = 256;
-
 // One launch of the persistent kernel: one resident grid (every CU filled to the kernel's occupancy).
 // LDS words per lane: 14 traversal-stack entries (deeper ones overflow to global memory) + the
 // 8-entry LDS ring of the 9-entry leaf queue = 22 (7 blocks of 256 lanes per CU).
-template <bool S, bool PURE, bool H, bool W, bool WH = !PURE, bool SOA = false>
+template <bool S, dev::SecForm F, dev::SecTree T>
 static hipError_t ww_launch(const RenderArgs& A, hipStream_t stream) {
-    constexpr int kStack = VR_WW_STACK, kQueue = VR_WW_QCAP;
-    constexpr int kWaves = PURE ? 5 : WH ? VR_WW_WAVES : 6;  // PureRayMarching's marched depth does not fit 80 VGPRs without spills
-    const void* fn = (const void*)dev::secondary_ww_kernel<kBlockSecondary, kStack, S, PURE, kWaves, kQueue, H, W, WH, SOA>;
+    constexpr int kBlock = dev::kSecBlock;
+    const void* fn = (const void*)dev::secondary_ww_kernel<S, F, T>;
     int dv = 0, cus = 0, per_cu = 0;
     if (hipGetDevice(&dv) != hipSuccess) return hipErrorUnknown;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dv) != hipSuccess) return hipErrorUnknown;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlockSecondary, 0) != hipSuccess || per_cu < 1)
-        per_cu = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kBlock, 0) != hipSuccess || per_cu < 1) per_cu = 1;
     uint64_t grid = (uint64_t)cus * (uint64_t)per_cu;
-    if (grid * kBlockSecondary > A.stack_ovf_lanes) grid = A.stack_ovf_lanes / kBlockSecondary;  // overflow slots
+    if (grid * kBlock > A.stack_ovf_lanes) grid = A.stack_ovf_lanes / kBlock;  // overflow slots
     if (grid == 0) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(A.ray_next, 0, sizeof(unsigned long long), stream);
     if (e != hipSuccess) return e;
-    RenderArgs B = A;  // the tight tree only under the whitened test (the M forms: the shared tree's padded boxes)
-    if (PURE || !WH) B.hnodes4s = A.hnodes4;
-    if (SOA && B.hnodes4s == A.hnodes4) B.hnodes4t = A.hnodes4w;  // the per-axis copy of the tree walked
-    hipLaunchKernelGGL((dev::secondary_ww_kernel<kBlockSecondary, kStack, S, PURE, kWaves, kQueue, H, W, WH, SOA>), dim3((unsigned)grid),
-                       dim3(kBlockSecondary), 0, stream, B);
+    // The 4-wide walk reads the per-axis copy of its tree (A.hnodes4t): the tight tree's under the whitened test; the
+    // M forms walk the shared tree's padded boxes, and so does a whitened scene without a tight tree
+    RenderArgs B = A;
+    if (F != dev::SecForm::Whitened) B.hnodes4s = A.hnodes4;
+    if (T == dev::SecTree::Wide4 && B.hnodes4s == A.hnodes4) B.hnodes4t = A.hnodes4w;
+    hipLaunchKernelGGL((dev::secondary_ww_kernel<S, F, T>), dim3((unsigned)grid), dim3(kBlock), 0, stream, B);
     return hipGetLastError();
 }
 
-template <bool S, bool PURE>
+template <bool S, dev::SecForm F>
 static hipError_t secondary_launch(const RenderArgs& A, hipStream_t stream) {
-    hipError_t e;
-    // (4-wide trees: the node step reads the per-axis copy of the tree the variant walks, VR_SEC_SOA)
-    if (!PURE && A.wrec == nullptr) {  // a record without a Cholesky factor: the M forms (rare scenes)
-        if (A.hnodes != nullptr && A.hnodes4 != nullptr) e = ww_launch<S, PURE, true, true, false, VR_SEC_SOA != 0>(A, stream);
-        else if (A.hnodes != nullptr) e = ww_launch<S, PURE, true, false, false>(A, stream);
-        else e = ww_launch<S, PURE, false, false, false>(A, stream);
-    } else if (A.hnodes != nullptr && A.hnodes4 != nullptr)  // 4-wide half-precision tree
-        e = ww_launch<S, PURE, true, true, !PURE, VR_SEC_SOA != 0>(A, stream);
-    else if (A.hnodes != nullptr)
-        e = ww_launch<S, PURE, true, false>(A, stream);
-    else  // f32 child-pair tree (scenes whose leaf boxes are too small for f16 boxes)
-        e = ww_launch<S, PURE, false, false>(A, stream);
+    // the 4-wide f16 tree when the scene has one (its leaf boxes are large enough for f16 boxes), else the f32 pairs
+    hipError_t e = A.hnodes4 != nullptr ? ww_launch<S, F, dev::SecTree::Wide4>(A, stream)
+                                        : ww_launch<S, F, dev::SecTree::PairF32>(A, stream);
     if (e != hipSuccess) return e;
-    if (!PURE) {  // PureRayMarching has no first-event-past-the-light quirk, hence no slow path
+    if (F != dev::SecForm::Pure) {  // PureRayMarching has no first-event-past-the-light quirk, hence no slow path
         hipLaunchKernelGGL(dev::secondary_fix_kernel, dim3(1024), dim3(64), 0, stream, A);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         e = secondary_slow_launch(A, stream, S);
@@ -1395,12 +1197,17 @@ static hipError_t secondary_launch(const RenderArgs& A, hipStream_t stream) {
     return e;
 }
 
+// The form of a frame's secondary rays: PureRayMarching; else the whitened records, or the M forms for a scene with a
+// record without a Cholesky factor (A.wrec == nullptr; rare scenes).
+template <bool S>
+static hipError_t secondary_form_launch(const RenderArgs& A, hipStream_t stream) {
+    if (A.pure) return secondary_launch<S, dev::SecForm::Pure>(A, stream);
+    if (A.wrec == nullptr) return secondary_launch<S, dev::SecForm::MForm>(A, stream);
+    return secondary_launch<S, dev::SecForm::Whitened>(A, stream);
+}
+
 hipError_t gauss_secondary(const RenderArgs& A, hipStream_t stream, bool stats) {
     if (A.num_lights + A.env_samples == 0) return hipSuccess;
-#ifdef VR_DIAG_LEVELS
-    if (A.hn4_parent != nullptr && A.num_nodes4 > 0)
-        hipLaunchKernelGGL(dev::depth_kernel, dim3((A.num_nodes4 + 255) / 256), dim3(256), 0, stream, A.hn4_parent, A.num_nodes4);
-#endif
     if (A.rec_start != nullptr) {  // every record's start subtree (the 4-wide walk with parents only)
         hipLaunchKernelGGL(dev::record_start_kernel, dim3(record_grid(A, 256, 16384)), dim3(256), 0, stream, A);
         hipError_t e = hipGetLastError();
@@ -1408,15 +1215,14 @@ hipError_t gauss_secondary(const RenderArgs& A, hipStream_t stream, bool stats) 
     }
     if (A.env_order != nullptr) {
         // (stats: the instrumented build counts the list filter's work with the persistent kernel's)
-        if (stats) hipLaunchKernelGGL((dev::env_order_kernel<256, true>), dim3(record_grid(A, A.chunk_rec * 4, 4096)), dim3(256), 0, stream, A);
-        else hipLaunchKernelGGL((dev::env_order_kernel<256, false>), dim3(record_grid(A, A.chunk_rec * 4, 4096)), dim3(256), 0, stream, A);
+        if (stats) hipLaunchKernelGGL((dev::env_order_kernel<true>), dim3(record_grid(A, A.chunk_rec * 4, 4096)), dim3(256), 0, stream, A);
+        else hipLaunchKernelGGL((dev::env_order_kernel<false>), dim3(record_grid(A, A.chunk_rec * 4, 4096)), dim3(256), 0, stream, A);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     // stats: the instrumented build of the same persistent kernel (vr_count_work), which counts
     // the work this schedule really does (node steps, list and leaf primitive tests, optical depths)
-    if (A.pure) return stats ? secondary_launch<true, true>(A, stream) : secondary_launch<false, true>(A, stream);
-    return stats ? secondary_launch<true, false>(A, stream) : secondary_launch<false, false>(A, stream);
+    return stats ? secondary_form_launch<true>(A, stream) : secondary_form_launch<false>(A, stream);
 }
 
 }  // namespace vr

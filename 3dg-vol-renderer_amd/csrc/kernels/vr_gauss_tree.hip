@@ -118,10 +118,10 @@ __global__ __launch_bounds__(256) void refit_kernel(const HNode4* __restrict__ s
     }
 }
 
-// The secondary rays' per-axis node copy (VR_SEC_SOA): node i's words 4a..4a+3 hold axis a's box bounds as f16
+// The secondary rays' per-axis node copy: node i's words 4a..4a+3 hold axis a's box bounds as f16
 // pairs {min of children 0, 1}, {min of 2, 3}, {max of 0, 1}, {max of 2, 3}; words 12-15 the child refs. A ray
 // picks its near and far bound of an axis once per node (the sign of its direction), for all four children at
-// once, instead of a min and a max per child and axis (sec_node4v<SOA>).
+// once, instead of a min and a max per child and axis (sec_node4v).
 __global__ __launch_bounds__(256) void soa_nodes_kernel(const HNode4* __restrict__ src, HNode4* __restrict__ dst, uint32_t n) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;

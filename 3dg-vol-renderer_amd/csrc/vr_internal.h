@@ -77,10 +77,6 @@ struct HNode4 {
 };
 static_assert(sizeof(HNode4) == 64, "4-wide half node must be 64 B");
 
-#ifndef VR_SEC_SOA
-#define VR_SEC_SOA 1  // the secondary rays' node step reads a per-axis copy of their tree (sign-selected slabs; A/B)
-#endif
-
 // Where a record's secondary rays start (record_start_kernel): one 8-B gather at the ray's start instead of two
 // dependent loads (the start node, then its parent entry).
 struct alignas(8) RecStart {
@@ -178,7 +174,8 @@ struct RenderArgs {
     const HNode* hnodes;      // nullptr: the scene is not suited to half-precision boxes (see vr_upload.cpp)
     const HNode4* hnodes4;    // 4-wide collapse of the same tree (secondary rays); nullptr with hnodes
     const HNode4* hnodes4s;   // the secondary rays' copy with tight boxes (gauss_refit_secondary), else hnodes4
-    const HNode4* hnodes4t;   // hnodes4s's nodes with the boxes laid out per axis (soa_nodes_kernel), or nullptr
+    const HNode4* hnodes4t;   // the tight copy's nodes with the boxes laid out per axis (soa_nodes_kernel): the secondary
+                              // rays' node step reads it; nullptr without a tight copy (the walk then reads hnodes4w)
     const HNode4* hnodes4w;   // hnodes4's nodes laid out per axis (soa_nodes_kernel; read by wide_children), with hnodes4
     const int32_t* prim_node4;  // the 4-wide node whose child is each record's leaf (record starts), or nullptr
     const int32_t* hn4_parent;  // parent of every HNode4 | (its slot + 1) << 28 (root: -1); nullptr: walks start at the root
