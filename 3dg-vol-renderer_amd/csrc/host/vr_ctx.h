@@ -129,6 +129,7 @@ struct vr_ctx {
     // host forms (synchronous, one at a time): the batch on the device by role, each sized in 4-byte words: the inputs
     // (rays / points), the weights / targets / samples / event offsets, the first result and the second
     vr::DevBuf<float> q_in, q_w, q_out, q_out2;
+    vr::DevBuf<float> q_feat, q_w2;             // the feature queries' further inputs: the rows, the mass weights
     vr::DevBuf<uint32_t> q_cnt;                 // events: counts,
     vr::DevBuf<unsigned long long> q_keys, q_keys2;  // sort keys (in / out),
     vr::DevBuf<std::byte> q_tmp;                // scan + sort scratch
@@ -139,6 +140,9 @@ struct vr_ctx {
                                       // gradient queries may be queued on different streams)
     vr::DevBuf<double> q_prof_grad;   // profile gradient query (kernels/vr_query_profile.hip): 10 doubles of staging per
                                       // Gaussian, its own for q_sgrad's reason
+    vr::DevBuf<double> q_feat_grad;   // feature gradient query (kernels/vr_query_features.hip): 10 doubles of staging per
+    vr::DevBuf<double> q_feat_fgrad;  // Gaussian and C per Gaussian for the rows' gradient (tree order), zeroed per call,
+                                      // grown on demand; its own for q_sgrad's reason
     // free-flight query (kernels/vr_query_flight.hip): its own scratch rows (the layouts of ff_scratch and of
     // ff_fb's rows), so a frame queued on another stream never shares them; counters + queue of rays over the rows
     vr::DevBuf<std::byte> q_ff_rows, q_ff_big;

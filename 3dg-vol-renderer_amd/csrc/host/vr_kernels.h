@@ -66,6 +66,17 @@ hipError_t query_transmittance_profile_grad(const RenderArgs& A, const vr_ray* r
                                             const float* weight, uint32_t n, uint32_t K, bool moving, double* acc, float* grad,
                                             uint32_t* next, int refill, int cus, hipStream_t s);
 
+// kernels/vr_query_features.hip
+// (feat: C floats per scene Gaussian; out: n * C floats; mass, n_active: n each or nullptr. n > 0, 1 <= C, n * C < 2^31)
+hipError_t query_features(const RenderArgs& A, const float* xyz, uint32_t n, const float* feat, uint32_t C, float* out, float* mass,
+                          uint32_t* n_active, hipStream_t s);
+// (weights: n * C floats or nullptr; weight_mass: n or nullptr; stage / fstage: 10 / C doubles per Gaussian of staging,
+// zeroed by the call, each read only with its output; grad: 10 floats per Gaussian; grad_features: C per Gaussian; grad_xyz:
+// 3 per point; any of the three may be nullptr)
+hipError_t query_features_grad(const RenderArgs& A, const float* xyz, uint32_t n, const float* feat, uint32_t C,
+                               const float* weights, const float* weight_mass, double* stage, double* fstage, float* grad,
+                               float* grad_features, float* grad_xyz, hipStream_t s);
+
 // kernels/vr_query_flight.hip (the sweep, the solvers and the albedo are the path kernels': kernels/vr_ff_bounce.h)
 // (ctl: query_flight_ctl_words(n) words; A.ff_*: the scratch rows, sized as the free-flight frames size theirs)
 size_t query_flight_ctl_words(uint32_t n);

@@ -1,6 +1,7 @@
-// Mixture queries (vr_query_*, kernels/vr_query.hip, kernels/vr_query_profile.hip, kernels/vr_query_flight.hip): batched
-// transmittance and its gradients with respect to the Gaussians and to the rays, transmittance profiles and their
-// gradient, ray events, sigma and its gradient, and free-flight distances.
+// Mixture queries (vr_query_*, kernels/vr_query.hip, kernels/vr_query_profile.hip, kernels/vr_query_features.hip,
+// kernels/vr_query_flight.hip): batched transmittance and its gradients with respect to the Gaussians and to the rays,
+// transmittance profiles and their gradient, ray events, sigma and its gradient, per-Gaussian features at points and
+// their gradient, and free-flight distances.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -56,6 +57,14 @@ vr_status profile_check(const char* what, size_t t_stride, size_t n, uint32_t K)
     if (t_stride != 0 && t_stride != K) return fail(VR_ERR_INVALID, std::string(what) + ": t_stride must be 0 (one shared row) or K");
     if (n >= (1ull << 31) || n * (size_t)K >= (1ull << 31))
         return fail(VR_ERR_INVALID, std::string(what) + ": more than 2^31 - 1 samples in one call");
+    return VR_OK;
+}
+// The two feature entry points' own, before every launch. N: the scene's Gaussians.
+vr_status features_check(const char* what, size_t n, size_t N, uint32_t C) {
+    if (C == 0 || C > VR_FEATURES_MAX_CHANNELS)
+        return fail(VR_ERR_INVALID, std::string(what) + ": C must lie in [1, " + std::to_string(VR_FEATURES_MAX_CHANNELS) + "]");
+    if (n * (size_t)C >= (1ull << 31) || N * (size_t)C >= (1ull << 31))
+        return fail(VR_ERR_INVALID, std::string(what) + ": more than 2^31 - 1 feature entries in one call");
     return VR_OK;
 }
 // The gradient over no entries, or of a scene without Gaussians, is `words` zeros: true, and no launch follows.
@@ -308,6 +317,99 @@ vr_status vr_query_sigma_grad(vr_ctx* c, const float* xyz, const float* weight_a
                      "query_sigma_grad_kernel", [&] {
                          return vr_query_sigma_grad_device(c, c->q_in.get(), dev<float>(c->q_w, weight_as), n, dev<float>(c->q_out, grad),
                                                            dev<float>(c->q_out2, grad_xyz), c->stream);
+                     });
+}
+
+// ---- features: sum_g m_g(x) f_gc over the active set, for the caller's rows f ----
+vr_status vr_query_features_device(vr_ctx* c, const float* d_xyz, size_t n, const float* d_features, uint32_t C, float* d_out,
+                                   float* d_mass, uint32_t* d_n_active, void* stream) {
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_features", n, A));
+    VR_TRY(features_check("vr_query_features", n, (size_t)std::max(A.num_prims, 0), C));
+    if (n == 0) return VR_OK;
+    if (!d_xyz || !d_features || !d_out) return fail(VR_ERR_INVALID, "vr_query_features: NULL argument");
+    HIP_TRY(query_features(A, d_xyz, (uint32_t)n, d_features, C, d_out, d_mass, d_n_active, (hipStream_t)stream),
+            "query_features_kernel");
+    return VR_OK;
+}
+
+vr_status vr_query_features(vr_ctx* c, const float* xyz, size_t n, const float* features, uint32_t C, float* out, float* mass,
+                            uint32_t* n_active) {
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_features", n, A));
+    const size_t N = (size_t)std::max(A.num_prims, 0);
+    VR_TRY(features_check("vr_query_features", n, N, C));
+    if (n == 0) return VR_OK;
+    if (!xyz || !features || !out) return fail(VR_ERR_INVALID, "vr_query_features: NULL argument");
+    if (N == 0) {  // an empty scene: there are no rows to send, and every result is +0
+        std::memset(out, 0, n * (size_t)C * sizeof(float));
+        if (mass) std::memset(mass, 0, n * sizeof(float));
+        if (n_active) std::memset(n_active, 0, n * sizeof(uint32_t));
+        return VR_OK;
+    }
+    // (the mass and the counts share the second result's workspace)
+    return host_form(c, {{c->q_in, xyz, n * 3, "query points"}, {c->q_feat, features, N * C, "query features"}},
+                     {{c->q_out, out, n * (size_t)C, "query results"}, {c->q_out2, mass, n, "query results"},
+                      {c->q_out2, n_active, n, "query results", n}},
+                     "query_features_kernel", [&] {
+                         return vr_query_features_device(c, c->q_in.get(), n, c->q_feat.get(), C, c->q_out.get(),
+                                                         dev<float>(c->q_out2, mass), dev<uint32_t>(c->q_out2, n_active, n), c->stream);
+                     });
+}
+
+vr_status vr_query_features_grad_device(vr_ctx* c, const float* d_xyz, size_t n, const float* d_features, uint32_t C,
+                                        const float* d_weights, const float* d_weight_mass, float* d_grad, float* d_grad_features,
+                                        float* d_grad_xyz, void* stream) {
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_features_grad", n, A));
+    const size_t N = (size_t)std::max(A.num_prims, 0);
+    VR_TRY(features_check("vr_query_features_grad", n, N, C));
+    if (n == 0) {
+        if (d_grad && N) HIP_TRY(hipMemsetAsync(d_grad, 0, N * 10 * sizeof(float), (hipStream_t)stream), "hipMemset(feature gradient)");
+        if (d_grad_features && N)
+            HIP_TRY(hipMemsetAsync(d_grad_features, 0, N * C * sizeof(float), (hipStream_t)stream), "hipMemset(feature gradient)");
+        return VR_OK;
+    }
+    if (!d_xyz || !d_features) return fail(VR_ERR_INVALID, "vr_query_features_grad: NULL argument");
+    if (!d_grad && !d_grad_features && !d_grad_xyz) return fail(VR_ERR_INVALID, "vr_query_features_grad: all three outputs are NULL");
+    // the staging rows are the query's own: a frame or another gradient query queued on another stream never sees them
+    if (d_grad) VR_TRY(c->q_feat_grad.grow(std::max<size_t>(N, 1) * 10, "hipMalloc(gradient staging)"));
+    if (d_grad_features) VR_TRY(c->q_feat_fgrad.grow(std::max<size_t>(N, 1) * C, "hipMalloc(feature gradient staging)"));
+    HIP_TRY(query_features_grad(A, d_xyz, (uint32_t)n, d_features, C, d_weights, d_weight_mass,
+                                d_grad ? c->q_feat_grad.get() : nullptr, d_grad_features ? c->q_feat_fgrad.get() : nullptr, d_grad,
+                                d_grad_features, d_grad_xyz, (hipStream_t)stream),
+            "query_features_grad_kernel");
+    return VR_OK;
+}
+
+vr_status vr_query_features_grad(vr_ctx* c, const float* xyz, size_t n, const float* features, uint32_t C, const float* weights,
+                                 const float* weight_mass, float* grad, float* grad_features, float* grad_xyz) {
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_features_grad", n, A));
+    const size_t N = (size_t)std::max(A.num_prims, 0);
+    VR_TRY(features_check("vr_query_features_grad", n, N, C));
+    if (n == 0) {
+        grad_is_zero(0, N * 10, grad);
+        grad_is_zero(0, N * C, grad_features);
+        return VR_OK;
+    }
+    if (!xyz || !features) return fail(VR_ERR_INVALID, "vr_query_features_grad: NULL argument");
+    if (!grad && !grad_features && !grad_xyz) return fail(VR_ERR_INVALID, "vr_query_features_grad: all three outputs are NULL");
+    if (N == 0) {  // an empty scene: grad and grad_features have no entries, and no point has an active Gaussian
+        if (grad_xyz) std::memset(grad_xyz, 0, n * 3 * sizeof(float));
+        return VR_OK;
+    }
+    // (the points' rows follow the features' in the second result's workspace)
+    const size_t at_xyz = grad_features ? N * C : 0;
+    return host_form(c, {{c->q_in, xyz, n * 3, "query points"}, {c->q_feat, features, N * C, "query features"},
+                         {c->q_w, weights, n * (size_t)C, "query weights"}, {c->q_w2, weight_mass, n, "query weights"}},
+                     {{c->q_out, grad, N * 10, "query results"}, {c->q_out2, grad_features, N * C, "query results"},
+                      {c->q_out2, grad_xyz, n * 3, "query results", at_xyz}},
+                     "query_features_grad_kernel", [&] {
+                         return vr_query_features_grad_device(c, c->q_in.get(), n, c->q_feat.get(), C, dev<float>(c->q_w, weights),
+                                                              dev<float>(c->q_w2, weight_mass), dev<float>(c->q_out, grad),
+                                                              dev<float>(c->q_out2, grad_features),
+                                                              dev<float>(c->q_out2, grad_xyz, at_xyz), c->stream);
                      });
 }
 

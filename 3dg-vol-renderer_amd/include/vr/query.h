@@ -179,6 +179,48 @@ public:
         return grad;
     }
 
+    // The caller's own per-Gaussian vectors at points (vr_query_features): `features` holds C floats per scene Gaussian,
+    // row g for Gaussian g. The result holds F row-major, pos.size() * C floats, F[i][c] = sum_g m_g(pos_i) features[g][c]
+    // over evaluate_sigma's active set; *mass (if given) receives sum_g m_g(pos_i), *n_active the size of the set.
+    std::vector<float> evaluate_features(const std::vector<Eigen::Vector3f>& pos, const std::vector<float>& features, uint32_t C,
+                                         std::vector<float>* mass = nullptr, std::vector<uint32_t>* n_active = nullptr) const {
+        feature_rows("evaluate_features", features.size(), C);
+        vr_ctx* ctx = ready();
+        std::vector<float> xyz(3 * pos.size()), out(pos.size() * C);
+        for (size_t i = 0; i < pos.size(); ++i)
+            for (int k = 0; k < 3; ++k) xyz[3 * i + k] = pos[i][k];
+        if (mass) mass->assign(pos.size(), 0.0f);
+        if (n_active) n_active->assign(pos.size(), 0u);
+        vr_cpp::check(vr_query_features(ctx, xyz.data(), pos.size(), features.data(), C, out.data(), mass ? mass->data() : nullptr,
+                                        n_active ? n_active->data() : nullptr));
+        return out;
+    }
+
+    // The gradient of L = sum_i (sum_c weights[i][c] F[i][c] + weight_mass[i] mass[i]) for evaluate_features' F and mass
+    // (vr_query_features_grad): row g of the result (10 floats per scene Gaussian, transmittance_gradient's layout) is
+    // d L / d (mean[3], cov[6], density). An empty `weights` means 1 everywhere, an empty `weight_mass` 0. *grad_features
+    // (if given) receives C floats per Gaussian, d L / d features; *grad_pos (if given) 3 floats per point, d L / d pos.
+    std::vector<float> features_gradient(const std::vector<Eigen::Vector3f>& pos, const std::vector<float>& features, uint32_t C,
+                                         const std::vector<float>& weights = {}, const std::vector<float>& weight_mass = {},
+                                         std::vector<float>* grad_features = nullptr, std::vector<float>* grad_pos = nullptr) const {
+        feature_rows("features_gradient", features.size(), C);
+        if (!weights.empty() && weights.size() != pos.size() * C) throw std::runtime_error("features_gradient: C weights per point");
+        if (!weight_mass.empty() && weight_mass.size() != pos.size()) throw std::runtime_error("features_gradient: one mass weight per point");
+        vr_ctx* ctx = ready();
+        std::vector<float> xyz(3 * pos.size() + 1, 0.0f);  // (+ 1: never a NULL pointer)
+        for (size_t i = 0; i < pos.size(); ++i)
+            for (int k = 0; k < 3; ++k) xyz[3 * i + k] = pos[i][k];
+        std::vector<float> grad(10 * scene_.get_num_primitives() + 1, 0.0f);
+        if (grad_features) grad_features->assign(features.size(), 0.0f);
+        if (grad_pos) grad_pos->assign(3 * pos.size(), 0.0f);
+        vr_cpp::check(vr_query_features_grad(ctx, xyz.data(), pos.size(), features.data(), C, weights.empty() ? nullptr : weights.data(),
+                                             weight_mass.empty() ? nullptr : weight_mass.data(), grad.data(),
+                                             grad_features && !features.empty() ? grad_features->data() : nullptr,
+                                             grad_pos && !pos.empty() ? grad_pos->data() : nullptr));
+        grad.pop_back();
+        return grad;
+    }
+
     // integrator.h:422-498 MultiScatterGaussians::get_free_flight_distance(ray, events, target_tau) per ray, the
     // events being the ray's own: the collision distance, or -1 where the ray leaves the mixture before the
     // target is reached. *albedo (if given) receives evaluate_albedo (gmm.h:128-143) over the critical segment's
@@ -197,6 +239,11 @@ public:
     }
 
 private:
+    // `features` holds C floats for each of the scene's Gaussians.
+    void feature_rows(const char* what, size_t words, uint32_t C) const {
+        if (C == 0 || C > VR_FEATURES_MAX_CHANNELS) throw std::runtime_error(std::string(what) + ": C must lie in [1, 64]");
+        if (words != (size_t)scene_.get_num_primitives() * C) throw std::runtime_error(std::string(what) + ": C features per Gaussian");
+    }
     // t of size K is one row shared by all rays (stride 0), of size n * K a row per ray (stride K).
     static size_t profile_stride(const char* what, size_t n, size_t nt, uint32_t K) {
         if (K == 0) throw std::runtime_error(std::string(what) + ": K must be positive");

@@ -693,6 +693,71 @@ class Device:
                       kind.ptr(grad) if N > 0 else None, kind.ptr(gx))
         return (grad, gx) if gaussians and positions else grad if gaussians else gx
 
+    def evaluate_features(self, scene, points, features, return_mass=False, return_active=False):
+        """The caller's per-Gaussian vectors at n points (vr_query_features): points (n, 3) float32, features (N, C)
+        float32 of the same kind (numpy or torch), row g for scene Gaussian g, 1 <= C <= VR_FEATURES_MAX_CHANNELS.
+        Returns F (n, C) with F[i, c] = sum_g m_g(x_i) features[g, c] over query_sigma's active set (m: its f32 mu_t; the
+        sum in double, rounded once), or (F, mass), (F, n_active), (F, mass, n_active) with mass (n,) = sum_g m_g(x_i)
+        and the size of the set. A channel of ones has the bits of mass; F / mass is the mass-weighted mean of the
+        features at the point. A channel's bits do not depend on C or on its place among the channels."""
+        kind = _ArrayKind(points, _query_point_args(points))
+        C = _query_feature_args(features, "features", None, kind.torch, "Gaussians")
+        n = points.shape[0]
+        _query_feature_sizes(n, features.shape[0], C)
+        N = scene.get_num_primitives()
+        if features.shape[0] != N:
+            raise ValueError(f"features has {features.shape[0]} rows for {N} Gaussians")
+        self.upload(scene)
+        self._check_kind(kind, points, features)
+        run = n > 0 and N > 0  # (otherwise every result is zero and nothing is launched)
+        out = kind.new((n, C), zero=not run)
+        mass = kind.new(n, zero=not run) if return_mass else None
+        act = kind.new(n, np.int32, zero=not run) if return_active else None  # (the library's uint32 counts)
+        if run:
+            kind.call("vr_query_features", self._h, kind.ptr(kind.contiguous(points)), n, kind.ptr(kind.contiguous(features)), C,
+                      kind.ptr(out), kind.ptr(mass), kind.ptr(act))
+        got = (out,) + ((mass,) if return_mass else ()) + ((act,) if return_active else ())
+        return got if len(got) > 1 else out
+
+    def features_gradient(self, scene, points, features, weights=None, weight_mass=None, gaussians=True, features_grad=True,
+                            positions=False):
+        """The gradient of L = sum_i (sum_c weights[i, c] F[i, c] + weight_mass[i] mass[i]) for evaluate_features' F and mass
+        (vr_query_features_grad). weights (n, C) float32 or None (1 everywhere), weight_mass (n,) float32 or None (0).
+        gaussians=True: the (N, 10) array d L / d (mean[3], cov6 [xx xy xz yy yz zz], density) of scene Gaussian g, in
+        query_transmittance_grad's layout; features_grad=True: the (N, C) array d L / d features; positions=True: the
+        (n, 3) array d L / d points. Returns the one asked for, or a tuple of those asked for in that order. Only what
+        is asked for is computed: positions alone runs without a single atomic add. The active set is query_sigma's bit
+        for bit and is not differentiated; a point in no ellipsoid, or with a non-finite coordinate, contributes nothing
+        and gets a zero row. The per-Gaussian sums are double atomics: reproducible to the rounding of a double sum."""
+        kind = _ArrayKind(points, _query_point_args(points))
+        n = points.shape[0]
+        C = _query_feature_args(features, "features", None, kind.torch, "Gaussians")
+        if not (gaussians or features_grad or positions):
+            raise ValueError("features_gradient: ask for gaussians, features_grad, positions or any of them together")
+        if weights is not None and _query_feature_args(weights, "weights", n, kind.torch, "points") != C:
+            raise ValueError(f"weights has {weights.shape[1]} columns for {C} channels")
+        if weight_mass is not None:
+            if _query_f32(weight_mass, "weight_mass", ()) != kind.torch:
+                raise ValueError("weight_mass must be of the same kind as points")
+            if weight_mass.shape[0] != n:
+                raise ValueError(f"weight_mass has {weight_mass.shape[0]} entries for {n} points")
+        _query_feature_sizes(n, features.shape[0], C)
+        N = scene.get_num_primitives()
+        if features.shape[0] != N:
+            raise ValueError(f"features has {features.shape[0]} rows for {N} Gaussians")
+        self.upload(scene)
+        self._check_kind(kind, points, features, weights, weight_mass)
+        run = n > 0 and N > 0  # (otherwise every result is zero and nothing is launched)
+        grad = kind.new((N, 10), zero=not run) if gaussians else None
+        gf = kind.new((N, C), zero=not run) if features_grad else None
+        gx = kind.new((n, 3), zero=not run) if positions else None
+        if run:
+            kind.call("vr_query_features_grad", self._h, kind.ptr(kind.contiguous(points)), n, kind.ptr(kind.contiguous(features)),
+                      C, kind.ptr(kind.contiguous(weights)), kind.ptr(kind.contiguous(weight_mass)), kind.ptr(grad), kind.ptr(gf),
+                      kind.ptr(gx))
+        got = tuple(a for a in (grad, gf, gx) if a is not None)
+        return got if len(got) > 1 else got[0]
+
     def query_events(self, scene, origins, directions):
         """GaussianMixtureModel::intersect_events (gmm.h:457-515) for n rays. Returns (offsets, t, gaussian,
         entering): ray i's events are the slice offsets[i]:offsets[i + 1] (offsets: (n + 1,) int64) of t
@@ -890,6 +955,27 @@ def _query_profile_args(x, name, n, torch_in, shared_ok):
 
 def _query_point_args(points):
     return _query_f32(points, "points", (3,))
+
+
+def _query_feature_args(x, name, rows, torch_in, of):
+    """Checks a feature query's rows or weights before anything reaches the library: float32, (rows, C) with
+    1 <= C <= VR_FEATURES_MAX_CHANNELS (rows None: any number), of the points' kind. Returns C."""
+    shape = tuple(getattr(x, "shape", ()))
+    if len(shape) != 2:
+        raise ValueError(f"{name} must have shape ({'N' if rows is None else rows}, C), not {shape}")
+    C = shape[1]
+    if not 1 <= C <= L.VR_FEATURES_MAX_CHANNELS:
+        raise ValueError(f"{name} has {C} channels: 1 to {L.VR_FEATURES_MAX_CHANNELS} are allowed")
+    if _query_f32(x, name, (C,)) != torch_in:
+        raise ValueError(f"{name} must be of the same kind as points")
+    if rows is not None and shape[0] != rows:
+        raise ValueError(f"{name} has {shape[0]} rows for {rows} {of}")
+    return C
+
+
+def _query_feature_sizes(n, N, C):
+    if n * C >= 2 ** 31 or N * C >= 2 ** 31:
+        raise ValueError(f"{n} points and {N} Gaussians of {C} channels: more than 2^31 - 1 entries in one call")
 
 
 # ---- ray grids (vr_render_rays, include/vr_hip.h): Integrator.render_rays ----

@@ -30,6 +30,7 @@ VR_OPT_FF_KERNEL = 13
 VR_OPT_SEC_FILTER = 14
 VR_GRAD_FROZEN_BOUNDS = 1  # vr_query_transmittance_grad / _ray_grad / _profile_grad flags
 VR_PROFILE_MAX_SAMPLES = 1024  # vr_query_transmittance_profile: the most samples per ray
+VR_FEATURES_MAX_CHANNELS = 64  # vr_query_features: the most channels per Gaussian
 
 f3 = ctypes.c_float * 3
 
@@ -199,6 +200,10 @@ SIGNATURES = {
     "vr_query_sigma_device": (ST, [P, P, ctypes.c_size_t, P, P, P]),
     "vr_query_sigma_grad": (ST, [P, FP, FP, ctypes.c_size_t, FP, FP]),
     "vr_query_sigma_grad_device": (ST, [P, P, P, ctypes.c_size_t, P, P, P]),
+    "vr_query_features": (ST, [P, FP, ctypes.c_size_t, FP, ctypes.c_uint32, FP, FP, U32P]),
+    "vr_query_features_device": (ST, [P, P, ctypes.c_size_t, P, ctypes.c_uint32, P, P, P, P]),
+    "vr_query_features_grad": (ST, [P, FP, ctypes.c_size_t, FP, ctypes.c_uint32, FP, FP, FP, FP, FP]),
+    "vr_query_features_grad_device": (ST, [P, P, ctypes.c_size_t, P, ctypes.c_uint32, P, P, P, P, P, P]),
     "vr_query_events_count_device":(ST, [P, P, ctypes.c_size_t, P, ctypes.POINTER(ctypes.c_uint64)]),
     "vr_query_events_fill_device": (ST, [P, P, ctypes.c_size_t, P, P, P, ctypes.c_uint64, P]),
     "vr_query_events": (ST, [P, P, ctypes.c_size_t, U32P, FP, U32P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),

@@ -29,11 +29,27 @@ Device.query_transmittance_profile_grad): one tree walk per ray in forward, one 
 
     tau = optical_depth_profile(mean, cov6, density, albedo, origins, directions, t)   # (n, K); t is (K,) or (n, K)
     T = torch.exp(-torch.cat([torch.zeros_like(tau[:, :1]), tau], 1))                   # emission-absorption quadrature:
+    x = (origins[:, None] + t_mid[..., None] * directions[:, None]).reshape(-1, 3)      # a sample point per interval
+    F, mass = features(mean, cov6, density, albedo, rgb_g, x)                           # (n K, 3), (n K,)
+    colour = (F / mass.clamp_min(1e-30)[:, None]).reshape(n, K, 3)                      # the mixture's colour there
     rgb = ((T[:, :-1] - T[:, 1:])[..., None] * colour).sum(1)                           # sum_k (T_k - T_k+1) c_k
-    loss.backward()                                                                     # mean.grad, cov6.grad, density.grad
+    loss.backward()                                                                     # mean.grad, cov6.grad, density.grad,
+                                                                                        # rgb_g.grad
 
 optical_depth_profile_resident is the same for parameters on the rays' device. Backward is one profile-gradient call
 with grad_output as the (n, K) weights; origins, directions, t and albedo get no gradient.
+
+The caller's own per-Gaussian vectors at points (Device.evaluate_features / Device.features_gradient), the colour of the
+quadrature above among them:
+
+    F, mass = features(mean, cov6, density, albedo, feats, points)               # (n, C) = sum_g m_g(x) feats[g], (n,)
+
+feats is (N, C): emission, RGB, SH coefficients, semantic features. features_resident is the same for parameters and
+feats on the points' device. Differentiable with respect to mean, cov6, density, feats and points; albedo gets None
+(neither output depends on it). Backward is one Device.features_gradient call with (grad_F, grad_mass) as its (weights,
+weight_mass), asking only for the outputs some input needs; exact over the forward's active set (float64 per active
+Gaussian), the 3-sigma cut-off not differentiated, not differentiable a second time. One profile call plus one feature
+call is a differentiable radiance-field renderer on the uploaded tree.
 
 The extinction field itself, at the caller's points (Device.query_sigma / Device.query_sigma_grad):
 
@@ -213,3 +229,52 @@ def sigma_resident(mean, cov6, density, albedo, points, device=0):
     (ValueError otherwise), and forward uploads them with Device.upload_gaussians instead of copying them to the
     host. Same arguments, same gradients."""
     return _Sigma.apply(mean, cov6, density, albedo, points, device, True)
+
+
+class _Features(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mean, cov6, density, albedo, feats, points, device, resident):
+        if resident and feats.device != points.device:
+            raise ValueError(f"feats is on {feats.device}, the points on {points.device}: a resident scene's "
+                             "features live on the points' device")
+        dev, scene = _scene_of(mean, cov6, density, albedo, points, "the points", device, resident)
+        pts = points.detach().contiguous()
+        f = feats.detach().to(device=pts.device, dtype=torch.float32).contiguous()
+        ctx.dev, ctx.scene, ctx.pts, ctx.f = dev, scene, pts, f
+        ctx.like = (mean, cov6, density)
+        ctx.feats_like, ctx.pts_dtype = feats, points.dtype
+        F, mass = dev.evaluate_features(scene, pts, f, return_mass=True)
+        return F, mass
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_F, grad_mass):
+        need_g, need_f, need_x = any(ctx.needs_input_grad[:3]), ctx.needs_input_grad[4], ctx.needs_input_grad[5]
+        out, gf, gx = (None,) * 3, None, None
+        if need_g or need_f or need_x:
+            got = ctx.dev.features_gradient(ctx.scene, ctx.pts, ctx.f, grad_F.to(torch.float32).contiguous(),
+                                              grad_mass.to(torch.float32).contiguous(), gaussians=need_g, features_grad=need_f,
+                                              positions=need_x)
+            got = list(got) if isinstance(got, tuple) else [got]
+            if need_g:
+                out = _split_grad(got.pop(0), ctx.like, ctx.needs_input_grad[:3])
+            if need_f:
+                gf = got.pop(0).to(device=ctx.feats_like.device, dtype=ctx.feats_like.dtype)
+            if need_x:
+                gx = got.pop(0).to(ctx.pts_dtype)
+        return out + (None, gf, gx, None, None)
+
+
+def features(mean, cov6, density, albedo, feats, points, device=0):
+    """(F (n, C), mass (n,)) float32 at points ((n, 3) float32 tensor on cuda:`device`): F[i, c] = sum_g m_g(x_i) feats[g, c]
+    and mass[i] = sum_g m_g(x_i) over the Gaussians active at x_i, for the mixture mean (N, 3), cov6 (N, 6) [xx xy xz yy yz
+    zz], density (N,), albedo (N,) and the caller's feats (N, C) (tensors on any device): the values of
+    Device.evaluate_features. Differentiable with respect to mean, cov6, density, feats and points; albedo gets None."""
+    return _Features.apply(mean, cov6, density, albedo, feats, points, device, False)
+
+
+def features_resident(mean, cov6, density, albedo, feats, points, device=0):
+    """features for parameters that never leave the GPU: mean, cov6, density, albedo and feats must be on the points'
+    device (ValueError otherwise), and forward uploads the scene with Device.upload_gaussians instead of copying it to the
+    host. Same arguments, same gradients."""
+    return _Features.apply(mean, cov6, density, albedo, feats, points, device, True)

@@ -24,6 +24,7 @@ extern "C" {
 #endif
 
 #define VR_ABI_VERSION 11
+/* (still 11 with vr_query_features / vr_query_features_grad: entry points were added, none changed) */
 
 typedef enum vr_status {
     VR_OK = 0,
@@ -707,6 +708,56 @@ vr_status vr_query_sigma_grad(vr_ctx* ctx, const float* xyz, const float* weight
                               float* grad_xyz);
 vr_status vr_query_sigma_grad_device(vr_ctx* ctx, const float* d_xyz, const float* d_weight_as, size_t n, float* d_grad,
                                      float* d_grad_xyz, void* stream);
+
+/* The caller's own per-Gaussian vectors at n points xyz[3n]: features[N * C], row g (C floats) for SCENE Gaussian g
+ * (emission, RGB, SH coefficients, semantic features, a temperature ...), passed per call, not part of the scene. Over
+ * the active set A(x) of vr_query_sigma (the same f32 decision, the same walks: bit for bit the same set), with m_g the
+ * f32 mu_t of vr_query_sigma:
+ *   mass[i]        = f32( sum_{g in A} (double) m_g )                    (may be NULL)
+ *   out[C i + c]   = f32( sum_{g in A} (double)(m_g * features[C g + c]) )   (one f32 multiply per term)
+ *   n_active[i]    = |A|                                                  (may be NULL)
+ * both sums in double, rounded to f32 once. A point whose summed m is <= 0 (non-positive densities only; vr_query_sigma's
+ * (0, 0)) gets a +0 row and mass +0; a point whose child-pair walk is deeper than the builder allows (vr_query_sigma's
+ * NaN) gets NaN in out and mass and n_active 0. Hence two exact ties: a channel whose features are all 1.0f has the bits
+ * of mass; and with C = 1 and features = the albedos, a = out / mass (correctly rounded), sigma_s = a * mass,
+ * sigma_a = (1 - a) * mass, (0, 0) where mass is not > 0, are vr_query_sigma's (sigma_a, sigma_s) bit for bit. A channel's
+ * bits depend neither on C nor on the channel's place among the C. vr_query_sigma is the one-channel case.
+ * C == 0, C > VR_FEATURES_MAX_CHANNELS, n * C >= 2^31 or num_primitives * C >= 2^31: VR_ERR_INVALID before anything is
+ * launched; xyz, features or out NULL with n > 0: VR_ERR_INVALID; the common errors above apply. A scene without
+ * Gaussians gives zeros. */
+#define VR_FEATURES_MAX_CHANNELS 64   /* SH degree 3 x RGB = 48, with room; bounds the w/f row pass per hit */
+vr_status vr_query_features(vr_ctx* ctx, const float* xyz, size_t n, const float* features, uint32_t C, float* out,
+                            float* mass, uint32_t* n_active);
+vr_status vr_query_features_device(vr_ctx* ctx, const float* d_xyz, size_t n, const float* d_features, uint32_t C,
+                                   float* d_out, float* d_mass, uint32_t* d_n_active, void* stream);
+
+/* The gradient of L = sum_i ( sum_c w_ic F_ic + u_i mass_i ), F = vr_query_features' out, with respect to the Gaussians,
+ * the feature rows and the points. weights[n * C] = w (NULL: 1 everywhere), weight_mass[n] = u (NULL: 0).
+ * Notation of vr_query_sigma_grad: per active (i, g), from the record's f32 numbers, the point, the row and the weights
+ * read as doubles, p = x - mean, q = p.Mp, e = norm exp(-q / 2), m = rho e, and c = u_i + sum_c w_ic f_gc:
+ *   grad[10 g + k]           d L / d (mean[3], cov[6] = {xx, xy, xz, yy, yz, zz}, density) of SCENE Gaussian g, the layout
+ *                            of vr_query_transmittance_grad: mean: c m M p; cov: c m ((Mp)(Mp)^T - M) / 2, an
+ *                            off-diagonal entry the derivative with respect to the stored number (twice that); density: c e
+ *   grad_features[C g + c]   w_ic m
+ *   grad_xyz[3 i + k]        -c m M p
+ * summed over the active pairs of the points that contribute. Any output may be NULL (all three with n > 0:
+ * VR_ERR_INVALID); every entry of a given output is written. grad_features == NULL runs without the feature staging and
+ * its adds, grad == NULL without the other ten adds per pair, and grad_xyz alone without a single atomic add.
+ * A point whose summed m is <= 0 and a point with a non-finite coordinate contribute nothing and get a +0 grad_xyz row; a
+ * point whose child-pair walk is deeper than the builder allows contributes nothing and gets a NaN row (adds of a point
+ * that turns out not to contribute are added again with the opposite sign, as in vr_query_sigma_grad). n == 0 is VR_OK:
+ * it zeroes grad and grad_features if given and launches nothing. The other errors are vr_query_features'.
+ * Arithmetic: the active set is the forward's f32 decision and is not differentiated; everything on a decided pair is
+ * double; per Gaussian the sums are double atomic adds into staging rows (10 + C doubles per Gaussian, the query's own,
+ * zeroed on `stream` by each call), staged per unit density (c e M p, -c e p p^T / 2, c e) and converted as
+ * vr_query_transmittance_grad's are; the sums per point stay in registers; each result is rounded to f32 once.
+ * Reproducible to the rounding of a double sum (grad_xyz bit for bit). Not differentiable a second time. */
+vr_status vr_query_features_grad(vr_ctx* ctx, const float* xyz, size_t n, const float* features, uint32_t C,
+                                 const float* weights, const float* weight_mass, float* grad, float* grad_features,
+                                 float* grad_xyz);
+vr_status vr_query_features_grad_device(vr_ctx* ctx, const float* d_xyz, size_t n, const float* d_features, uint32_t C,
+                                        const float* d_weights, const float* d_weight_mass, float* d_grad,
+                                        float* d_grad_features, float* d_grad_xyz, void* stream);
 
 /* GaussianMixtureModel::intersect_events (gmm.h:457-515; tmax is not read): per ray the events of every
  * Gaussian it hits, an entry at t_enter (clamped to 0 for an origin inside) and an exit at t_exit, sorted by

@@ -6,7 +6,7 @@ rays packed on the device), every query is warmed up, and the figure is the medi
 events on torch's current stream. Prints one JSON line and, with --out, writes it to a file.
 
     python tools/query_bench.py [--gaussians 1000000] [--rays 4194304] [--points 4194304] [--repeats 5] [--out F]
-                                [--flight-scene FILE] [--only all|mixture|flight|grad|raygrad|upload|sigmagrad|profile]
+                                [--flight-scene FILE] [--only all|mixture|flight|grad|raygrad|upload|sigmagrad|profile|features]
 
 --only grad times the optical-depth gradient query (Device.query_transmittance_grad, unit weights, moving and frozen
 bounds) beside the tau query on the same rays, on --flight-scene and on the make_random scene (--gaussians 0 skips it).
@@ -15,6 +15,10 @@ with unit=True on the same stored directions).
 --only sigmagrad times the sigma gradient query (Device.query_sigma_grad, weights None: both outputs, positions only,
 Gaussians only) beside query_sigma on the same points, on a make_random scene of --gaussians Gaussians: --points points,
 point i in or just outside Gaussian i mod N (mean + chol(cov) r u, u a uniform direction, r uniform in [0, 3.3]).
+--only features times the feature query (Device.evaluate_features with the mass and the counts) at C = 1, 3 and 48 channels
+and its gradient with all three outputs (Device.features_gradient, signed weights) beside query_sigma and
+query_sigma_grad (both outputs) on sigmagrad's points, each both with one call per timed interval and with ten (the device
+stays busy, which hides the host's time per call).
 --only profile times the transmittance profile (Device.query_transmittance_profile, --profile-k samples per ray, ascending
 through the cloud, a row per ray) beside K calls of the tau query on the same rays, and its gradient
 (Device.query_transmittance_profile_grad, unit weights) beside the gradient query on the n K expanded rays, on
@@ -68,7 +72,7 @@ def main():
     ap.add_argument("--seed", type=int, default=2025)
     ap.add_argument("--out", default=None)
     ap.add_argument("--flight-scene", default=os.path.join(ROOT, "tests", "golden", "scenes", "1000_random.txt"))
-    ap.add_argument("--only", choices=("all", "mixture", "flight", "grad", "raygrad", "upload", "sigmagrad", "profile"),
+    ap.add_argument("--only", choices=("all", "mixture", "flight", "grad", "raygrad", "upload", "sigmagrad", "profile", "features"),
                     default="all")
     ap.add_argument("--profile-k", default="8,64", help="samples per ray of --only profile, comma-separated")
     ap.add_argument("--profile-forward-only", action="store_true")
@@ -103,6 +107,9 @@ def main():
     if args.only == "sigmagrad":
         res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
         res.update(sigmagrad(args, dev, timed))
+    if args.only == "features":
+        res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
+        res.update(features(args, dev, timed))
     if args.only == "profile":
         res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
         res.update(profile(args, dev, o, d, timed))
@@ -211,6 +218,49 @@ def sigmagrad(args, dev, timed):
            "all_ms": {"sigma": s_all, "both": b_all, "positions": x_all, "gaussians": g_all}}
     return {"sigmagrad": out, "timing": "median of HIP-event intervals on torch's current stream, inputs on the device; "
                                         "each call allocates its result tensors"}
+
+
+def features(args, dev, timed):
+    """The feature query at C = 1, 3 and 48 channels and its gradient with all three outputs, beside the sigma query and
+    the sigma gradient (both outputs) on the same points: sigmagrad's points on a make_random scene."""
+    import torch
+    scene = vr.Scene(vr.Scene.GAUSSIANS)
+    scene.add_random_gaussians(args.gaussians, seed=args.seed, variant=0)
+    g = scene.gaussians().astype(np.float64)
+    c6 = g[:, 3:9]
+    cov = np.stack([c6[:, [0, 1, 2]], c6[:, [1, 3, 4]], c6[:, [2, 4, 5]]], 1)
+    rng = np.random.default_rng(7)
+    u = rng.normal(size=(args.points, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    r = rng.uniform(0.0, 3.3, args.points)
+    k = np.arange(args.points) % len(g)
+    p = torch.tensor((g[k, 0:3] + np.einsum("nij,nj->ni", np.linalg.cholesky(cov)[k], r[:, None] * u)).astype(np.float32)).cuda()
+    dev.upload(scene)
+    out = {"scene": f"make_random_{args.gaussians}", "gaussians": scene.get_num_primitives(), "points": args.points, "all_ms": {}}
+
+    def both(name, fn):
+        """(one call per interval, a tenth of ten calls per interval): the second keeps the device busy, so the host's
+        time per call (argument checks, result tensors) is hidden where the first includes it."""
+        one, one_all, res = timed(fn)
+        ten, ten_all, _ = timed(lambda: [fn() for _ in range(10)])
+        out["all_ms"][name], out["all_ms"][name + "_x10"] = one_all, ten_all
+        return one, ten / 10.0, res
+
+    s1, s10, sg = both("sigma", lambda: dev.query_sigma(scene, p, return_active=True))
+    g1, g10, _ = both("sigma_grad", lambda: dev.query_sigma_grad(scene, p, gaussians=True, positions=True))
+    out.update({"sigma_ms": s1, "sigma_busy_ms": s10, "sigma_grad_ms": g1, "sigma_grad_busy_ms": g10})
+    for C in (1, 3, 48):
+        f = torch.tensor(rng.uniform(-1, 1, (len(g), C)).astype(np.float32)).cuda()
+        w = torch.tensor(rng.uniform(-1, 1, (args.points, C)).astype(np.float32)).cuda()
+        m = torch.tensor(rng.uniform(-1, 1, args.points).astype(np.float32)).cuda()
+        fw1, fw10, _ = both(f"features_C{C}", lambda: dev.evaluate_features(scene, p, f, return_mass=True, return_active=True))
+        bw1, bw10, _ = both(f"features_grad_C{C}", lambda: dev.features_gradient(scene, p, f, w, m, positions=True))
+        out[f"C{C}"] = {"features_ms": fw1, "features_busy_ms": fw10, "features_grad_ms": bw1, "features_grad_busy_ms": bw10,
+                        "features_over_sigma": fw1 / s1, "features_busy_over_sigma_busy": fw10 / s10,
+                        "features_grad_over_sigma_grad": bw1 / g1, "features_grad_busy_over_sigma_grad_busy": bw10 / g10}
+    out["mean_active"], out["max_active"] = float(sg[1].float().mean()), int(sg[1].max())
+    return {"features": out, "timing": "median of HIP-event intervals on torch's current stream, inputs on the device; "
+                                       "each call allocates its result tensors; *_busy_ms: ten calls per interval, divided by ten"}
 
 
 def upload(args, dev, o, d):

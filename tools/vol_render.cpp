@@ -30,6 +30,11 @@
 // --query-sigma-grad RAYS.bin (the same file) prints MixtureQuery::sigma_gradient at the file's points, all weights (1, 1):
 // one line `sg <scene index> <11 hex words>` per Gaussian (d/d mean[3], cov[6], density, albedo), then one line
 // `sx <point index> <3 hex words>` per point (the gradient with respect to the point).
+// --query-features RAYS.bin FEATURES.bin (FEATURES.bin: uint32 N, uint32 C, then N rows of C floats, row g for scene Gaussian
+// g) prints MixtureQuery::evaluate_features at the first file's points: one line `fq <point index> <n_active> <mass and C
+// channels as hex words>` per point; then MixtureQuery::features_gradient there, all weights 1 and mass weights 0: one line
+// `fg <scene index> <10 hex words>` per Gaussian, one line `fr <scene index> <C hex words>` per Gaussian (the gradient with
+// respect to its row), one line `fx <point index> <3 hex words>` per point.
 // --query-profile RAYS.bin K (the same file) prints MixtureQuery::transmittance_profile of the file's rays at K distances
 // per ray, t[i][k] = tmax_i * (k + 1) / K in f32: one line `tp <ray index> <k> <t, Tr, tau as hex words>` per sample, then
 // MixtureQuery::transmittance_profile_gradient of the same samples, all weights 1: one line `pg <scene index> <10 hex
@@ -153,6 +158,46 @@ static int run_query_sigma_grad(const Scene& scene, const std::string& path) {
     return 0;
 }
 
+// --query-features: the caller's rows at the file's points, and the gradient of the sum of the result's entries.
+static int run_query_features(const Scene& scene, const std::string& path, const std::string& feat_path) {
+    std::vector<Ray> rays;
+    std::vector<float> tmax;
+    std::vector<Eigen::Vector3f> pos;
+    read_query_file(path, rays, tmax, pos);
+    std::FILE* f = std::fopen(feat_path.c_str(), "rb");
+    if (!f) throw std::runtime_error("cannot open " + feat_path);
+    uint32_t hdr[2] = {0, 0};
+    bool ok = std::fread(hdr, 4, 2, f) == 2 && hdr[1] >= 1 && hdr[1] <= VR_FEATURES_MAX_CHANNELS;
+    std::vector<float> feat(ok ? (size_t)hdr[0] * hdr[1] : 0);
+    ok = ok && std::fread(feat.data(), 4, feat.size(), f) == feat.size();
+    std::fclose(f);
+    if (!ok) throw std::runtime_error("short or malformed feature file " + feat_path);
+    const uint32_t C = hdr[1];
+    MixtureQuery q(scene);
+    std::vector<float> mass, gf, gx;
+    std::vector<uint32_t> na;
+    const std::vector<float> F = q.evaluate_features(pos, feat, C, &mass, &na);
+    for (size_t i = 0; i < pos.size(); ++i) {
+        std::printf("fq %zu %u %08x", i, na[i], fbits(mass[i]));
+        for (uint32_t k = 0; k < C; ++k) std::printf(" %08x", fbits(F[C * i + k]));
+        std::printf("\n");
+    }
+    const std::vector<float> g = q.features_gradient(pos, feat, C, {}, {}, &gf, &gx);
+    for (size_t i = 0; i < g.size() / 10; ++i) {
+        std::printf("fg %zu", i);
+        for (int k = 0; k < 10; ++k) std::printf(" %08x", fbits(g[10 * i + k]));
+        std::printf("\n");
+    }
+    for (size_t i = 0; i < gf.size() / C; ++i) {
+        std::printf("fr %zu", i);
+        for (uint32_t k = 0; k < C; ++k) std::printf(" %08x", fbits(gf[C * i + k]));
+        std::printf("\n");
+    }
+    for (size_t i = 0; i < gx.size() / 3; ++i)
+        std::printf("fx %zu %08x %08x %08x\n", i, fbits(gx[3 * i]), fbits(gx[3 * i + 1]), fbits(gx[3 * i + 2]));
+    return 0;
+}
+
 // --query-profile: tau and Tr at K distances up to each ray's tmax, and the gradient of the sum of those optical depths.
 static int run_query_profile(const Scene& scene, const std::string& path, int K) {
     if (K <= 0) throw std::runtime_error("--query-profile: K must be positive");
@@ -230,7 +275,8 @@ int main(int argc, char** argv) try {
     int inverse = 0, stoch = 4, final_spp = 0;
     uint64_t seed = 0;
     float lr = 1e-2f;
-    std::string ref_path, sfd_out, gif_path, query_path, query_grad_path, query_ray_grad_path, query_sigma_grad_path, query_profile_path;
+    std::string ref_path, sfd_out, gif_path, query_path, query_grad_path, query_ray_grad_path, query_sigma_grad_path, query_profile_path,
+        query_features_path, features_path;
     int profile_k = 0;
     int frames = 120;
     float fps = 30.0f;
@@ -261,6 +307,7 @@ int main(int argc, char** argv) try {
         else if (a == "--query-grad") query_grad_path = next();
         else if (a == "--query-ray-grad") query_ray_grad_path = next();
         else if (a == "--query-sigma-grad") query_sigma_grad_path = next();
+        else if (a == "--query-features") { query_features_path = next(); features_path = next(); }
         else if (a == "--query-profile") { query_profile_path = next(); profile_k = std::atoi(next()); }
         else if (a == "--gif") gif_path = next();
         else if (a == "--frames") frames = std::atoi(next());
@@ -321,6 +368,7 @@ int main(int argc, char** argv) try {
     if (!query_grad_path.empty()) return run_query_grad(scene, query_grad_path);
     if (!query_ray_grad_path.empty()) return run_query_ray_grad(scene, query_ray_grad_path);
     if (!query_sigma_grad_path.empty()) return run_query_sigma_grad(scene, query_sigma_grad_path);
+    if (!query_features_path.empty()) return run_query_features(scene, query_features_path, features_path);
     if (!query_profile_path.empty()) return run_query_profile(scene, query_profile_path, profile_k);
 
     if (!gif_path.empty()) {  // main.cpp:81-114
