@@ -4,7 +4,7 @@
 // nlights + env_samples secondary rays one after another. The transmittance T of the primary ray
 // never depends on those secondary rays (they only add to L), so the device path splits the loop:
 //
-//   1. march_kernel (one thread per pixel, 256-thread workgroup per 16x16 tile): walks the primary
+//   1. march_kernel (one lane per pixel, a 64-lane workgroup per 8x8 quarter of a 16x16 tile): walks the primary
 //      ray's steps and emits one *scatter record* per step with sigma_s > 0 (position, T*sigma_s,
 //      step index k, the active Gaussian set). Run twice: MODE 0 counts records per pixel, an
 //      exclusive scan places them, MODE 1 writes them — so the record order is a pure function of

@@ -28,17 +28,58 @@
 #endif
 
 namespace vr {
-namespace dev {
 
-#ifdef VR_DIAG_UNION  // diagnostic builds only: the march's counter slots report the union-walk census
-constexpr bool kDiagUnion = true;
-#else
-constexpr bool kDiagUnion = false;
-#endif
+constexpr int kMarchBlock = VR_MARCH_BLOCK;                                // lanes per workgroup of the tile pass
+constexpr int kActFast = VR_MARCH_ACT, kActBig = VR_MARCH_ACT_BIG;         // its active-list slots per lane (LDS)
+constexpr int kMarchStack4 = VR_MARCH_STACK4, kMarchDeep = VR_MARCH_DEEP;  // its 4-wide walks' LDS + private stack entries
+constexpr int kActFallback = 64, kWaveBlock = 64;  // the wave pass: active-list slots per pixel (LDS); one wave
+
+namespace dev {
 
 // ---------------------------------------------------------------------------------------------
 // Stage 1: primary march
+//
+// Every pixel is marched by march<>: the same queries, steps and records whichever pass runs it, so a pixel's records
+// do not depend on the pass. A pass differs in how pixels map to lanes, where the active list lives and how many
+// Gaussians it holds; a pixel that outgrows a pass (kOverflow) is queued for the next one and marched again from its
+// start.
+//   Tile  march_kernel           one pixel per lane, a workgroup of kMarchBlock lanes per 8x8 quarter of a 16x16 tile;
+//                                16 (or 32: march_big) active-list slots per lane in LDS. Overflow: the fallback queue.
+//   Wave  march_fallback_kernel  a fallback queue shorter than A.wide_min: one pixel per wave (the step's evaluation
+//                                split over the lanes), kActFallback slots in LDS. Overflow: the deep queue.
+//   Lane  march_wide_kernel      a longer fallback queue: one pixel per lane, kActWide slots per lane in global
+//                                memory. Overflow: the deep queue.
+//   Deep  march_deep_kernel      the deep queue: one pixel per wave, kActDeep slots in global memory. Overflow: an error
+//                                pixel (NaN, VR_ERR_OVERFLOW).
+// The tree a pass's window queries walk is the scene's (march_pass). Its boxes only propose candidates; every decision
+// is the exact quadratic.
 // ---------------------------------------------------------------------------------------------
+enum class MarchPass { Tile, Wave, Lane, Deep };
+enum class MarchTree {
+    Wide4,    // the 4-wide f16 tree (traverse_wide); a walk past its stack sends the pixel to the next pass
+    PairF16,  // the f16 child-pair tree: the deep pass of a scene with a 4-wide tree, where no walk may overflow
+    PairF32,  // the f32 child-pair tree, every pass (scenes whose leaf boxes are too small for f16 boxes)
+};
+constexpr MarchTree deep_tree(MarchTree TREE) { return TREE == MarchTree::Wide4 ? MarchTree::PairF16 : TREE; }
+
+// What follows from the pass, the tree and the tile pass's two choices: BIG, kActBig slots instead of kActFast (a 4-wide
+// scene whose frames overflow 16 on >= 5 % of their pixels), and TALL, a kStackSize-entry stack instead of
+// kShallowStack (a pair tree deeper than kShallowStack + 1: a child-pair walk pushes at most depth - 1 entries).
+struct MarchShape {
+    int act;    // active-list capacity
+    int stack;  // LDS stack entries per lane
+    int deep;   // private-memory stack entries of a 4-wide walk past them
+    bool coop;  // one pixel per wave (march)
+};
+constexpr MarchShape march_shape(MarchPass P, MarchTree TREE, bool BIG, bool TALL) {
+    const bool wide = TREE == MarchTree::Wide4;
+    if (P == MarchPass::Tile)
+        return {BIG ? kActBig : kActFast, wide ? kMarchStack4 : TALL ? kStackSize : kShallowStack, wide ? kMarchDeep : 0, false};
+    if (P == MarchPass::Wave) return {kActFallback, kStackSize, 0, true};
+    if (P == MarchPass::Lane) return {kActWide, kStackSize, 0, false};
+    return {kActDeep, kStackSize, 0, true};
+}
+
 // Early-out weight (t_eps > 0). Stopping after step k drops
 //   sum_{j>k} T_j sigma_s,j dt (Li_j + Le_j) / (4 pi) + T_end env
 // and T_j sigma_s,j dt is not bounded by T alone: the reference's point-sampled estimator can
@@ -106,7 +147,7 @@ __device__ __forceinline__ bool march_step(const RenderArgs& A, const Ray& ray, 
                 smu += __shfl(m, sl, 64);
                 smua += __shfl(ma, sl, 64);
                 if (!A.pure) tau_seg += __shfl(od, sl, 64);
-                if constexpr (S && !kDiagUnion) {
+                if constexpr (S) {
                     c.v[kCtrMu]++;
                     c.v[kCtrOD]++;
                     c.v[kCtrPrims]++;
@@ -127,7 +168,7 @@ __device__ __forceinline__ bool march_step(const RenderArgs& A, const Ray& ray, 
             smu += m;
             smua += m * g.albedo;
             if (!A.pure) tau_seg += optical_depth(g, q, t_k, t_k1);
-            if constexpr (S && !kDiagUnion) {
+            if constexpr (S) {
                 c.v[kCtrMu]++;
                 c.v[kCtrOD]++;
                 c.v[kCtrPrims]++;
@@ -136,7 +177,7 @@ __device__ __forceinline__ bool march_step(const RenderArgs& A, const Ray& ray, 
     }
     act.n = w;
     if (w == 0) return true;
-    if constexpr (S && !kDiagUnion) c.v[kCtrSteps]++;
+    if constexpr (S) c.v[kCtrSteps]++;
     float sigma_s = 0.0f;
     if (smu > 0.0f) {
         float a_mix = smua / smu;
@@ -216,83 +257,29 @@ __device__ __forceinline__ bool march_step(const RenderArgs& A, const Ray& ray, 
 // to the pixel's previous record (px_first / rec_next), so a pixel's records are visited in step
 // order by accumulate_kernel wherever they landed in memory. Records that do not fit the
 // capacity raise rec_alloc[2]; the host then grows the buffers and re-runs the march.
-// W: BVH window queries on the 4-wide half-precision tree (CAP-entry stack; a query that could
-// overflow it sends the pixel to the fallback kernel, which walks the pair tree).
-// COOP: the whole wave marches the same pixel (the fallback passes: a pixel whose active set
-// outgrew the fast kernel's slots marches serially for a long time). Every lane runs the same
+// <P, TREE, S, RAYS, BIG, TALL>: the pass, the tree its window queries walk, the instrumented build (vr_count_work), a ray
+// grid, and the tile pass's two choices; capacities and COOP follow (march_shape).
+// COOP: the whole wave marches the same pixel (the wave and deep passes: a pixel whose active set
+// outgrew the tile pass's slots marches serially for a long time). Every lane runs the same
 // queries and keeps its own identical copy of the active list; only the per-step evaluation of the
 // active list is split over the lanes (one Gaussian each), its sums and compaction then taken in
 // list order through lane broadcasts — the serial loop's operations in its order, so the result is
 // bit-identical — and lane 0 writes the records.
-#ifdef VR_DIAG_UNION
-// Diagnostic builds only (with vr_count_work): what a wave-coherent walk of the march's window queries would cost.
-// At every query call, the lanes running the query this iteration walk the 4-wide tree as one wave: a node is
-// fetched once for the wave (wave-uniform stack in LDS) and descended into if any lane's box test and prune keep
-// it (ballot). Counted per call, in the march counters' slots: kCtrSecRays += union node visits, kCtrMu += union
-// leaf visits, kCtrOD += the per-lane walk's node-fetch passes (the largest per-lane node-step count among the
-// calling lanes: what the SIMT walk's loop runs), kCtrSteps += calls; kCtrNodes keeps the per-lane node steps.
-template <typename Prune>
-__device__ void union_walk_count(const RenderArgs& A, const Ray& r0, Prune prune, Ctr& c) {
-    __shared__ int ustack[256];  // (march workgroups are one wave)
-    float ox = r0.ox, oy = r0.oy, oz = r0.oz;
-    node_space<true>(A, ox, oy, oz);
-    auto inv = [&](float d) {
-        d *= A.hn_scale;
-        return __frcp_rn(fabsf(d) > 1e-30f ? d : copysignf(1e-30f, d));
-    };
-    const float ix = inv(r0.dx), iy = inv(r0.dy), iz = inv(r0.dz);
-    const float oxi = ox * ix, oyi = oy * iy, ozi = oz * iz;
-    const uint64_t act = __ballot(1);
-    const bool first_lane = __lane_id() == (uint32_t)(__ffsll((unsigned long long)act) - 1);
-    uint32_t visits = 0, leaves = 0;
-    int sp = 0, node = 0;
-    for (;;) {
-        ++visits;
-        float key[4];
-        int32_t kr[4];
-        wide_children<Prune, false>(A, node, ix, iy, iz, oxi, oyi, ozi, prune, key, kr);
-        const int4 rf = reinterpret_cast<const int4*>(A.hnodes4 + node)[3];
-        const int32_t ref[4] = {rf.x, rf.y, rf.z, rf.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const bool any = __ballot(kr[i] != 0) != 0ull;
-            if (!any) continue;
-            if (ref[i] < 0) {
-                ++leaves;
-            } else if (sp < 256) {
-                if (first_lane) ustack[sp] = ref[i];
-                ++sp;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (sp == 0) break;
-        --sp;
-        node = __builtin_amdgcn_readfirstlane(ustack[sp]);
-    }
-    if (first_lane) {
-        c.v[kCtrSecRays] += visits;
-        c.v[kCtrMu] += leaves;
-        c.v[kCtrSteps] += 1u;
-    }
-}
-// Largest per-lane value among the calling lanes (bit-sliced ballots), added once.
-__device__ __forceinline__ void union_walk_simt(uint32_t steps, Ctr& c) {
-    const uint64_t act = __ballot(1);
-    uint32_t m = 0;
-    for (int b = 15; b >= 0; --b)
-        if (__ballot(steps >= (m | (1u << b))) != 0ull) m |= 1u << b;
-    if (__lane_id() == (uint32_t)(__ffsll((unsigned long long)act) - 1)) c.v[kCtrOD] += m;
-}
-#endif
-
 // (Measured and not kept, DESIGN.md §3: window queries starting in the subtree holding the window and climbing,
 // a fast-form pre-test of the candidates, look-ahead windows over 2-4 steps, a closest-entry query merged with
 // the following entrant query, a sorting network in the entrant walk; all bit-identical, all slower at C4.)
 // RAYS: the pixel marches its row of the caller's ray grid (GridArgs) instead of the camera's ray; everything after the
 // ray is the frame's. An invalid row (grid_ray) ends the pixel at once: NaN transmittance, no records, no error count.
-template <int ACT, bool S, bool H, bool W = false, int CAP = kStackSize, bool COOP = false, int DEEP = 0, bool RAYS = false>
+template <MarchPass P, MarchTree TREE, bool S, bool RAYS, bool BIG = false, bool TALL = false>
 __device__ int march(const FrameArgs<RAYS>& A, uint32_t p, int px, int py, int* act_base, int* stack, int stride, Ctr& c,
                      int act_stride = -1) {
+    static_assert(P == MarchPass::Deep ? TREE != MarchTree::Wide4 : TREE != MarchTree::PairF16,
+                  "the deep pass walks a pair tree, and it alone the f16 one (deep_tree)");
+    static_assert(P == MarchPass::Tile ? !(BIG && TREE != MarchTree::Wide4) && !(TALL && TREE == MarchTree::Wide4) : !BIG && !TALL,
+                  "BIG: the tile pass on the 4-wide tree; TALL: the tile pass on a pair tree");
+    constexpr MarchShape kShape = march_shape(P, TREE, BIG, TALL);
+    constexpr int ACT = kShape.act, CAP = kShape.stack, DEEP = kShape.deep;
+    constexpr bool COOP = kShape.coop, W = TREE == MarchTree::Wide4;
     const bool writer = !COOP || __lane_id() == 0u;  // COOP: lane 0 writes the pixel's records
     bool ray_ok = true;
     const Ray ray = pixel_ray<RAYS>(A, px, py, ray_ok);
@@ -318,7 +305,7 @@ __device__ int march(const FrameArgs<RAYS>& A, uint32_t p, int px, int py, int* 
             return traverse_wide<CAP, decltype(prune), decltype(leaf), NodeCount<S>, true, DEEP>(A, ray, stack, stride, prune, leaf,
                                                                                                 NodeCount<S>{&c});
         } else {
-            traverse<H>(A, ray, stack, stride, prune, leaf, NodeCount<S>{&c});
+            traverse<TREE == MarchTree::PairF16>(A, ray, stack, stride, prune, leaf, NodeCount<S>{&c});
             return true;
         }
     };
@@ -353,14 +340,7 @@ __device__ int march(const FrameArgs<RAYS>& A, uint32_t p, int px, int py, int* 
                     }
                     return true;
                 };
-#ifdef VR_DIAG_UNION
-                if constexpr (S && W && !COOP) union_walk_count(A, ray, prune_c, c);
-                const uint32_t n0 = c.v[kCtrNodes];
-#endif
                 if (!walk(prune_c, leaf_c)) return kOverflow;
-#ifdef VR_DIAG_UNION
-                if constexpr (S && W && !COOP) union_walk_simt(c.v[kCtrNodes] - n0, c);
-#endif
                 if (best == INFINITY) break;
                 k = kfirst(ts, nts, step, best);
                 // No entry lies in (t_lo, best) and ts[k - 1] < best: the step's entrant window (t_lo, t_k] holds
@@ -378,10 +358,6 @@ __device__ int march(const FrameArgs<RAYS>& A, uint32_t p, int px, int py, int* 
             auto prune_w = [&](float tmin, float tmax) {
                 return tmax >= t_lo - kTPad * (1.0f + fabsf(t_lo)) && tmin <= t_k + kTPad * (1.0f + t_k);
             };
-#ifdef VR_DIAG_UNION
-            if constexpr (S && W && !COOP) union_walk_count(A, ray, prune_w, c);
-            const uint32_t n1 = c.v[kCtrNodes];
-#endif
             const bool ok = walk_any(
                 prune_w,
                 [&](uint32_t first, uint32_t count) {
@@ -409,9 +385,6 @@ __device__ int march(const FrameArgs<RAYS>& A, uint32_t p, int px, int py, int* 
                     }
                     return true;
                 });
-#ifdef VR_DIAG_UNION
-            if constexpr (S && W && !COOP) union_walk_simt(c.v[kCtrNodes] - n1, c);
-#endif
             if (ovf || !ok) return kOverflow;
             kq = k + 1;
             if (!march_step<S, COOP>(A, ray, p, px, py, k, t_k, act, T, prev, c, writer)) break;
@@ -436,10 +409,13 @@ __device__ __forceinline__ void orphan_records(const RenderArgs& A, uint32_t p) 
         reinterpret_cast<float*>(A.rec_pos + r)[3] = kOrphanWeight;
 }
 
-template <int ACT, int BLOCK, bool S, int STACK, bool H, bool W = false, bool RAYS = false>
-__global__ __launch_bounds__(BLOCK) void march_kernel(FrameArgs<RAYS> A) {
-    __shared__ int s_act[ACT * BLOCK];
-    __shared__ int s_stack[STACK * BLOCK];
+// The tile pass. LDS per lane: (active-list slots + stack entries) * 4 B.
+template <MarchTree TREE, bool S, bool RAYS, bool BIG, bool TALL>
+__global__ __launch_bounds__(kMarchBlock) void march_kernel(FrameArgs<RAYS> A) {
+    constexpr int BLOCK = kMarchBlock;
+    constexpr MarchShape kShape = march_shape(MarchPass::Tile, TREE, BIG, TALL);
+    __shared__ int s_act[kShape.act * BLOCK];
+    __shared__ int s_stack[kShape.stack * BLOCK];
     // A workgroup is one 16x16 tile (BLOCK 256) or one of its 8x8 quarters (BLOCK 64: four times as
     // many, shorter workgroups, so the frame's last ones leave a shorter tail). Lanes never share LDS.
     constexpr uint32_t kParts = 256u / BLOCK;
@@ -452,7 +428,7 @@ __global__ __launch_bounds__(BLOCK) void march_kernel(FrameArgs<RAYS> A) {
     Ctr c{};
     int st = kOK;
     if (x < (int)A.width && y < (int)A.height) {
-        st = march<ACT, S, H, W, STACK, false, W ? VR_MARCH_DEEP : 0, RAYS>(A, p, x, y, s_act + threadIdx.x, s_stack + threadIdx.x, BLOCK, c);
+        st = march<MarchPass::Tile, TREE, S, RAYS, BIG, TALL>(A, p, x, y, s_act + threadIdx.x, s_stack + threadIdx.x, BLOCK, c);
     } else {
         A.px_first[p] = kNoRecord;
         A.px_T[p] = 0.0f;
@@ -468,13 +444,14 @@ __global__ __launch_bounds__(BLOCK) void march_kernel(FrameArgs<RAYS> A) {
     }
 }
 
-// The fallback passes march one pixel per wave (march<COOP>): a pixel lands here because its active
+// The wave pass marches one pixel per wave (march's COOP): a pixel lands here because its active
 // set is large, and its serial march was the tail of the whole march stage (~1 ms at C4, also for a
-// 1/8 multi-GPU share). BLOCK = one wave.
-template <int ACT, int BLOCK, bool S, bool H, bool W = false, bool RAYS = false>
-__global__ __launch_bounds__(BLOCK) void march_fallback_kernel(FrameArgs<RAYS> A) {
-    static_assert(BLOCK == 64, "one pixel per wave");
-    __shared__ int s_act[ACT * BLOCK];
+// 1/8 multi-GPU share).
+template <MarchTree TREE, bool S, bool RAYS>
+__global__ __launch_bounds__(kWaveBlock) void march_fallback_kernel(FrameArgs<RAYS> A) {
+    static_assert(kWaveBlock == 64, "one pixel per wave");
+    constexpr int BLOCK = kWaveBlock;
+    __shared__ int s_act[kActFallback * BLOCK];
     __shared__ int s_stack[kStackSize * BLOCK];
     const int tid = threadIdx.x;
     const uint32_t n = min(A.queue[0], A.queue_cap);
@@ -484,13 +461,13 @@ __global__ __launch_bounds__(BLOCK) void march_fallback_kernel(FrameArgs<RAYS> A
         int lx, ly, x, y;
         tile_pixel(A, p >> 8, (int)(p & 255u), lx, ly, x, y);
         Ctr c{};
-        // (W: the 4-wide walks — half the dependent node fetches of the pair tree on a single pixel's
-        // serial queries; a walk past the kStackSize stack goes to the deep pass)
-        int st = march<ACT, S, H, W, kStackSize, true, 0, RAYS>(A, p, x, y, s_act + tid, s_stack + tid, BLOCK, c);  // re-links px_first
+        // (Wide4: half the dependent node fetches of the pair tree on a single pixel's serial queries; a walk past
+        // the kStackSize stack goes to the deep pass)
+        int st = march<MarchPass::Wave, TREE, S, RAYS>(A, p, x, y, s_act + tid, s_stack + tid, BLOCK, c);  // re-links px_first
         if (tid != 0) continue;
         if constexpr (S)
             for (int i = 0; i < kNumCtr; ++i) atomicAdd(A.work + i, (unsigned long long)c.v[i]);
-        if (st == kOverflow) {  // more than ACT Gaussians active at one step: the deep pass
+        if (st == kOverflow) {  // more than kActFallback Gaussians active at one step: the deep pass
             orphan_records(A, p);
             const uint32_t slot = atomicAdd(A.deepq, 1u);
             if (slot < A.deepq_cap) A.deepq[1 + slot] = p;
@@ -508,7 +485,7 @@ __global__ __launch_bounds__(BLOCK) void march_fallback_kernel(FrameArgs<RAYS> A
 // queues shorter than A.wide_min (C4: 833 pixels). Same march<> operations as every other pass, so
 // a pixel's records do not depend on which pass marched it. Overflow (more than kActWide active, or a
 // 4-wide walk past its stack): the deep pass.
-template <bool S, bool H, bool W, bool RAYS = false>
+template <MarchTree TREE, bool S, bool RAYS>
 __global__ __launch_bounds__(kWideBlock) void march_wide_kernel(FrameArgs<RAYS> A) {
     __shared__ int s_stack[kStackSize * kWideBlock];
     const int tid = threadIdx.x;
@@ -520,7 +497,7 @@ __global__ __launch_bounds__(kWideBlock) void march_wide_kernel(FrameArgs<RAYS> 
         const uint32_t p = A.queue[1 + q];
         int lx, ly, x, y;
         tile_pixel(A, p >> 8, (int)(p & 255u), lx, ly, x, y);
-        const int st = march<kActWide, S, H, W, kStackSize, false, 0, RAYS>(A, p, x, y, A.wide_act + gt, s_stack + tid, kWideBlock, c, (int)nthreads);
+        const int st = march<MarchPass::Lane, TREE, S, RAYS>(A, p, x, y, A.wide_act + gt, s_stack + tid, kWideBlock, c, (int)nthreads);
         if (st == kOverflow) {
             orphan_records(A, p);
             const uint32_t slot = atomicAdd(A.deepq, 1u);
@@ -536,7 +513,8 @@ __global__ __launch_bounds__(kWideBlock) void march_wide_kernel(FrameArgs<RAYS> 
 // Pixels whose active set outgrew the fallback's 64 LDS slots: the same march with the active list in
 // global memory (kActDeep slots per lane, [slot][thread] rows, one pixel per wave).
 // Only an active set past kActDeep, Gaussians overlapping one point, fails (NaN, VR_ERR_OVERFLOW).
-template <bool S, bool H, bool RAYS = false>
+// TREE: a child-pair tree (deep_tree).
+template <MarchTree TREE, bool S, bool RAYS>
 __global__ __launch_bounds__(kDeepBlock) void march_deep_kernel(FrameArgs<RAYS> A) {
     static_assert(kDeepBlock == 64, "one pixel per wave");
     __shared__ int s_stack[kStackSize * kDeepBlock];
@@ -548,8 +526,7 @@ __global__ __launch_bounds__(kDeepBlock) void march_deep_kernel(FrameArgs<RAYS> 
         int lx, ly, x, y;
         tile_pixel(A, p >> 8, (int)(p & 255u), lx, ly, x, y);
         Ctr c{};
-        const int st =
-            march<kActDeep, S, H, false, kStackSize, true, 0, RAYS>(A, p, x, y, A.deep_act + gt, s_stack + tid, kDeepBlock, c, (int)nthreads);
+        const int st = march<MarchPass::Deep, TREE, S, RAYS>(A, p, x, y, A.deep_act + gt, s_stack + tid, kDeepBlock, c, (int)nthreads);
         if (tid != 0) continue;
         if constexpr (S)
             for (int i = 0; i < kNumCtr; ++i) atomicAdd(A.work + i, (unsigned long long)c.v[i]);
@@ -847,9 +824,6 @@ __global__ __launch_bounds__(64) void march_binned_kernel(RenderArgs A) {
 // ---------------------------------------------------------------------------------------------
 // Host launchers
 // ---------------------------------------------------------------------------------------------
-constexpr int kActFast = VR_MARCH_ACT, kActBig = VR_MARCH_ACT_BIG, kBlockFast = VR_MARCH_BLOCK;
-constexpr int kActFallback = 64, kBlockFallback = 64;
-
 hipError_t gauss_bin(const RenderArgs& A, bool emit, hipStream_t stream) {
     const unsigned grid = (unsigned)std::min<uint64_t>(((uint64_t)A.num_prims + 255) / 256, 16384);
     if (emit) hipLaunchKernelGGL(dev::bin_kernel<true>, dim3(std::max(grid, 1u)), dim3(256), 0, stream, A);
@@ -862,53 +836,50 @@ hipError_t gauss_bin_scan(const uint32_t* cnt, uint32_t* off, uint32_t n, void* 
 }
 
 // RAYS: a ray grid (never binned: the bins are built from the camera's tile frusta).
-template <bool S, bool H, bool RAYS = false>
-static hipError_t march_pass(const FrameArgs<RAYS>& A, hipStream_t stream) {
-    // LDS per 256-lane workgroup = (active-list slots + stack entries) * 1 KiB. Shallow trees use a
-    // 24-entry stack; the 16-slot active list overflows to the 64-slot fallback kernel. H: the
-    // half-precision node copy (boxes only propose candidates; every decision is the exact quadratic).
-    const bool shallow = A.bvh_depth <= kShallowStack + 1;
-    if (!RAYS && A.bin_ent != nullptr)  // binned march (its overflowing pixels re-run in the BVH fallback below)
+template <dev::MarchTree TREE, bool S, bool RAYS, bool BIG, bool TALL>
+static void tile_launch(const FrameArgs<RAYS>& A, hipStream_t stream) {
+    hipLaunchKernelGGL((dev::march_kernel<TREE, S, RAYS, BIG, TALL>), dim3(A.num_tiles * (256 / kMarchBlock)), dim3(kMarchBlock), 0, stream, A);
+}
+
+// The four passes of a frame on the scene's tree TREE.
+template <dev::MarchTree TREE, bool S, bool RAYS>
+static hipError_t march_passes(const FrameArgs<RAYS>& A, hipStream_t stream) {
+    if (!RAYS && A.bin_ent != nullptr) {  // binned march (its overflowing pixels re-run in the BVH fallback below)
         hipLaunchKernelGGL((dev::march_binned_kernel<S>), dim3(A.num_tiles * 4), dim3(64), 0, stream, static_cast<const RenderArgs&>(A));
-    else if (H && A.hnodes4 != nullptr && A.march_big)  // translucent, densely overlapping scenes (C2): fewer
-        // pixels overflow, and their records come from coherent quarter tiles instead of the fallback queue
-        hipLaunchKernelGGL((dev::march_kernel<kActBig, kBlockFast, S, VR_MARCH_STACK4, true, true, RAYS>), dim3(A.num_tiles * (256 / kBlockFast)),
-                           dim3(kBlockFast), 0, stream, A);
-    else if (H && A.hnodes4 != nullptr)  // 4-wide tree; a query that could overflow the stack goes to the fallback
-        hipLaunchKernelGGL((dev::march_kernel<kActFast, kBlockFast, S, VR_MARCH_STACK4, true, true, RAYS>), dim3(A.num_tiles * (256 / kBlockFast)),
-                           dim3(kBlockFast), 0, stream, A);
-    else if (shallow)
-        hipLaunchKernelGGL((dev::march_kernel<kActFast, kBlockFast, S, kShallowStack, H, false, RAYS>), dim3(A.num_tiles * (256 / kBlockFast)),
-                           dim3(kBlockFast), 0, stream, A);
-    else
-        hipLaunchKernelGGL((dev::march_kernel<kActFast, kBlockFast, S, kStackSize, H, false, RAYS>), dim3(A.num_tiles * (256 / kBlockFast)),
-                           dim3(kBlockFast), 0, stream, A);
+    } else if constexpr (TREE == dev::MarchTree::Wide4) {  // a query that could overflow the stack goes to the fallback
+        // march_big: translucent, densely overlapping scenes (C2): fewer pixels overflow, and their records come from
+        // coherent quarter tiles instead of the fallback queue
+        if (A.march_big) tile_launch<TREE, S, RAYS, true, false>(A, stream);
+        else tile_launch<TREE, S, RAYS, false, false>(A, stream);
+    } else {
+        if (A.bvh_depth <= kShallowStack + 1) tile_launch<TREE, S, RAYS, false, false>(A, stream);
+        else tile_launch<TREE, S, RAYS, false, true>(A, stream);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (H && A.hnodes4 != nullptr)  // the one-pixel-per-wave fallback march walks the 4-wide tree
-        hipLaunchKernelGGL((dev::march_fallback_kernel<kActFallback, kBlockFallback, S, H, true, RAYS>), dim3(1024), dim3(kBlockFallback), 0,
-                           stream, A);
-    else
-        hipLaunchKernelGGL((dev::march_fallback_kernel<kActFallback, kBlockFallback, S, H, false, RAYS>), dim3(1024), dim3(kBlockFallback), 0,
-                           stream, A);
+    // (exactly one of the wave and lane passes takes the fallback queue, by its length)
+    hipLaunchKernelGGL((dev::march_fallback_kernel<TREE, S, RAYS>), dim3(1024), dim3(kWaveBlock), 0, stream, A);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (H && A.hnodes4 != nullptr)  // (exactly one of the two passes takes the queue, by its length)
-        hipLaunchKernelGGL((dev::march_wide_kernel<S, H, true, RAYS>), dim3(kWideThreads / kWideBlock), dim3(kWideBlock), 0, stream, A);
-    else
-        hipLaunchKernelGGL((dev::march_wide_kernel<S, H, false, RAYS>), dim3(kWideThreads / kWideBlock), dim3(kWideBlock), 0, stream, A);
+    hipLaunchKernelGGL((dev::march_wide_kernel<TREE, S, RAYS>), dim3(kWideThreads / kWideBlock), dim3(kWideBlock), 0, stream, A);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL((dev::march_deep_kernel<S, H, RAYS>), dim3(kDeepThreads / kDeepBlock), dim3(kDeepBlock), 0, stream, A);
+    hipLaunchKernelGGL((dev::march_deep_kernel<dev::deep_tree(TREE), S, RAYS>), dim3(kDeepThreads / kDeepBlock), dim3(kDeepBlock), 0, stream, A);
     return hipGetLastError();
+}
+
+// The scene's tree: hnodes4 alone says whether it has its f16 trees (the invariant stated in fill_scene_args,
+// vr_frame.cpp), as in secondary_launch.
+template <bool S, bool RAYS = false>
+static hipError_t march_pass(const FrameArgs<RAYS>& A, hipStream_t stream) {
+    return A.hnodes4 != nullptr ? march_passes<dev::MarchTree::Wide4, S, RAYS>(A, stream)
+                                : march_passes<dev::MarchTree::PairF32, S, RAYS>(A, stream);
 }
 
 hipError_t gauss_march(const RenderArgs& A, hipStream_t stream, bool stats, const GridSrc* grid) {
     if (grid != nullptr) {  // a ray grid (no instrumented build: vr_count_work takes a camera)
         if (stats) return hipErrorInvalidValue;
-        const GridArgs G{A, *grid};
-        return A.hnodes != nullptr ? march_pass<false, true, true>(G, stream) : march_pass<false, false, true>(G, stream);
+        return march_pass<false, true>(GridArgs{A, *grid}, stream);
     }
-    if (A.hnodes != nullptr) return stats ? march_pass<true, true>(A, stream) : march_pass<false, true>(A, stream);
-    return stats ? march_pass<true, false>(A, stream) : march_pass<false, false>(A, stream);
+    return stats ? march_pass<true>(A, stream) : march_pass<false>(A, stream);
 }
 
 }  // namespace vr
