@@ -134,7 +134,8 @@ struct vr_ctx {
     vr::DevBuf<unsigned long long> q_keys, q_keys2;  // sort keys (in / out),
     vr::DevBuf<std::byte> q_tmp;                // scan + sort scratch
     vr::DevBuf<std::byte> q_ctl;      // words [0..3], [6] ray counters of the five persistent walks, [4..5] the 64-bit event total,
-                                      // [8], [9] the counters of the profile query's two walks
+                                      // [8], [9] the counters of the profile query's two walks, [10], [11] those of the
+                                      // radiance query's (its profile pass and its own)
     vr::DevBuf<double> q_grad;        // gradient query: 10 doubles of staging per Gaussian (tree order), zeroed per call
     vr::DevBuf<double> q_sgrad;       // sigma gradient query: 11 doubles of staging per Gaussian, its own (the two
                                       // gradient queries may be queued on different streams)
@@ -143,6 +144,9 @@ struct vr_ctx {
     vr::DevBuf<double> q_feat_grad;   // feature gradient query (kernels/vr_query_features.hip): 10 doubles of staging per
     vr::DevBuf<double> q_feat_fgrad;  // Gaussian and C per Gaussian for the rows' gradient (tree order), zeroed per call,
                                       // grown on demand; its own for q_sgrad's reason
+    vr::DevBuf<float> q_rad_tr;       // radiance query (kernels/vr_query_radiance.hip): the profile's Tr, n * K floats, when the
+                                      // caller does not ask for it; the query's only intermediate
+    vr::DevBuf<float> q_w3, q_out3;   // its host form's further arrays: the quadrature weights; the opacity and the counts
     // free-flight query (kernels/vr_query_flight.hip): its own scratch rows (the layouts of ff_scratch and of
     // ff_fb's rows), so a frame queued on another stream never shares them; counters + queue of rays over the rows
     vr::DevBuf<std::byte> q_ff_rows, q_ff_big;

@@ -77,6 +77,13 @@ hipError_t query_features_grad(const RenderArgs& A, const float* xyz, uint32_t n
                                const float* weights, const float* weight_mass, double* stage, double* fstage, float* grad,
                                float* grad_features, float* grad_xyz, hipStream_t s);
 
+// kernels/vr_query_radiance.hip
+// (t, q: n * K with stride K, or K with stride 0, q may be nullptr (ones); tr: n * K floats that query_transmittance_profile
+// wrote earlier on s; feat: C floats per scene Gaussian; out: n * C floats; opacity, n_pairs: n each or nullptr. n > 0)
+hipError_t query_radiance(const RenderArgs& A, const vr_ray* rays, const float* t, uint32_t t_stride, const float* q,
+                          uint32_t q_stride, uint32_t n, uint32_t K, const float* feat, uint32_t C, const float* tr, float* out,
+                          float* opacity, uint32_t* n_pairs, uint32_t* next, int refill, int cus, hipStream_t s);
+
 // kernels/vr_query_flight.hip (the sweep, the solvers and the albedo are the path kernels': kernels/vr_ff_bounce.h)
 // (ctl: query_flight_ctl_words(n) words; A.ff_*: the scratch rows, sized as the free-flight frames size theirs)
 size_t query_flight_ctl_words(uint32_t n);

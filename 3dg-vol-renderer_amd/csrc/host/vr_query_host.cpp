@@ -1,7 +1,7 @@
 // Mixture queries (vr_query_*, kernels/vr_query.hip, kernels/vr_query_profile.hip, kernels/vr_query_features.hip,
-// kernels/vr_query_flight.hip): batched transmittance and its gradients with respect to the Gaussians and to the rays,
-// transmittance profiles and their gradient, ray events, sigma and its gradient, per-Gaussian features at points and
-// their gradient, and free-flight distances.
+// kernels/vr_query_radiance.hip, kernels/vr_query_flight.hip): batched transmittance and its gradients with respect to
+// the Gaussians and to the rays, transmittance profiles and their gradient, ray events, sigma and its gradient,
+// per-Gaussian features at points and their gradient, the emission-absorption sum along rays, and free-flight distances.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -410,6 +410,63 @@ vr_status vr_query_features_grad(vr_ctx* c, const float* xyz, size_t n, const fl
                                                               dev<float>(c->q_w2, weight_mass), dev<float>(c->q_out, grad),
                                                               dev<float>(c->q_out2, grad_features),
                                                               dev<float>(c->q_out2, grad_xyz, at_xyz), c->stream);
+                     });
+}
+
+// ---- radiance: sum_k q T sum_g m f along each ray; the profile's walk for T, then one walk for the sum ----
+namespace {
+vr_status radiance_check(size_t t_stride, size_t q_stride, bool has_q, size_t n, size_t N, uint32_t K, uint32_t C) {
+    VR_TRY(profile_check("vr_query_radiance", t_stride, n, K));
+    VR_TRY(features_check("vr_query_radiance", n, N, C));
+    if (has_q && q_stride != 0 && q_stride != K) return fail(VR_ERR_INVALID, "vr_query_radiance: q_stride must be 0 (one shared row) or K");
+    return VR_OK;
+}
+}  // namespace
+
+vr_status vr_query_radiance_device(vr_ctx* c, const vr_ray* d_rays, const float* d_t, size_t t_stride, const float* d_q,
+                                   size_t q_stride, size_t n, uint32_t K, const float* d_features, uint32_t C, float* d_out,
+                                   float* d_opacity, float* d_tr, uint32_t* d_n_pairs, void* stream) {
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_radiance", n, A));
+    const size_t N = (size_t)std::max(A.num_prims, 0);
+    VR_TRY(radiance_check(t_stride, q_stride, d_q != nullptr, n, N, K, C));
+    if (n == 0) return VR_OK;
+    if (!d_rays || !d_t || !d_features || !d_out) return fail(VR_ERR_INVALID, "vr_query_radiance: NULL argument");
+    VR_TRY(rays_aligned("vr_query_radiance", d_rays));
+    // Tr without a place of the caller's: the query's own workspace, so a profile query on another stream never shares it
+    if (!d_tr) {
+        VR_TRY(c->q_rad_tr.grow(n * (size_t)K, "hipMalloc(radiance transmittances)"));
+        d_tr = c->q_rad_tr.get();
+    }
+    uint32_t* ctl = (uint32_t*)c->q_ctl.get();
+    HIP_TRY(query_transmittance_profile(A, d_rays, d_t, (uint32_t)t_stride, (uint32_t)n, K, d_tr, nullptr, ctl + 10, query_refill(c),
+                                        c->cus, (hipStream_t)stream),
+            "query_profile_kernel");
+    HIP_TRY(query_radiance(A, d_rays, d_t, (uint32_t)t_stride, d_q, (uint32_t)q_stride, (uint32_t)n, K, d_features, C, d_tr, d_out,
+                           d_opacity, d_n_pairs, ctl + 11, query_refill(c), c->cus, (hipStream_t)stream),
+            "query_radiance_kernel");
+    return VR_OK;
+}
+
+vr_status vr_query_radiance(vr_ctx* c, const vr_ray* rays, const float* t, size_t t_stride, const float* q, size_t q_stride, size_t n,
+                            uint32_t K, const float* features, uint32_t C, float* out, float* opacity, float* tr, uint32_t* n_pairs) {
+    RenderArgs A;
+    VR_TRY(query_begin(c, "vr_query_radiance", n, A));
+    const size_t N = (size_t)std::max(A.num_prims, 0);
+    VR_TRY(radiance_check(t_stride, q_stride, q != nullptr, n, N, K, C));
+    if (n == 0) return VR_OK;
+    if (!rays || !t || !features || !out) return fail(VR_ERR_INVALID, "vr_query_radiance: NULL argument");
+    const size_t nk = n * (size_t)K, nt = t_stride ? nk : (size_t)K, nq = q_stride ? nk : (size_t)K;
+    VR_TRY(room(c->q_feat, std::max<size_t>(N * C, 1), "query features"));  // (an empty scene has no rows; the pointer is not read)
+    // (the opacity and the counts share the third result's workspace)
+    return host_form(c, {{c->q_in, rays, n * kRayWords, "query rays"}, {c->q_w, t, nt, "profile samples"},
+                         {c->q_w3, q, nq, "quadrature weights"}, {c->q_feat, N ? features : nullptr, N * C, "query features"}},
+                     {{c->q_out, out, n * (size_t)C, "query results"}, {c->q_out2, tr, nk, "profile results"},
+                      {c->q_out3, opacity, n, "query results"}, {c->q_out3, n_pairs, n, "query results", n}},
+                     "query_radiance_kernel", [&] {
+                         return vr_query_radiance_device(c, dev<vr_ray>(c->q_in, rays), c->q_w.get(), t_stride, dev<float>(c->q_w3, q),
+                                                         q_stride, n, K, c->q_feat.get(), C, c->q_out.get(), dev<float>(c->q_out3, opacity),
+                                                         dev<float>(c->q_out2, tr), dev<uint32_t>(c->q_out3, n_pairs, n), c->stream);
                      });
 }
 

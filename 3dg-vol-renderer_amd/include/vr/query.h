@@ -221,6 +221,32 @@ public:
         return grad;
     }
 
+    // The emission-absorption sum along rays in one call (vr_query_radiance): `t` holds K distances shared by all rays, or
+    // rays.size() * K, as for transmittance_profile; `features` C floats per scene Gaussian, as for evaluate_features; `q`
+    // the quadrature weights in t's two layouts, or empty (all ones). The result holds L row-major, rays.size() * C floats,
+    //   L[i][c] = sum_k q[i][k] Tr[i][k] sum_g m_g(x_ik) features[g][c],   x_ik = origin_i + t[i][k] * direction_i in f32,
+    // over evaluate_sigma's active set at x_ik with Tr the profile's. *opacity (if given) receives the same sum without
+    // the features, *tr the profile's Tr (rays.size() * K floats), *n_pairs the active (sample, Gaussian) pairs per ray.
+    std::vector<float> radiance(const std::vector<Ray>& rays, const std::vector<float>& t, uint32_t K,
+                                const std::vector<float>& features, uint32_t C, const std::vector<float>& q = {},
+                                std::vector<float>* opacity = nullptr, std::vector<float>* tr = nullptr,
+                                std::vector<uint32_t>* n_pairs = nullptr) const {
+        const size_t stride = profile_stride("radiance", rays.size(), t.size(), K);
+        const size_t q_stride = q.empty() ? 0 : profile_stride("radiance", rays.size(), q.size(), K);
+        feature_rows("radiance", features.size(), C);
+        vr_ctx* ctx = ready();
+        const std::vector<vr_ray> r = pack(rays, nullptr, std::numeric_limits<float>::infinity());
+        std::vector<float> out(r.size() * C), none(1, 0.0f);  // (none: a scene without Gaussians has no rows, never a NULL pointer)
+        if (opacity) opacity->assign(r.size(), 0.0f);
+        if (tr) tr->assign(r.size() * K, 0.0f);
+        if (n_pairs) n_pairs->assign(r.size(), 0u);
+        vr_cpp::check(vr_query_radiance(ctx, r.data(), t.data(), stride, q.empty() ? nullptr : q.data(), q_stride, r.size(), K,
+                                        features.empty() ? none.data() : features.data(), C, out.data(),
+                                        opacity ? opacity->data() : nullptr, tr ? tr->data() : nullptr,
+                                        n_pairs ? n_pairs->data() : nullptr));
+        return out;
+    }
+
     // integrator.h:422-498 MultiScatterGaussians::get_free_flight_distance(ray, events, target_tau) per ray, the
     // events being the ray's own: the collision distance, or -1 where the ray leaves the mixture before the
     // target is reached. *albedo (if given) receives evaluate_albedo (gmm.h:128-143) over the critical segment's

@@ -758,6 +758,47 @@ class Device:
         got = tuple(a for a in (grad, gf, gx) if a is not None)
         return got if len(got) > 1 else got[0]
 
+    def radiance(self, scene, origins, directions, t, features, weights=None, unit=False, return_opacity=False, return_tr=False,
+                 return_pairs=False):
+        """The emission-absorption sum along n rays in one call (vr_query_radiance): origins, directions (n, 3) float32; t
+        float32 of shape (K,) (one row shared by all rays) or (n, K), the samples of query_transmittance_profile; features
+        (N, C) float32, row g for scene Gaussian g, as for evaluate_features; weights the quadrature weights in t's two
+        shapes, or None (all ones). All arrays are of one kind, numpy or torch. Returns L (n, C) with
+            L[i, c] = sum_k weights[i, k] Tr[i, k] sum_g m_g(x_ik) features[g, c],   x_ik = origins[i] + t[i, k] * d_i
+        (the f32 product and sum numpy computes; d_i the normalised direction, or directions[i] as it stands with
+        unit=True), over query_sigma's active set at x_ik, with Tr the profile's; sums in double, rounded once. Further
+        results follow in this order when asked for: opacity (n,), the same sum without the features; Tr (n, K), the bits of
+        query_transmittance_profile; pairs (n,) int32, the active (sample, Gaussian) pairs of the ray. A sample that is
+        negative, NaN or infinite contributes nothing. A channel of ones has the bits of opacity; a channel's bits do not
+        depend on C or on its place. Unlike evaluate_features, a point whose summed m is <= 0 is not zeroed (this
+        differs with non-positive densities only)."""
+        kind = _ArrayKind(origins, _query_ray_args(origins, directions, 0.0))
+        n = origins.shape[0]
+        K, stride = _query_profile_args(t, "t", n, kind.torch, shared_ok=True)
+        C = _query_feature_args(features, "features", None, kind.torch, "Gaussians")
+        q_stride = 0
+        if weights is not None:
+            Kq, q_stride = _query_profile_args(weights, "weights", n, kind.torch, shared_ok=True)
+            if Kq != K:
+                raise ValueError(f"weights has {Kq} columns for {K} samples")
+        _query_feature_sizes(n, features.shape[0], C)
+        N = scene.get_num_primitives()
+        if features.shape[0] != N:
+            raise ValueError(f"features has {features.shape[0]} rows for {N} Gaussians")
+        self.upload(scene)
+        rays = self._query_rays(kind, origins, directions, float("inf"), unit, also=(t, features, weights))
+        out = kind.new((n, C))
+        opacity = kind.new(n) if return_opacity else None
+        tr = kind.new((n, K)) if return_tr else None
+        pairs = kind.new(n, np.int32) if return_pairs else None  # (the library's uint32 counts)
+        if n > 0:
+            feats = kind.contiguous(features) if N > 0 else kind.new((1, C), zero=True)  # (no rows: never read, never NULL)
+            kind.call("vr_query_radiance", self._h, kind.ptr(rays), kind.ptr(kind.contiguous(t)), stride,
+                      kind.ptr(kind.contiguous(weights)), q_stride, n, K, kind.ptr(feats), C, kind.ptr(out), kind.ptr(opacity),
+                      kind.ptr(tr), kind.ptr(pairs))
+        got = (out,) + tuple(a for a in (opacity, tr, pairs) if a is not None)
+        return got if len(got) > 1 else out
+
     def query_events(self, scene, origins, directions):
         """GaussianMixtureModel::intersect_events (gmm.h:457-515) for n rays. Returns (offsets, t, gaussian,
         entering): ray i's events are the slice offsets[i]:offsets[i + 1] (offsets: (n + 1,) int64) of t

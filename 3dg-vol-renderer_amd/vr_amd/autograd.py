@@ -51,6 +51,23 @@ weight_mass), asking only for the outputs some input needs; exact over the forwa
 Gaussian), the 3-sigma cut-off not differentiated, not differentiable a second time. One profile call plus one feature
 call is a differentiable radiance-field renderer on the uploaded tree.
 
+The emission-absorption sum along rays itself, in one call (Device.radiance):
+
+    L, opacity = radiance(mean, cov6, density, albedo, feats, origins, directions, t, q)   # (n, C), (n,)
+    loss = (L - image).square().mean()                  # L[i] = sum_k q[i, k] T[i, k] sum_g m_g(x_ik) feats[g]
+    loss.backward()                                     # mean.grad, cov6.grad, density.grad, feats.grad
+
+t is (K,) or (n, K), q the quadrature weights in the same shapes or None (ones). The forward is the fused query: it
+never holds the n K points or their n K C features, and keeps the (n, K) transmittances for the backward. The
+directions are normalised once in torch (v / |v|) and handed over as unit vectors, so that both passes use the same
+sample points. The backward composes the gradient queries that exist: one Device.features_gradient at the n K points
+with weights q T grad_L and mass weights q T grad_opacity, one Device.evaluate_features for s = grad_L . F + grad_opacity
+mass, one Device.query_transmittance_profile_grad with weights -q T s, and the two (N, 10) results added; it asks only
+for what some input needs. So the backward costs what the composition costs in memory and walks, and it carries the
+feature query's rule that a point whose summed m is <= 0 is zeroed: it is the forward's gradient for positive densities
+only. albedo, origins, directions, t and q get None; a fused backward and gradients with respect to the rays are not
+part of this.
+
 The extinction field itself, at the caller's points (Device.query_sigma / Device.query_sigma_grad):
 
     sig = sigma(mean, cov6, density, albedo, points)                             # (n, 2) = (sigma_a, sigma_s)
@@ -278,3 +295,78 @@ def features_resident(mean, cov6, density, albedo, feats, points, device=0):
     device (ValueError otherwise), and forward uploads the scene with Device.upload_gaussians instead of copying it to the
     host. Same arguments, same gradients."""
     return _Features.apply(mean, cov6, density, albedo, feats, points, device, True)
+
+
+def _unit_directions(d):
+    """v / |v| per row in f32, |v|^2 summed as the library sums it."""
+    s = d[:, 0] * d[:, 0] + (d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2])
+    return (d / torch.sqrt(s)[:, None]).contiguous()
+
+
+class _Radiance(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mean, cov6, density, albedo, feats, origins, directions, t, q, device, resident):
+        if resident and feats.device != origins.device:
+            raise ValueError(f"feats is on {feats.device}, the rays on {origins.device}: a resident scene's "
+                             "features live on the rays' device")
+        dev, scene = _scene_of(mean, cov6, density, albedo, origins, "the rays", device, resident)
+        o, d = origins.detach().contiguous(), _unit_directions(directions.detach())
+        ts = t.detach().contiguous()
+        qs = None if q is None else q.detach().contiguous()
+        f = feats.detach().to(device=o.device, dtype=torch.float32).contiguous()
+        L, opacity, tr = dev.radiance(scene, o, d, ts, f, qs, unit=True, return_opacity=True, return_tr=True)
+        ctx.dev, ctx.scene, ctx.saved = dev, scene, (o, d, ts, qs, f, tr)
+        ctx.like, ctx.feats_like = (mean, cov6, density), feats
+        ctx.mark_non_differentiable(tr)
+        return L, opacity, tr
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_L, grad_opacity, _grad_tr):
+        need_g, need_f = any(ctx.needs_input_grad[:3]), ctx.needs_input_grad[4]
+        out, gf = (None,) * 3, None
+        if need_g or need_f:
+            o, d, ts, qs, f, tr = ctx.saved
+            n, K = tr.shape
+            C = f.shape[1]
+            # the weights are formed in double and rounded once, so they carry one f32 rounding each
+            gL, gA = grad_L.to(torch.float64), grad_opacity.to(torch.float64)
+            tk = ts.expand(n, K)
+            x = (o[:, None, :] + tk[:, :, None] * d[:, None, :]).reshape(-1, 3).contiguous()
+            valid = torch.isfinite(tk) & (tk >= 0) & torch.isfinite(tr)  # (an invalid ray's T is NaN: it contributes nothing)
+            qt = tr.to(torch.float64) if qs is None else qs.expand(n, K).to(torch.float64) * tr.to(torch.float64)  # (n, K): q T
+            qt = torch.where(valid, qt, torch.zeros_like(qt))
+            x = torch.where(valid.reshape(-1, 1), x, torch.full_like(x, float("nan")))  # (a non-finite point lies in no box)
+            w = (qt[:, :, None] * gL[:, None, :]).reshape(-1, C).to(torch.float32).contiguous()
+            u = (qt * gA[:, None]).reshape(-1).to(torch.float32).contiguous()
+            got = ctx.dev.features_gradient(ctx.scene, x, f, w, u, gaussians=need_g, features_grad=need_f)
+            got = list(got) if isinstance(got, tuple) else [got]
+            if need_g:
+                g = got.pop(0)
+                F, mass = ctx.dev.evaluate_features(ctx.scene, x, f, return_mass=True)
+                s = (F.reshape(n, K, C).to(torch.float64) * gL[:, None, :]).sum(2) + mass.reshape(n, K).to(torch.float64) * gA[:, None]
+                wp = torch.where(valid, -qt * s, torch.zeros_like(s)).to(torch.float32).contiguous()
+                gp = ctx.dev.query_transmittance_profile_grad(ctx.scene, o, d, ts, wp)
+                out = _split_grad(g.to(torch.float64) + gp.to(torch.float64), ctx.like, ctx.needs_input_grad[:3])
+            if need_f:
+                gf = got.pop(0).to(device=ctx.feats_like.device, dtype=ctx.feats_like.dtype)
+        return out + (None, gf) + (None,) * 6
+
+
+def radiance(mean, cov6, density, albedo, feats, origins, directions, t, q=None, device=0):
+    """(L (n, C), opacity (n,)) float32 along rays (origins, directions: (n, 3) float32 tensors on cuda:`device`) at the
+    distances t ((K,) shared by all rays, or (n, K)) with the quadrature weights q (t's shapes, or None: ones), for the
+    mixture mean (N, 3), cov6 (N, 6) [xx xy xz yy yz zz], density (N,), albedo (N,) and the caller's feats (N, C) (tensors on
+    any device): L[i] = sum_k q[i, k] T[i, k] sum_g m_g(x_ik) feats[g], opacity the same sum without feats; the values of
+    Device.radiance for the directions normalised in torch and unit=True. Differentiable with respect to mean, cov6,
+    density and feats (positive densities; see the module's head); albedo, origins, directions, t and q get None."""
+    L, opacity, _ = _Radiance.apply(mean, cov6, density, albedo, feats, origins, directions, t, q, device, False)
+    return L, opacity
+
+
+def radiance_resident(mean, cov6, density, albedo, feats, origins, directions, t, q=None, device=0):
+    """radiance for parameters that never leave the GPU: mean, cov6, density, albedo and feats must be on the rays' device
+    (ValueError otherwise), and forward uploads the scene with Device.upload_gaussians instead of copying it to the host.
+    Same arguments, same gradients."""
+    L, opacity, _ = _Radiance.apply(mean, cov6, density, albedo, feats, origins, directions, t, q, device, True)
+    return L, opacity

@@ -24,7 +24,7 @@ extern "C" {
 #endif
 
 #define VR_ABI_VERSION 11
-/* (still 11 with vr_query_features / vr_query_features_grad: entry points were added, none changed) */
+/* (still 11 with vr_query_features / vr_query_features_grad and vr_query_radiance: entry points were added, none changed) */
 
 typedef enum vr_status {
     VR_OK = 0,
@@ -758,6 +758,44 @@ vr_status vr_query_features_grad(vr_ctx* ctx, const float* xyz, size_t n, const 
 vr_status vr_query_features_grad_device(vr_ctx* ctx, const float* d_xyz, size_t n, const float* d_features, uint32_t C,
                                         const float* d_weights, const float* d_weight_mass, float* d_grad,
                                         float* d_grad_features, float* d_grad_xyz, void* stream);
+
+/* The emission-absorption sum along n rays, in one call: the caller's per-Gaussian rows (features[N * C], as for
+ * vr_query_features) weighted by the mixture's m at the caller's K samples per ray, by the transmittance up to each sample
+ * and by the caller's quadrature weights. t is the sample array of vr_query_transmittance_profile (n * K floats with
+ * t_stride = K, or one shared row with t_stride = 0); q holds the quadrature weights in the same two layouts (q_stride 0
+ * or K; NULL: all ones). The quadrature rule (midpoint, trapezoid, stratified ...) lives in t and q, not in the library.
+ * Sample k of ray i is valid iff t_ik is finite and >= 0. Its point is x_ik = o_i + t_ik d_i, per component one f32
+ * multiply and then one f32 add, never fused (the point numpy or torch compute from the f32 arrays); d is the direction
+ * the walk uses (normalised once if unit == 0). With A(x) the active set of vr_query_sigma (the same f32 decision), m_g its
+ * f32 mu_t and T_ik the f32 tr of vr_query_transmittance_profile for that ray and sample, all bit for bit:
+ *   out[C i + c]  = f32( sum_{k valid} sum_{g in A(x_ik)} (double)q_ik (double)T_ik (double)m_g(x_ik) (double)f_gc )
+ *   opacity[i]    = f32( the same sum without the f factor )            (may be NULL)
+ *   tr[K i + k]   = the profile's tr for (ray i, t_ik), bit for bit      (may be NULL)
+ *   n_pairs[i]    = sum_{k valid} |A(x_ik)|                              (may be NULL)
+ * The sums are double (a Gaussian's samples are added first, then its term W f_gc, W = sum_k q T m, to each channel) and
+ * each result is rounded to f32 once. tr is written for every sample, valid or not, by the profile's own rules (a sample
+ * that is not > 0 has tr = 1). Terms exist only for active pairs: a sample in no ellipsoid contributes exactly nothing
+ * whatever q is, and a row without pairs is +0. An invalid ray (the queries' rule) gets NaN in out, opacity and its tr
+ * row, and 0 pairs. With q_k = the spacing of the samples, opacity is the Riemann sum of int T sigma_t dt = 1 - T(end).
+ * Hence: a channel whose features are all 1.0f has the bits of opacity; a channel's bits depend neither on C nor on its
+ * place among the C; n_pairs[i] is the sum of vr_query_features' n_active over ray i's valid sample points; tr is the
+ * profile query's output.
+ * One deliberate difference from composing vr_query_transmittance_profile and vr_query_features: the feature query zeroes
+ * a point whose summed m is <= 0, which happens with non-positive densities only; this query does not apply that rule,
+ * every active pair counts. With positive densities the two definitions coincide.
+ * 1 <= K <= VR_PROFILE_MAX_SAMPLES, 1 <= C <= VR_FEATURES_MAX_CHANNELS, and n * K, n * C and num_primitives * C each
+ * below 2^31; a t_stride or q_stride other than 0 and K; rays, t, features or out NULL with n > 0; a device ray array
+ * that is not 16-byte aligned: VR_ERR_INVALID before anything is launched. The common errors above apply (a sphere
+ * scene: VR_ERR_UNSUPPORTED; no scene: VR_ERR_NOSCENE). n == 0 is VR_OK and touches nothing. A scene without Gaussians
+ * gives zeros and tr = 1.
+ * Two passes on `stream`: the profile's walk writes tr (into a workspace of the query's own, n * K floats, when tr is
+ * NULL: the only intermediate), then one walk per (ray, 8 channels) forms the sums. */
+vr_status vr_query_radiance(vr_ctx* ctx, const vr_ray* rays, const float* t, size_t t_stride, const float* q,
+                            size_t q_stride, size_t n, uint32_t K, const float* features, uint32_t C, float* out,
+                            float* opacity, float* tr, uint32_t* n_pairs);
+vr_status vr_query_radiance_device(vr_ctx* ctx, const vr_ray* d_rays, const float* d_t, size_t t_stride, const float* d_q,
+                                   size_t q_stride, size_t n, uint32_t K, const float* d_features, uint32_t C,
+                                   float* d_out, float* d_opacity, float* d_tr, uint32_t* d_n_pairs, void* stream);
 
 /* GaussianMixtureModel::intersect_events (gmm.h:457-515; tmax is not read): per ray the events of every
  * Gaussian it hits, an entry at t_enter (clamped to 0 for an origin inside) and an exit at t_exit, sorted by

@@ -6,7 +6,7 @@ rays packed on the device), every query is warmed up, and the figure is the medi
 events on torch's current stream. Prints one JSON line and, with --out, writes it to a file.
 
     python tools/query_bench.py [--gaussians 1000000] [--rays 4194304] [--points 4194304] [--repeats 5] [--out F]
-                                [--flight-scene FILE] [--only all|mixture|flight|grad|raygrad|upload|sigmagrad|profile|features]
+                                [--flight-scene FILE] [--only all|mixture|flight|grad|raygrad|upload|sigmagrad|profile|features|radiance]
 
 --only grad times the optical-depth gradient query (Device.query_transmittance_grad, unit weights, moving and frozen
 bounds) beside the tau query on the same rays, on --flight-scene and on the make_random scene (--gaussians 0 skips it).
@@ -24,6 +24,13 @@ through the cloud, a row per ray) beside K calls of the tau query on the same ra
 (Device.query_transmittance_profile_grad, unit weights) beside the gradient query on the n K expanded rays, on
 --flight-scene and on the make_random scene (--gaussians 0 skips it); --profile-forward-only leaves the gradients out.
 Each comparison reports the existing query's own spread over the repeats: a difference counts from three times that.
+--only radiance times the radiance query (Device.radiance with the opacity: one call) against the composition it replaces
+(Device.query_transmittance_profile, Device.evaluate_features with the mass at the n K points, and the torch sum), on a
+make_random scene of --gaussians Gaussians with --rays rays, K = 64 samples per ray through the cloud (a row per ray, midpoint
+weights) and C = 3 and 48 channels. One process, one warm-up of each side, then the two sides alternate --repeats times; the
+medians, each side's spread (max - min), the peak device memory of one call of each side over what is resident before it,
+and the largest |fused - composition| over S = sum_k |q| T F_abs beside the tests' bound 2^-22 (the composition summed
+again in double for this; entries whose S is below 2^-100, where the f32 result underflows, are counted apart).
 --only upload times getting a scene whose parameters live in torch tensors on the GPU onto the device, on --flight-scene
 and on make_random scenes of 100 000 and --gaussians Gaussians: (a) a copy to the host, Scene.from_gaussians and
 Device.upload with the host builder, (b) the same with device_bvh = 1, (c) Device.upload_gaussians. A host clock
@@ -72,7 +79,7 @@ def main():
     ap.add_argument("--seed", type=int, default=2025)
     ap.add_argument("--out", default=None)
     ap.add_argument("--flight-scene", default=os.path.join(ROOT, "tests", "golden", "scenes", "1000_random.txt"))
-    ap.add_argument("--only", choices=("all", "mixture", "flight", "grad", "raygrad", "upload", "sigmagrad", "profile", "features"),
+    ap.add_argument("--only", choices=("all", "mixture", "flight", "grad", "raygrad", "upload", "sigmagrad", "profile", "features", "radiance"),
                     default="all")
     ap.add_argument("--profile-k", default="8,64", help="samples per ray of --only profile, comma-separated")
     ap.add_argument("--profile-forward-only", action="store_true")
@@ -110,6 +117,9 @@ def main():
     if args.only == "features":
         res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
         res.update(features(args, dev, timed))
+    if args.only == "radiance":
+        res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
+        res.update(radiance(args, dev, o, d))
     if args.only == "profile":
         res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
         res.update(profile(args, dev, o, d, timed))
@@ -189,6 +199,89 @@ def profile(args, dev, o, d, timed):
     return {"profile": out, "library": os.path.basename(vr._lib.LIB_PATH),
             "timing": "median of HIP-event intervals on torch's current stream after the warm-up, inputs on the device; "
                       "spread = max - min of the existing query's intervals, a difference counts from 3 spreads"}
+
+
+def radiance(args, dev, o, d):
+    """The fused radiance query against profile + features at n K points + the torch sum, alternating in one process."""
+    import torch
+    scene = vr.Scene(vr.Scene.GAUSSIANS)
+    scene.add_random_gaussians(args.gaussians, seed=args.seed, variant=0)
+    info = scene.info()
+    lo, hi = np.array(list(info.bounds_min), np.float64), np.array(list(info.bounds_max), np.float64)
+    dist, rad = float(np.linalg.norm(0.5 * (lo + hi) - CAM_POS)), 0.5 * float(np.linalg.norm(hi - lo))
+    dev.upload(scene)
+    n, N, K = o.shape[0], scene.get_num_primitives(), 64
+    edges = np.linspace(max(dist - rad, 0.0), dist + rad, K + 1)
+    t = torch.tensor(np.tile((0.5 * (edges[1:] + edges[:-1])).astype(np.float32), (n, 1))).cuda()
+    q = torch.tensor(np.tile(np.diff(edges).astype(np.float32), (n, 1))).cuda()
+    # the library's normalisation, for the composition's points (f32 products and sums in its order)
+    dn = d / torch.sqrt(d[:, 0] * d[:, 0] + (d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]))[:, None]
+
+    def interval(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        got = fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), got
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        return (torch.cuda.max_memory_allocated() - base) / 2.0 ** 20
+
+    out = []
+    for C in (3, 48):
+        f = torch.tensor(np.random.default_rng(7).uniform(-1, 1, (N, C)).astype(np.float32)).cuda()
+
+        def fused():
+            return dev.radiance(scene, o, d, t, f, q, return_opacity=True)
+
+        def composed(feats=f):
+            tr = dev.query_transmittance_profile(scene, o, d, t)
+            x = (o[:, None, :] + t[:, :, None] * dn[:, None, :]).reshape(-1, 3)
+            F, mass = dev.evaluate_features(scene, x, feats, return_mass=True)
+            w = q * tr
+            return (w[:, :, None] * F.reshape(n, K, -1)).sum(1), (w * mass.reshape(n, K)).sum(1), w
+
+        for _ in range(max(1, args.warmup)):
+            a, b = fused(), composed()
+        # the comparison, apart from the timed path: the composition's sums again in double, S = sum_k |q| T F_abs
+        def in_double(feats):
+            tr = dev.query_transmittance_profile(scene, o, d, t)
+            x = (o[:, None, :] + t[:, :, None] * dn[:, None, :]).reshape(-1, 3)
+            F = dev.evaluate_features(scene, x, feats).reshape(n, K, -1).double()
+            return ((q.double() * tr.double())[:, :, None] * F).sum(1), ((q.double() * tr.double()).abs()[:, :, None] * F).sum(1)
+        ref, S = in_double(f)[0], in_double(f.abs())[1]
+        err = (a[0].double() - ref).abs()
+        # (an entry whose S lies below 2^-100 is counted apart: there the f32 result itself underflows, and its last
+        # rounding is no longer 2^-24 of it)
+        normal = S >= 2.0 ** -100
+        rel = torch.where(normal, err / S, torch.zeros_like(S))
+        ratio, over = float(rel.max()), int((normal & (err > 2.0 ** -22 * S)).sum())
+        tiny = int(((S > 0) & ~normal).sum())
+        del S, err, b, ref, rel, normal
+        fm, cm = [], []
+        for _ in range(args.repeats):
+            fm.append(interval(fused)[0])
+            cm.append(interval(composed)[0])
+        f_ms, c_ms = statistics.median(fm), statistics.median(cm)
+        f_sp, c_sp = max(fm) - min(fm), max(cm) - min(cm)
+        out.append({"scene": f"make_random_{args.gaussians}", "gaussians": N, "rays": n, "K": K, "C": C, "fused_ms": f_ms,
+                    "composition_ms": c_ms, "composition_over_fused": c_ms / f_ms, "fused_spread_ms": f_sp,
+                    "composition_spread_ms": c_sp, "fused_faster_by_more_than_the_spreads": bool(c_ms - f_ms > max(f_sp, c_sp)),
+                    "fused_peak_mib": peak(fused), "composition_peak_mib": peak(composed),
+                    "max_difference_over_S": ratio, "bound": 2.0 ** -22,
+                    "entries_over_the_bound": over, "entries": n * C, "entries_with_S_below_2^-100": tiny, "mean_opacity": float(a[1].mean()),
+                    "all_ms": {"fused": fm, "composition": cm}})
+    return {"radiance": out, "library": os.path.basename(vr._lib.LIB_PATH),
+            "timing": "HIP-event intervals on torch's current stream, the two sides alternating after a warm-up of each, inputs on "
+                      "the device; spread = max - min of a side's intervals; peak = torch's peak allocation during one call over "
+                      "what was allocated before it (the library's own workspaces, n K floats of Tr for the fused side, are not "
+                      "torch's and are not counted on either side)"}
 
 
 def sigmagrad(args, dev, timed):

@@ -39,6 +39,9 @@
 // per ray, t[i][k] = tmax_i * (k + 1) / K in f32: one line `tp <ray index> <k> <t, Tr, tau as hex words>` per sample, then
 // MixtureQuery::transmittance_profile_gradient of the same samples, all weights 1: one line `pg <scene index> <10 hex
 // words>` per Gaussian.
+// --query-radiance RAYS.bin K FEATURES.bin (the two files above) prints MixtureQuery::radiance of the file's rays at
+// --query-profile's K distances per ray with the quadrature weights q[i][k] = tmax_i / K in f32: one line `rq <ray index>
+// <n_pairs> <opacity and C channels as hex words>` per ray, then one line `rt <ray index> <K hex words of Tr>` per ray.
 // --upload-device (Gaussian scenes, one GPU): copies the loaded scene's rows to device memory and uploads them with
 // HipIntegrator::upload_device (vr_upload_gaussians_device: records, boxes and tree computed on the device), then
 // renders the scene the context holds.
@@ -158,12 +161,8 @@ static int run_query_sigma_grad(const Scene& scene, const std::string& path) {
     return 0;
 }
 
-// --query-features: the caller's rows at the file's points, and the gradient of the sum of the result's entries.
-static int run_query_features(const Scene& scene, const std::string& path, const std::string& feat_path) {
-    std::vector<Ray> rays;
-    std::vector<float> tmax;
-    std::vector<Eigen::Vector3f> pos;
-    read_query_file(path, rays, tmax, pos);
+// FEATURES.bin: the rows, and C.
+static std::vector<float> read_feature_file(const std::string& feat_path, uint32_t& C) {
     std::FILE* f = std::fopen(feat_path.c_str(), "rb");
     if (!f) throw std::runtime_error("cannot open " + feat_path);
     uint32_t hdr[2] = {0, 0};
@@ -172,7 +171,18 @@ static int run_query_features(const Scene& scene, const std::string& path, const
     ok = ok && std::fread(feat.data(), 4, feat.size(), f) == feat.size();
     std::fclose(f);
     if (!ok) throw std::runtime_error("short or malformed feature file " + feat_path);
-    const uint32_t C = hdr[1];
+    C = hdr[1];
+    return feat;
+}
+
+// --query-features: the caller's rows at the file's points, and the gradient of the sum of the result's entries.
+static int run_query_features(const Scene& scene, const std::string& path, const std::string& feat_path) {
+    std::vector<Ray> rays;
+    std::vector<float> tmax;
+    std::vector<Eigen::Vector3f> pos;
+    read_query_file(path, rays, tmax, pos);
+    uint32_t C = 0;
+    const std::vector<float> feat = read_feature_file(feat_path, C);
     MixtureQuery q(scene);
     std::vector<float> mass, gf, gx;
     std::vector<uint32_t> na;
@@ -216,6 +226,36 @@ static int run_query_profile(const Scene& scene, const std::string& path, int K)
     for (size_t i = 0; i < g.size() / 10; ++i) {
         std::printf("pg %zu", i);
         for (int k = 0; k < 10; ++k) std::printf(" %08x", fbits(g[10 * i + k]));
+        std::printf("\n");
+    }
+    return 0;
+}
+
+// --query-radiance: the emission-absorption sum of the file's rays over --query-profile's samples, in one call.
+static int run_query_radiance(const Scene& scene, const std::string& path, int K, const std::string& feat_path) {
+    if (K <= 0) throw std::runtime_error("--query-radiance: K must be positive");
+    std::vector<Ray> rays;
+    std::vector<float> tmax;
+    std::vector<Eigen::Vector3f> pos;
+    read_query_file(path, rays, tmax, pos);
+    uint32_t C = 0;
+    const std::vector<float> feat = read_feature_file(feat_path, C);
+    std::vector<float> t(rays.size() * (size_t)K), q(t.size()), opacity, tr;
+    for (size_t i = 0; i < rays.size(); ++i)
+        for (int k = 0; k < K; ++k) {
+            t[i * (size_t)K + k] = tmax[i] * (float)(k + 1) / (float)K;
+            q[i * (size_t)K + k] = tmax[i] / (float)K;
+        }
+    std::vector<uint32_t> np;
+    const std::vector<float> L = MixtureQuery(scene).radiance(rays, t, (uint32_t)K, feat, C, q, &opacity, &tr, &np);
+    for (size_t i = 0; i < rays.size(); ++i) {
+        std::printf("rq %zu %u %08x", i, np[i], fbits(opacity[i]));
+        for (uint32_t k = 0; k < C; ++k) std::printf(" %08x", fbits(L[C * i + k]));
+        std::printf("\n");
+    }
+    for (size_t i = 0; i < rays.size(); ++i) {
+        std::printf("rt %zu", i);
+        for (int k = 0; k < K; ++k) std::printf(" %08x", fbits(tr[i * (size_t)K + k]));
         std::printf("\n");
     }
     return 0;
@@ -276,7 +316,8 @@ int main(int argc, char** argv) try {
     uint64_t seed = 0;
     float lr = 1e-2f;
     std::string ref_path, sfd_out, gif_path, query_path, query_grad_path, query_ray_grad_path, query_sigma_grad_path, query_profile_path,
-        query_features_path, features_path;
+        query_features_path, features_path, query_radiance_path;
+    int radiance_k = 0;
     int profile_k = 0;
     int frames = 120;
     float fps = 30.0f;
@@ -308,6 +349,7 @@ int main(int argc, char** argv) try {
         else if (a == "--query-ray-grad") query_ray_grad_path = next();
         else if (a == "--query-sigma-grad") query_sigma_grad_path = next();
         else if (a == "--query-features") { query_features_path = next(); features_path = next(); }
+        else if (a == "--query-radiance") { query_radiance_path = next(); radiance_k = std::atoi(next()); features_path = next(); }
         else if (a == "--query-profile") { query_profile_path = next(); profile_k = std::atoi(next()); }
         else if (a == "--gif") gif_path = next();
         else if (a == "--frames") frames = std::atoi(next());
@@ -369,6 +411,7 @@ int main(int argc, char** argv) try {
     if (!query_ray_grad_path.empty()) return run_query_ray_grad(scene, query_ray_grad_path);
     if (!query_sigma_grad_path.empty()) return run_query_sigma_grad(scene, query_sigma_grad_path);
     if (!query_features_path.empty()) return run_query_features(scene, query_features_path, features_path);
+    if (!query_radiance_path.empty()) return run_query_radiance(scene, query_radiance_path, radiance_k, features_path);
     if (!query_profile_path.empty()) return run_query_profile(scene, query_profile_path, profile_k);
 
     if (!gif_path.empty()) {  // main.cpp:81-114
