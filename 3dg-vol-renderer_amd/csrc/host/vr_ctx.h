@@ -135,7 +135,8 @@ struct vr_ctx {
     vr::DevBuf<std::byte> q_tmp;                // scan + sort scratch
     vr::DevBuf<std::byte> q_ctl;      // words [0..3], [6] ray counters of the five persistent walks, [4..5] the 64-bit event total,
                                       // [8], [9] the counters of the profile query's two walks, [10], [11] those of the
-                                      // radiance query's (its profile pass and its own)
+                                      // radiance query's (its profile pass and its own), [12] .. [14] those of the
+                                      // radiance gradient query's three passes
     vr::DevBuf<double> q_grad;        // gradient query: 10 doubles of staging per Gaussian (tree order), zeroed per call
     vr::DevBuf<double> q_sgrad;       // sigma gradient query: 11 doubles of staging per Gaussian, its own (the two
                                       // gradient queries may be queued on different streams)
@@ -147,6 +148,13 @@ struct vr_ctx {
     vr::DevBuf<float> q_rad_tr;       // radiance query (kernels/vr_query_radiance.hip): the profile's Tr, n * K floats, when the
                                       // caller does not ask for it; the query's only intermediate
     vr::DevBuf<float> q_w3, q_out3;   // its host form's further arrays: the quadrature weights; the opacity and the counts
+    // radiance gradient query (kernels/vr_query_radiance_grad.hip), its own for q_sgrad's reason, grown on demand:
+    vr::DevBuf<float> q_radg_tr;      //   the profile's Tr when the caller has none, n * K floats
+    vr::DevBuf<float> q_radg_tau;     //   grad_tau when grad is asked for without it, n * K floats
+    vr::DevBuf<double> q_radg_s;      //   s = sum_g m phi per sample, n * K doubles, each row zeroed by its own ray
+    vr::DevBuf<double> q_radg_stage;  //   10 doubles of staging per Gaussian (both parts of grad), zeroed per call
+    vr::DevBuf<double> q_radg_fstage; //   C doubles of feature staging per Gaussian, zeroed per call
+    vr::DevBuf<float> q_w4, q_w5;     //   its host form's further inputs: the opacity weights, the forward's Tr
     // free-flight query (kernels/vr_query_flight.hip): its own scratch rows (the layouts of ff_scratch and of
     // ff_fb's rows), so a frame queued on another stream never shares them; counters + queue of rays over the rows
     vr::DevBuf<std::byte> q_ff_rows, q_ff_big;

@@ -65,6 +65,10 @@ hipError_t query_transmittance_profile(const RenderArgs& A, const vr_ray* rays, 
 hipError_t query_transmittance_profile_grad(const RenderArgs& A, const vr_ray* rays, const float* t, uint32_t t_stride,
                                             const float* weight, uint32_t n, uint32_t K, bool moving, double* acc, float* grad,
                                             uint32_t* next, int refill, int cus, hipStream_t s);
+// (the same walk adding into staging rows the caller zeroed and finishes: the radiance gradient's second pass. n > 0)
+hipError_t query_transmittance_profile_grad_add(const RenderArgs& A, const vr_ray* rays, const float* t, uint32_t t_stride,
+                                                const float* weight, uint32_t n, uint32_t K, bool moving, double* acc,
+                                                uint32_t* next, int refill, int cus, hipStream_t s);
 
 // kernels/vr_query_features.hip
 // (feat: C floats per scene Gaussian; out: n * C floats; mass, n_active: n each or nullptr. n > 0, 1 <= C, n * C < 2^31)
@@ -76,6 +80,8 @@ hipError_t query_features(const RenderArgs& A, const float* xyz, uint32_t n, con
 hipError_t query_features_grad(const RenderArgs& A, const float* xyz, uint32_t n, const float* feat, uint32_t C,
                                const float* weights, const float* weight_mass, double* stage, double* fstage, float* grad,
                                float* grad_features, float* grad_xyz, hipStream_t s);
+// (the finish of a feature staging, C doubles per Gaussian in tree order -> grad_features; the radiance gradient's too)
+hipError_t query_features_finish(const RenderArgs& A, const double* fstage, uint32_t C, float* grad_features, hipStream_t s);
 
 // kernels/vr_query_radiance.hip
 // (t, q: n * K with stride K, or K with stride 0, q may be nullptr (ones); tr: n * K floats that query_transmittance_profile
@@ -83,6 +89,17 @@ hipError_t query_features_grad(const RenderArgs& A, const float* xyz, uint32_t n
 hipError_t query_radiance(const RenderArgs& A, const vr_ray* rays, const float* t, uint32_t t_stride, const float* q,
                           uint32_t q_stride, uint32_t n, uint32_t K, const float* feat, uint32_t C, const float* tr, float* out,
                           float* opacity, uint32_t* n_pairs, uint32_t* next, int refill, int cus, hipStream_t s);
+
+// kernels/vr_query_radiance_grad.hip
+// (the inputs of query_radiance; weights: n * C or nullptr (ones); weight_opacity: n or nullptr (zeros); tr: n * K, the
+// forward's. Workspaces: s_rows n * K doubles (not needed for grad_features alone), stage 10 and fstage C doubles per
+// Gaussian (with grad / grad_features; zeroed by the call), tau_ws n * K floats (with grad and without grad_tau); next: three
+// counter words. grad: 10 floats per Gaussian, grad_features: C per Gaussian, grad_q, grad_tau: n * K; any may be nullptr)
+hipError_t query_radiance_grad(const RenderArgs& A, const vr_ray* rays, const float* t, uint32_t t_stride, const float* q,
+                               uint32_t q_stride, uint32_t n, uint32_t K, const float* feat, uint32_t C, const float* weights,
+                               const float* weight_opacity, const float* tr, bool moving, double* s_rows, double* stage,
+                               double* fstage, float* tau_ws, float* grad, float* grad_features, float* grad_q, float* grad_tau,
+                               uint32_t* next, int refill, int cus, hipStream_t s);
 
 // kernels/vr_query_flight.hip (the sweep, the solvers and the albedo are the path kernels': kernels/vr_ff_bounce.h)
 // (ctl: query_flight_ctl_words(n) words; A.ff_*: the scratch rows, sized as the free-flight frames size theirs)

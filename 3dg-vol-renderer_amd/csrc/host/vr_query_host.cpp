@@ -1,7 +1,8 @@
 // Mixture queries (vr_query_*, kernels/vr_query.hip, kernels/vr_query_profile.hip, kernels/vr_query_features.hip,
-// kernels/vr_query_radiance.hip, kernels/vr_query_flight.hip): batched transmittance and its gradients with respect to
-// the Gaussians and to the rays, transmittance profiles and their gradient, ray events, sigma and its gradient,
-// per-Gaussian features at points and their gradient, the emission-absorption sum along rays, and free-flight distances.
+// kernels/vr_query_radiance.hip, kernels/vr_query_radiance_grad.hip, kernels/vr_query_flight.hip): batched transmittance and
+// its gradients with respect to the Gaussians and to the rays, transmittance profiles and their gradient, ray events, sigma
+// and its gradient, per-Gaussian features at points and their gradient, the emission-absorption sum along rays and its
+// gradient, and free-flight distances.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -38,7 +39,7 @@ vr_status query_begin(vr_ctx*& c, const char* what, size_t n, RenderArgs& A) {
     A.num_prims = c->num_prims;
     A.bvh_depth = sd.bvh_depth;
     A.gauss_order = sd.order.get();
-    return c->q_ctl.grow(48, "hipMalloc(query counters)");
+    return c->q_ctl.grow(64, "hipMalloc(query counters)");  // (16 words: vr_ctx.h)
 }
 int query_refill(const vr_ctx* c) { return std::clamp<int>(c->auto_nee_refill, 1, 64); }
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
@@ -415,10 +416,11 @@ vr_status vr_query_features_grad(vr_ctx* c, const float* xyz, size_t n, const fl
 
 // ---- radiance: sum_k q T sum_g m f along each ray; the profile's walk for T, then one walk for the sum ----
 namespace {
-vr_status radiance_check(size_t t_stride, size_t q_stride, bool has_q, size_t n, size_t N, uint32_t K, uint32_t C) {
-    VR_TRY(profile_check("vr_query_radiance", t_stride, n, K));
-    VR_TRY(features_check("vr_query_radiance", n, N, C));
-    if (has_q && q_stride != 0 && q_stride != K) return fail(VR_ERR_INVALID, "vr_query_radiance: q_stride must be 0 (one shared row) or K");
+vr_status radiance_check(size_t t_stride, size_t q_stride, bool has_q, size_t n, size_t N, uint32_t K, uint32_t C,
+                         const char* what = "vr_query_radiance") {
+    VR_TRY(profile_check(what, t_stride, n, K));
+    VR_TRY(features_check(what, n, N, C));
+    if (has_q && q_stride != 0 && q_stride != K) return fail(VR_ERR_INVALID, std::string(what) + ": q_stride must be 0 (one shared row) or K");
     return VR_OK;
 }
 }  // namespace
@@ -467,6 +469,89 @@ vr_status vr_query_radiance(vr_ctx* c, const vr_ray* rays, const float* t, size_
                          return vr_query_radiance_device(c, dev<vr_ray>(c->q_in, rays), c->q_w.get(), t_stride, dev<float>(c->q_w3, q),
                                                          q_stride, n, K, c->q_feat.get(), C, c->q_out.get(), dev<float>(c->q_out3, opacity),
                                                          dev<float>(c->q_out2, tr), dev<uint32_t>(c->q_out3, n_pairs, n), c->stream);
+                     });
+}
+
+// ---- radiance gradient: the profile's walk for T if the caller has none, one walk per ray, the profile gradient's walk ----
+vr_status vr_query_radiance_grad_device(vr_ctx* c, const vr_ray* d_rays, const float* d_t, size_t t_stride, const float* d_q,
+                                        size_t q_stride, size_t n, uint32_t K, const float* d_features, uint32_t C,
+                                        const float* d_weights, const float* d_weight_opacity, const float* d_tr, uint32_t flags,
+                                        float* d_grad, float* d_grad_features, float* d_grad_q, float* d_grad_tau, void* stream) {
+    const char* what = "vr_query_radiance_grad";
+    RenderArgs A;
+    VR_TRY(query_begin(c, what, n, A));
+    const size_t N = (size_t)std::max(A.num_prims, 0);
+    VR_TRY(radiance_check(t_stride, q_stride, d_q != nullptr, n, N, K, C, what));
+    VR_TRY(grad_flags(what, flags));
+    if (n == 0) {
+        if (d_grad && N) HIP_TRY(hipMemsetAsync(d_grad, 0, N * 10 * sizeof(float), (hipStream_t)stream), "hipMemset(radiance gradient)");
+        if (d_grad_features && N)
+            HIP_TRY(hipMemsetAsync(d_grad_features, 0, N * C * sizeof(float), (hipStream_t)stream), "hipMemset(radiance gradient)");
+        return VR_OK;
+    }
+    if (!d_rays || !d_t || !d_features) return fail(VR_ERR_INVALID, "vr_query_radiance_grad: NULL argument");
+    if (!d_grad && !d_grad_features && !d_grad_q && !d_grad_tau) return fail(VR_ERR_INVALID, "vr_query_radiance_grad: all four outputs are NULL");
+    VR_TRY(rays_aligned(what, d_rays));
+    if (N == 0) d_grad = d_grad_features = nullptr;  // an empty scene: they have no entries
+    if (!d_grad && !d_grad_features && !d_grad_q && !d_grad_tau) return VR_OK;
+    // the workspaces are the query's own: a frame or another query queued on another stream never sees them
+    const size_t nk = n * (size_t)K;
+    const bool rows = d_grad || d_grad_q || d_grad_tau;
+    if (rows) VR_TRY(c->q_radg_s.grow(nk, "hipMalloc(radiance gradient rows)"));
+    if (d_grad) VR_TRY(c->q_radg_stage.grow(N * 10, "hipMalloc(gradient staging)"));
+    if (d_grad_features) VR_TRY(c->q_radg_fstage.grow(N * C, "hipMalloc(feature gradient staging)"));
+    if (d_grad && !d_grad_tau) VR_TRY(c->q_radg_tau.grow(nk, "hipMalloc(radiance gradient weights)"));
+    uint32_t* ctl = (uint32_t*)c->q_ctl.get();
+    if (!d_tr) {
+        VR_TRY(c->q_radg_tr.grow(nk, "hipMalloc(radiance transmittances)"));
+        HIP_TRY(query_transmittance_profile(A, d_rays, d_t, (uint32_t)t_stride, (uint32_t)n, K, c->q_radg_tr.get(), nullptr, ctl + 12,
+                                            query_refill(c), c->cus, (hipStream_t)stream),
+                "query_profile_kernel");
+        d_tr = c->q_radg_tr.get();
+    }
+    HIP_TRY(query_radiance_grad(A, d_rays, d_t, (uint32_t)t_stride, d_q, (uint32_t)q_stride, (uint32_t)n, K, d_features, C, d_weights,
+                                d_weight_opacity, d_tr, !(flags & VR_GRAD_FROZEN_BOUNDS), rows ? c->q_radg_s.get() : nullptr,
+                                d_grad ? c->q_radg_stage.get() : nullptr, d_grad_features ? c->q_radg_fstage.get() : nullptr,
+                                d_grad && !d_grad_tau ? c->q_radg_tau.get() : nullptr, d_grad, d_grad_features, d_grad_q, d_grad_tau,
+                                ctl + 13, query_refill(c), c->cus, (hipStream_t)stream),
+            "query_radiance_grad_kernel");
+    return VR_OK;
+}
+
+vr_status vr_query_radiance_grad(vr_ctx* c, const vr_ray* rays, const float* t, size_t t_stride, const float* q, size_t q_stride,
+                                 size_t n, uint32_t K, const float* features, uint32_t C, const float* weights,
+                                 const float* weight_opacity, const float* tr, uint32_t flags, float* grad, float* grad_features,
+                                 float* grad_q, float* grad_tau) {
+    const char* what = "vr_query_radiance_grad";
+    RenderArgs A;
+    VR_TRY(query_begin(c, what, n, A));
+    const size_t N = (size_t)std::max(A.num_prims, 0);
+    VR_TRY(radiance_check(t_stride, q_stride, q != nullptr, n, N, K, C, what));
+    VR_TRY(grad_flags(what, flags));
+    if (n == 0) {
+        grad_is_zero(0, N * 10, grad);
+        grad_is_zero(0, N * C, grad_features);
+        return VR_OK;
+    }
+    if (!rays || !t || !features) return fail(VR_ERR_INVALID, "vr_query_radiance_grad: NULL argument");
+    if (!grad && !grad_features && !grad_q && !grad_tau) return fail(VR_ERR_INVALID, "vr_query_radiance_grad: all four outputs are NULL");
+    if (N == 0) grad = grad_features = nullptr;  // an empty scene: they have no entries,
+    if (!grad && !grad_features && !grad_q && !grad_tau) return VR_OK;  // and nothing else was asked for
+    const size_t nk = n * (size_t)K, nt = t_stride ? nk : (size_t)K, nq = q_stride ? nk : (size_t)K;
+    VR_TRY(room(c->q_feat, std::max<size_t>(N * C, 1), "query features"));  // (an empty scene has no rows; the pointer is not read)
+    // (the rows' gradient follows the Gaussians' in the first result's workspace)
+    return host_form(c, {{c->q_in, rays, n * kRayWords, "query rays"}, {c->q_w, t, nt, "profile samples"},
+                         {c->q_w3, q, nq, "quadrature weights"}, {c->q_feat, N ? features : nullptr, N * C, "query features"},
+                         {c->q_w2, weights, n * (size_t)C, "query weights"}, {c->q_w4, weight_opacity, n, "query weights"},
+                         {c->q_w5, tr, nk, "profile results"}},
+                     {{c->q_out, grad, N * 10, "query results"}, {c->q_out, grad_features, N * C, "query results", N * 10},
+                      {c->q_out2, grad_q, nk, "query results"}, {c->q_out3, grad_tau, nk, "query results"}},
+                     "query_radiance_grad_kernel", [&] {
+                         return vr_query_radiance_grad_device(c, dev<vr_ray>(c->q_in, rays), c->q_w.get(), t_stride, dev<float>(c->q_w3, q),
+                                                              q_stride, n, K, c->q_feat.get(), C, dev<float>(c->q_w2, weights),
+                                                              dev<float>(c->q_w4, weight_opacity), dev<float>(c->q_w5, tr), flags,
+                                                              dev<float>(c->q_out, grad), dev<float>(c->q_out, grad_features, N * 10),
+                                                              dev<float>(c->q_out2, grad_q), dev<float>(c->q_out3, grad_tau), c->stream);
                      });
 }
 

@@ -298,6 +298,15 @@ hipError_t query_features(const RenderArgs& A, const float* xyz, uint32_t n, con
     return hipGetLastError();
 }
 
+// The finish of a feature staging (C doubles per Gaussian, tree order) -> grad_features; the radiance gradient's unit calls
+// it too. A.num_prims > 0.
+hipError_t query_features_finish(const RenderArgs& A, const double* fstage, uint32_t C, float* grad_features, hipStream_t s) {
+    const uint32_t words = (uint32_t)((size_t)A.num_prims * C);
+    hipLaunchKernelGGL(dev::query_features_finish_kernel, dim3((words + 255u) / 256u), dim3(256), 0, s, A.gauss_order, fstage, words,
+                       C, grad_features);
+    return hipGetLastError();
+}
+
 // stage: 10 doubles per Gaussian, fstage: C doubles per Gaussian, both zeroed here, each needed only with its output;
 // grad: 10 floats per Gaussian, grad_features: C floats per Gaussian, grad_xyz: 3 floats per point, every entry of a
 // given output written. Any output may be nullptr; a scene without Gaussians has no rows to write.
@@ -327,12 +336,7 @@ hipError_t query_features_grad(const RenderArgs& A, const float* xyz, uint32_t n
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (stage && (e = query_grad_finish(A, stage, 10, grad, s)) != hipSuccess) return e;
-    if (fstage) {
-        const uint32_t words = (uint32_t)(N * C);
-        hipLaunchKernelGGL(dev::query_features_finish_kernel, dim3((words + 255u) / 256u), dim3(256), 0, s, A.gauss_order, fstage,
-                           words, C, grad_features);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
+    if (fstage && (e = query_features_finish(A, fstage, C, grad_features, s)) != hipSuccess) return e;
     return hipSuccess;
 }
 

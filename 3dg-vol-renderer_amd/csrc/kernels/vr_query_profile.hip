@@ -308,4 +308,16 @@ hipError_t query_transmittance_profile_grad(const RenderArgs& A, const vr_ray* r
     return query_grad_finish(A, acc, 10, grad, s);  // (vr_query.hip: GradOp's staging, so its finish)
 }
 
+// The same kernel adding into staging rows that the caller has zeroed (and may have added to) and finishes itself: the
+// radiance gradient's second pass (vr_query_radiance_grad.hip). n > 0, A.num_prims > 0.
+hipError_t query_transmittance_profile_grad_add(const RenderArgs& A, const vr_ray* rays, const float* t, uint32_t t_stride,
+                                                const float* weight, uint32_t n, uint32_t K, bool moving, double* acc,
+                                                uint32_t* next, int refill, int cus, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(next, 0, sizeof(uint32_t), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(dev::query_profile_grad_kernel, query_grid(cus), dim3(dev::kQBlock), 0, s, A, rays, t, t_stride, weight, n, K,
+                       moving ? 1u : 0u, acc, next, refill);
+    return hipGetLastError();
+}
+
 }  // namespace vr

@@ -247,6 +247,42 @@ public:
         return out;
     }
 
+    // The gradient of l = sum_i (sum_c weights[i][c] L[i][c] + weight_opacity[i] opacity[i]) for radiance's L and opacity, in
+    // one fused call (vr_query_radiance_grad): rays, t, K, features, C and q are radiance's; an empty `weights` means 1
+    // everywhere, an empty `weight_opacity` 0. The transmittances are computed again (the bits radiance returns). Row g of
+    // the result (10 floats per scene Gaussian, transmittance_gradient's layout and its moving_bounds) is d l / d (mean[3],
+    // cov[6], density), the emission part and the part through the transmittances together. *grad_features (if given)
+    // receives C floats per Gaussian, d l / d features; *grad_q and *grad_tau rays.size() * K floats each, d l / d q and
+    // d l / d tau (the optical depth up to the sample).
+    std::vector<float> radiance_gradient(const std::vector<Ray>& rays, const std::vector<float>& t, uint32_t K,
+                                         const std::vector<float>& features, uint32_t C, const std::vector<float>& weights = {},
+                                         const std::vector<float>& weight_opacity = {}, const std::vector<float>& q = {},
+                                         bool moving_bounds = true, std::vector<float>* grad_features = nullptr,
+                                         std::vector<float>* grad_q = nullptr, std::vector<float>* grad_tau = nullptr) const {
+        const size_t stride = profile_stride("radiance_gradient", rays.size(), t.size(), K);
+        const size_t q_stride = q.empty() ? 0 : profile_stride("radiance_gradient", rays.size(), q.size(), K);
+        feature_rows("radiance_gradient", features.size(), C);
+        if (!weights.empty() && weights.size() != rays.size() * C) throw std::runtime_error("radiance_gradient: C weights per ray");
+        if (!weight_opacity.empty() && weight_opacity.size() != rays.size())
+            throw std::runtime_error("radiance_gradient: one opacity weight per ray");
+        vr_ctx* ctx = ready();
+        const std::vector<vr_ray> r = pack(rays, nullptr, std::numeric_limits<float>::infinity());
+        std::vector<float> grad(10 * scene_.get_num_primitives() + 1, 0.0f), none(1, 0.0f);  // (+ 1, none: never a NULL pointer)
+        if (grad_features) grad_features->assign(features.size(), 0.0f);
+        if (grad_q) grad_q->assign(r.size() * K, 0.0f);
+        if (grad_tau) grad_tau->assign(r.size() * K, 0.0f);
+        vr_cpp::check(vr_query_radiance_grad(ctx, r.data(), t.data(), stride, q.empty() ? nullptr : q.data(), q_stride, r.size(), K,
+                                             features.empty() ? none.data() : features.data(), C,
+                                             weights.empty() ? nullptr : weights.data(),
+                                             weight_opacity.empty() ? nullptr : weight_opacity.data(), nullptr,
+                                             moving_bounds ? 0u : (uint32_t)VR_GRAD_FROZEN_BOUNDS, grad.data(),
+                                             grad_features && !features.empty() ? grad_features->data() : nullptr,
+                                             grad_q && !r.empty() ? grad_q->data() : nullptr,
+                                             grad_tau && !r.empty() ? grad_tau->data() : nullptr));
+        grad.pop_back();
+        return grad;
+    }
+
     // integrator.h:422-498 MultiScatterGaussians::get_free_flight_distance(ray, events, target_tau) per ray, the
     // events being the ray's own: the collision distance, or -1 where the ray leaves the mixture before the
     // target is reached. *albedo (if given) receives evaluate_albedo (gmm.h:128-143) over the critical segment's

@@ -799,6 +799,63 @@ class Device:
         got = (out,) + tuple(a for a in (opacity, tr, pairs) if a is not None)
         return got if len(got) > 1 else out
 
+    def radiance_gradient(self, scene, origins, directions, t, features, weights=None, weight_opacity=None, q=None, tr=None,
+                          unit=False, moving_bounds=True, gaussians=True, features_grad=True, grad_q=False, grad_tau=False):
+        """The gradient of l = sum_i (sum_c weights[i, c] L[i, c] + weight_opacity[i] opacity[i]) for radiance's L and opacity,
+        in one fused call (vr_query_radiance_grad). origins, directions, t, features and unit are radiance's; q holds the
+        quadrature weights (radiance's `weights`) in t's two shapes, or None (ones); weights (n, C) float32 is dl/dL (None:
+        ones), weight_opacity (n,) float32 dl/dopacity (None: zeros); tr (n, K) float32 is the Tr radiance returned (None:
+        it is computed again, with the same bits in every result). All arrays are of one kind, numpy or torch.
+        gaussians=True: the (N, 10) array d l / d (mean[3], cov6 [xx xy xz yy yz zz], density) of scene Gaussian g, in
+        query_transmittance_grad's layout and with its moving_bounds, the emission part and the part through the
+        transmittances together; features_grad=True: the (N, C) array d l / d features; grad_q=True: the (n, K) array
+        d l / d q (meaningful for q=None too); grad_tau=True: the (n, K) array d l / d tau, tau the optical depth up to each
+        sample. Returns the one asked for, or a tuple of those asked for in that order. Only what is asked for is computed:
+        grad_q and grad_tau alone run without a single atomic add. The sample points, their validity and the active set
+        are radiance's bit for bit and are not differentiated; an invalid ray contributes nothing and gets NaN rows in
+        grad_q and grad_tau, an invalid sample +0. The per-Gaussian sums are double atomics: reproducible to the rounding
+        of a double sum; grad_q and grad_tau are reproducible bit for bit."""
+        kind = _ArrayKind(origins, _query_ray_args(origins, directions, 0.0))
+        n = origins.shape[0]
+        K, stride = _query_profile_args(t, "t", n, kind.torch, shared_ok=True)
+        C = _query_feature_args(features, "features", None, kind.torch, "Gaussians")
+        if not (gaussians or features_grad or grad_q or grad_tau):
+            raise ValueError("radiance_gradient: ask for gaussians, features_grad, grad_q, grad_tau or any of them together")
+        q_stride = 0
+        if q is not None:
+            Kq, q_stride = _query_profile_args(q, "q", n, kind.torch, shared_ok=True)
+            if Kq != K:
+                raise ValueError(f"q has {Kq} columns for {K} samples")
+        if tr is not None and _query_profile_args(tr, "tr", n, kind.torch, shared_ok=False)[0] != K:
+            raise ValueError(f"tr has {tr.shape[1]} columns for {K} samples")
+        if weights is not None and _query_feature_args(weights, "weights", n, kind.torch, "rays") != C:
+            raise ValueError(f"weights has {weights.shape[1]} columns for {C} channels")
+        if weight_opacity is not None:
+            if _query_f32(weight_opacity, "weight_opacity", ()) != kind.torch:
+                raise ValueError("weight_opacity must be of the same kind as origins")
+            if weight_opacity.shape[0] != n:
+                raise ValueError(f"weight_opacity has {weight_opacity.shape[0]} entries for {n} rays")
+        _query_feature_sizes(n, features.shape[0], C)
+        N = scene.get_num_primitives()
+        if features.shape[0] != N:
+            raise ValueError(f"features has {features.shape[0]} rows for {N} Gaussians")
+        self.upload(scene)
+        rays = self._query_rays(kind, origins, directions, float("inf"), unit, also=(t, features, weights, weight_opacity, q, tr))
+        run = n > 0 and N > 0  # (otherwise the Gaussians' results are zero)
+        grad = kind.new((N, 10), zero=not run) if gaussians else None
+        gf = kind.new((N, C), zero=not run) if features_grad else None
+        gq = kind.new((n, K)) if grad_q else None
+        gt = kind.new((n, K)) if grad_tau else None
+        if n > 0 and (N > 0 or grad_q or grad_tau):
+            feats = kind.contiguous(features) if N > 0 else kind.new((1, C), zero=True)  # (no rows: never read, never NULL)
+            kind.call("vr_query_radiance_grad", self._h, kind.ptr(rays), kind.ptr(kind.contiguous(t)), stride,
+                      kind.ptr(kind.contiguous(q)), q_stride, n, K, kind.ptr(feats), C, kind.ptr(kind.contiguous(weights)),
+                      kind.ptr(kind.contiguous(weight_opacity)), kind.ptr(kind.contiguous(tr)),
+                      0 if moving_bounds else L.VR_GRAD_FROZEN_BOUNDS, kind.ptr(grad) if N > 0 else None,
+                      kind.ptr(gf) if N > 0 else None, kind.ptr(gq), kind.ptr(gt))
+        got = tuple(a for a in (grad, gf, gq, gt) if a is not None)
+        return got if len(got) > 1 else got[0]
+
     def query_events(self, scene, origins, directions):
         """GaussianMixtureModel::intersect_events (gmm.h:457-515) for n rays. Returns (offsets, t, gaussian,
         entering): ray i's events are the slice offsets[i]:offsets[i + 1] (offsets: (n + 1,) int64) of t

@@ -208,6 +208,10 @@ SIGNATURES = {
                                ctypes.c_uint32, FP, FP, FP, U32P]),
     "vr_query_radiance_device": (ST, [P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, P,
                                       ctypes.c_uint32, P, P, P, P, P]),
+    "vr_query_radiance_grad": (ST, [P, P, FP, ctypes.c_size_t, FP, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, FP,
+                                    ctypes.c_uint32, FP, FP, FP, ctypes.c_uint32, FP, FP, FP, FP]),
+    "vr_query_radiance_grad_device": (ST, [P, P, P, ctypes.c_size_t, P, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, P,
+                                           ctypes.c_uint32, P, P, P, ctypes.c_uint32, P, P, P, P, P]),
     "vr_query_events_count_device":(ST, [P, P, ctypes.c_size_t, P, ctypes.POINTER(ctypes.c_uint64)]),
     "vr_query_events_fill_device": (ST, [P, P, ctypes.c_size_t, P, P, P, ctypes.c_uint64, P]),
     "vr_query_events": (ST, [P, P, ctypes.c_size_t, U32P, FP, U32P, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),

@@ -68,6 +68,18 @@ feature query's rule that a point whose summed m is <= 0 is zeroed: it is the fo
 only. albedo, origins, directions, t and q get None; a fused backward and gradients with respect to the rays are not
 part of this.
 
+The same sum with a fused backward (Device.radiance_gradient):
+
+    L, opacity = radiance_fused(mean, cov6, density, albedo, feats, origins, directions, t, q)   # the same forward bits
+    loss.backward()                                     # mean.grad, cov6.grad, density.grad, feats.grad and q.grad
+
+radiance_fused and radiance_fused_resident take radiance's arguments. Their backward is one Device.radiance_gradient call
+with the saved (n, K) transmittances, asking only for what some input needs: a (ray, Gaussian) pair sums its samples on
+chip, and nothing of size n K C or n K 3 is formed. It is the gradient of the forward as defined (every active pair counts,
+whatever the sign of the densities), and it also gives q.grad. albedo, origins, directions and t get None.
+radiance and radiance_resident stay exactly as they are: existing tests pin their signatures and the sequence of Device
+calls their backward makes.
+
 The extinction field itself, at the caller's points (Device.query_sigma / Device.query_sigma_grad):
 
     sig = sigma(mean, cov6, density, albedo, points)                             # (n, 2) = (sigma_a, sigma_s)
@@ -369,4 +381,60 @@ def radiance_resident(mean, cov6, density, albedo, feats, origins, directions, t
     (ValueError otherwise), and forward uploads the scene with Device.upload_gaussians instead of copying it to the host.
     Same arguments, same gradients."""
     L, opacity, _ = _Radiance.apply(mean, cov6, density, albedo, feats, origins, directions, t, q, device, True)
+    return L, opacity
+
+
+class _RadianceFused(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mean, cov6, density, albedo, feats, origins, directions, t, q, device, resident):
+        if resident and feats.device != origins.device:
+            raise ValueError(f"feats is on {feats.device}, the rays on {origins.device}: a resident scene's "
+                             "features live on the rays' device")
+        dev, scene = _scene_of(mean, cov6, density, albedo, origins, "the rays", device, resident)
+        o, d = origins.detach().contiguous(), _unit_directions(directions.detach())
+        ts = t.detach().contiguous()
+        qs = None if q is None else q.detach().contiguous()
+        f = feats.detach().to(device=o.device, dtype=torch.float32).contiguous()
+        L, opacity, tr = dev.radiance(scene, o, d, ts, f, qs, unit=True, return_opacity=True, return_tr=True)
+        ctx.dev, ctx.scene, ctx.saved = dev, scene, (o, d, ts, qs, f, tr)
+        ctx.like, ctx.feats_like, ctx.q_like = (mean, cov6, density), feats, q
+        ctx.mark_non_differentiable(tr)
+        return L, opacity, tr
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_L, grad_opacity, _grad_tr):
+        need_g, need_f = any(ctx.needs_input_grad[:3]), ctx.needs_input_grad[4]
+        need_q = ctx.q_like is not None and ctx.needs_input_grad[8]
+        out, gf, gq = (None,) * 3, None, None
+        if need_g or need_f or need_q:
+            o, d, ts, qs, f, tr = ctx.saved
+            got = ctx.dev.radiance_gradient(ctx.scene, o, d, ts, f, grad_L.to(torch.float32).contiguous(),
+                                            grad_opacity.to(torch.float32).contiguous(), qs, tr, unit=True,
+                                            gaussians=need_g, features_grad=need_f, grad_q=need_q)
+            got = list(got) if isinstance(got, tuple) else [got]
+            if need_g:
+                out = _split_grad(got.pop(0), ctx.like, ctx.needs_input_grad[:3])
+            if need_f:
+                gf = got.pop(0).to(device=ctx.feats_like.device, dtype=ctx.feats_like.dtype)
+            if need_q:
+                gq = got.pop(0)
+                if ctx.q_like.dim() == 1:  # (one row shared by all rays: the sum over the rays)
+                    gq = gq.sum(0)
+                gq = gq.to(ctx.q_like.dtype)
+        return out + (None, gf, None, None, None, gq, None, None)
+
+
+def radiance_fused(mean, cov6, density, albedo, feats, origins, directions, t, q=None, device=0):
+    """radiance with a fused backward: the same arguments and the same (L, opacity) bits. Backward is one
+    Device.radiance_gradient call with the forward's transmittances; differentiable with respect to mean, cov6, density, feats
+    and q (a shared (K,) row gets the sum over the rays); albedo, origins, directions and t get None."""
+    L, opacity, _ = _RadianceFused.apply(mean, cov6, density, albedo, feats, origins, directions, t, q, device, False)
+    return L, opacity
+
+
+def radiance_fused_resident(mean, cov6, density, albedo, feats, origins, directions, t, q=None, device=0):
+    """radiance_fused for parameters that never leave the GPU: mean, cov6, density, albedo and feats must be on the rays'
+    device (ValueError otherwise), and forward uploads the scene with Device.upload_gaussians. Same arguments, same gradients."""
+    L, opacity, _ = _RadianceFused.apply(mean, cov6, density, albedo, feats, origins, directions, t, q, device, True)
     return L, opacity

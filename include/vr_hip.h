@@ -24,7 +24,8 @@ extern "C" {
 #endif
 
 #define VR_ABI_VERSION 11
-/* (still 11 with vr_query_features / vr_query_features_grad and vr_query_radiance: entry points were added, none changed) */
+/* (still 11 with vr_query_features / vr_query_features_grad, vr_query_radiance and vr_query_radiance_grad: entry points
+ * were added, none changed) */
 
 typedef enum vr_status {
     VR_OK = 0,
@@ -796,6 +797,49 @@ vr_status vr_query_radiance(vr_ctx* ctx, const vr_ray* rays, const float* t, siz
 vr_status vr_query_radiance_device(vr_ctx* ctx, const vr_ray* d_rays, const float* d_t, size_t t_stride, const float* d_q,
                                    size_t q_stride, size_t n, uint32_t K, const float* d_features, uint32_t C,
                                    float* d_out, float* d_opacity, float* d_tr, uint32_t* d_n_pairs, void* stream);
+
+/* The gradient of l = sum_i ( sum_c w_ic L_ic + u_i opacity_i ), L and opacity vr_query_radiance's out and opacity, with
+ * respect to the Gaussians, the feature rows, the quadrature weights and the optical depths, in one fused call: a
+ * (ray, Gaussian) pair sums its samples on chip and adds to the Gaussian's 10 + C sums once, and nothing of size n * K * C
+ * or n * K * 3 exists. weights[n * C] = w (NULL: ones), weight_opacity[n] = u (NULL: zeros). rays, t, t_stride, q,
+ * q_stride, n, K, features and C are vr_query_radiance's, and so are, bit for bit, the sample points x_ik, the validity of a
+ * sample and the active set A(x_ik) (every active pair counts; there is no "summed m <= 0" rule).
+ * T_ik is tr[K i + k], the tr the forward returned; tr == NULL: the profile's walk writes it into a workspace first, as the
+ * forward does, and every output has the same bits either way.
+ * Per active pair everything is double from the f32 record, point, row and weights: p = x_ik - mean, e = norm exp(-p.Mp / 2),
+ * m = rho e (vr_query_features_grad's m, not the forward's f32 mu_t). With phi_ig = u_i + sum_c w_ic f_gc and a_ik = q_ik T_ik
+ * (q == NULL: T_ik; an invalid sample: 0), and s_ik = sum_{g in A(x_ik)} m_g(x_ik) phi_ig:
+ *   grad_q[K i + k]          f32( T_ik s_ik ) = d l / d q_ik (meaningful with q == NULL too)
+ *   grad_tau[K i + k]        f32( -q_ik T_ik s_ik ) = d l / d tau_ik, tau the optical depth up to the sample
+ *   grad_features[C g + c]   sum_i w_ic sum_k a_ik m_g(x_ik)
+ *   grad[10 g + .]           d l / d (mean[3], cov[6], density) of SCENE Gaussian g, vr_query_transmittance_grad's layout:
+ *                            sum_i phi_ig sum_k a_ik d m_g(x_ik) / d theta_g (vr_query_features_grad's three formulas with
+ *                            c = a_ik phi_ig), plus exactly what vr_query_transmittance_profile_grad adds for the weights
+ *                            grad_tau as rounded to f32, honouring flags (VR_GRAD_FROZEN_BOUNDS or 0). Both parts are
+ *                            summed in one staging row per Gaussian and converted once: one rounding per output.
+ * Any output may be NULL (all four with n > 0: VR_ERR_INVALID); every entry of a given output is written. What is not
+ * asked for costs nothing: grad_q and / or grad_tau alone run one walk without a single atomic add and without the
+ * profile gradient's pass; grad_features alone runs without the ten adds per pair and without that pass.
+ * An invalid ray contributes nothing and gets NaN rows in grad_q and grad_tau; an invalid sample (t negative, NaN or
+ * infinite) contributes nothing and gets +0, and so does a sample in no ellipsoid, whatever its q. n == 0 is VR_OK: it
+ * zeroes grad and grad_features if given and launches nothing. A scene without Gaussians gives zeros. Argument errors are
+ * vr_query_radiance's (features NULL with n > 0 among them), plus unknown flag bits: VR_ERR_INVALID before anything is
+ * launched, the outputs untouched.
+ * Passes on `stream`: the profile's walk (tr == NULL only); one walk per ray (a lane owns its ray's row of s, plain loads
+ * and stores; per pair with an active sample 10 double atomic adds if grad is asked for and C if grad_features is); with
+ * grad, the profile gradient's walk with grad_tau as weights into the same staging; one conversion per staging.
+ * Workspaces, the query's own: s n * K doubles, tr and grad_tau n * K floats each when the caller gives none, staging
+ * (10 + C) doubles per Gaussian. grad_q and grad_tau are reproducible bit for bit, grad and grad_features to the rounding
+ * of a double sum. Not differentiable a second time; gradients with respect to origins, directions and t are not computed. */
+vr_status vr_query_radiance_grad(vr_ctx* ctx, const vr_ray* rays, const float* t, size_t t_stride, const float* q,
+                                 size_t q_stride, size_t n, uint32_t K, const float* features, uint32_t C,
+                                 const float* weights, const float* weight_opacity, const float* tr, uint32_t flags,
+                                 float* grad, float* grad_features, float* grad_q, float* grad_tau);
+vr_status vr_query_radiance_grad_device(vr_ctx* ctx, const vr_ray* d_rays, const float* d_t, size_t t_stride,
+                                        const float* d_q, size_t q_stride, size_t n, uint32_t K, const float* d_features,
+                                        uint32_t C, const float* d_weights, const float* d_weight_opacity,
+                                        const float* d_tr, uint32_t flags, float* d_grad, float* d_grad_features,
+                                        float* d_grad_q, float* d_grad_tau, void* stream);
 
 /* GaussianMixtureModel::intersect_events (gmm.h:457-515; tmax is not read): per ray the events of every
  * Gaussian it hits, an entry at t_enter (clamped to 0 for an origin inside) and an exit at t_exit, sorted by

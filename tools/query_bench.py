@@ -6,7 +6,7 @@ rays packed on the device), every query is warmed up, and the figure is the medi
 events on torch's current stream. Prints one JSON line and, with --out, writes it to a file.
 
     python tools/query_bench.py [--gaussians 1000000] [--rays 4194304] [--points 4194304] [--repeats 5] [--out F]
-                                [--flight-scene FILE] [--only all|mixture|flight|grad|raygrad|upload|sigmagrad|profile|features|radiance]
+                                [--flight-scene FILE] [--only all|mixture|flight|grad|raygrad|upload|sigmagrad|profile|features|radiance|radiance_grad]
 
 --only grad times the optical-depth gradient query (Device.query_transmittance_grad, unit weights, moving and frozen
 bounds) beside the tau query on the same rays, on --flight-scene and on the make_random scene (--gaussians 0 skips it).
@@ -31,6 +31,14 @@ weights) and C = 3 and 48 channels. One process, one warm-up of each side, then 
 medians, each side's spread (max - min), the peak device memory of one call of each side over what is resident before it,
 and the largest |fused - composition| over S = sum_k |q| T F_abs beside the tests' bound 2^-22 (the composition summed
 again in double for this; entries whose S is below 2^-100, where the f32 result underflows, are counted apart).
+--only radiance_grad times the fused backward of that query (Device.radiance_gradient with the forward's Tr: the Gaussians'
+and the rows' gradients in one call) against the composed backward it replaces (autograd.radiance's: the n K points, the
+weights q T gL, Device.features_gradient, Device.evaluate_features, Device.query_transmittance_profile_grad and the sum of the
+two (N, 10) results), on the radiance section's scene, rays, samples and channels and by its rules: one process, a warm-up of
+each side, the sides alternating --repeats times, medians and spreads (max - min), torch's peak allocation of one call of each
+side, and the library's own workspace sizes of the fused side from the shape. It also times the fused side's parts: the walk
+without atomics (grad_q and grad_tau alone), the walk with the rows' adds alone (grad_features), and the profile gradient
+query with grad_tau as weights, which is what the second pass runs.
 --only upload times getting a scene whose parameters live in torch tensors on the GPU onto the device, on --flight-scene
 and on make_random scenes of 100 000 and --gaussians Gaussians: (a) a copy to the host, Scene.from_gaussians and
 Device.upload with the host builder, (b) the same with device_bvh = 1, (c) Device.upload_gaussians. A host clock
@@ -79,7 +87,7 @@ def main():
     ap.add_argument("--seed", type=int, default=2025)
     ap.add_argument("--out", default=None)
     ap.add_argument("--flight-scene", default=os.path.join(ROOT, "tests", "golden", "scenes", "1000_random.txt"))
-    ap.add_argument("--only", choices=("all", "mixture", "flight", "grad", "raygrad", "upload", "sigmagrad", "profile", "features", "radiance"),
+    ap.add_argument("--only", choices=("all", "mixture", "flight", "grad", "raygrad", "upload", "sigmagrad", "profile", "features", "radiance", "radiance_grad"),
                     default="all")
     ap.add_argument("--profile-k", default="8,64", help="samples per ray of --only profile, comma-separated")
     ap.add_argument("--profile-forward-only", action="store_true")
@@ -120,6 +128,9 @@ def main():
     if args.only == "radiance":
         res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
         res.update(radiance(args, dev, o, d))
+    if args.only == "radiance_grad":
+        res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
+        res.update(radiance_grad(args, dev, o, d))
     if args.only == "profile":
         res["command"] = "python tools/query_bench.py " + " ".join(sys.argv[1:])
         res.update(profile(args, dev, o, d, timed))
@@ -282,6 +293,102 @@ def radiance(args, dev, o, d):
                       "the device; spread = max - min of a side's intervals; peak = torch's peak allocation during one call over "
                       "what was allocated before it (the library's own workspaces, n K floats of Tr for the fused side, are not "
                       "torch's and are not counted on either side)"}
+
+
+def radiance_grad(args, dev, o, d):
+    """The fused radiance backward against the composed one (autograd.radiance's), alternating in one process."""
+    import torch
+    scene = vr.Scene(vr.Scene.GAUSSIANS)
+    scene.add_random_gaussians(args.gaussians, seed=args.seed, variant=0)
+    info = scene.info()
+    lo, hi = np.array(list(info.bounds_min), np.float64), np.array(list(info.bounds_max), np.float64)
+    dist, rad = float(np.linalg.norm(0.5 * (lo + hi) - CAM_POS)), 0.5 * float(np.linalg.norm(hi - lo))
+    dev.upload(scene)
+    n, N, K = o.shape[0], scene.get_num_primitives(), 64
+    edges = np.linspace(max(dist - rad, 0.0), dist + rad, K + 1)
+    t = torch.tensor(np.tile((0.5 * (edges[1:] + edges[:-1])).astype(np.float32), (n, 1))).cuda()
+    q = torch.tensor(np.tile(np.diff(edges).astype(np.float32), (n, 1))).cuda()
+    dn = (d / torch.sqrt(d[:, 0] * d[:, 0] + (d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]))[:, None]).contiguous()
+
+    def interval(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        got = fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), got
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        return (torch.cuda.max_memory_allocated() - base) / 2.0 ** 20
+
+    out = []
+    for C in (3, 48):
+        rng = np.random.default_rng(7)
+        f = torch.tensor(rng.uniform(-1, 1, (N, C)).astype(np.float32)).cuda()
+        gL = torch.tensor(rng.uniform(-1, 1, (n, C)).astype(np.float32)).cuda()
+        gA = torch.tensor(rng.uniform(-1, 1, n).astype(np.float32)).cuda()
+        tr = dev.radiance(scene, o, dn, t, f, q, unit=True, return_tr=True)[1]
+
+        def fused():
+            return dev.radiance_gradient(scene, o, dn, t, f, gL, gA, q, tr, unit=True)
+
+        def composed():  # autograd._Radiance.backward, line for line
+            gL64, gA64 = gL.to(torch.float64), gA.to(torch.float64)
+            x = (o[:, None, :] + t[:, :, None] * dn[:, None, :]).reshape(-1, 3).contiguous()
+            valid = torch.isfinite(t) & (t >= 0) & torch.isfinite(tr)
+            qt = q.to(torch.float64) * tr.to(torch.float64)
+            qt = torch.where(valid, qt, torch.zeros_like(qt))
+            x = torch.where(valid.reshape(-1, 1), x, torch.full_like(x, float("nan")))
+            w = (qt[:, :, None] * gL64[:, None, :]).reshape(-1, C).to(torch.float32).contiguous()
+            u = (qt * gA64[:, None]).reshape(-1).to(torch.float32).contiguous()
+            g, gf = dev.features_gradient(scene, x, f, w, u)
+            F, mass = dev.evaluate_features(scene, x, f, return_mass=True)
+            s = (F.reshape(n, K, C).to(torch.float64) * gL64[:, None, :]).sum(2) + mass.reshape(n, K).to(torch.float64) * gA64[:, None]
+            wp = torch.where(valid, -qt * s, torch.zeros_like(s)).to(torch.float32).contiguous()
+            gp = dev.query_transmittance_profile_grad(scene, o, dn, t, wp)
+            return (g.to(torch.float64) + gp.to(torch.float64)).to(torch.float32), gf
+
+        def rows_only():
+            return dev.radiance_gradient(scene, o, dn, t, f, gL, gA, q, tr, unit=True, gaussians=False, features_grad=False, grad_q=True,
+                                         grad_tau=True)
+
+        def features_only():
+            return dev.radiance_gradient(scene, o, dn, t, f, gL, gA, q, tr, unit=True, gaussians=False)
+
+        for _ in range(max(1, args.warmup)):
+            a, b = fused(), composed()
+            gt = rows_only()[1]
+            features_only()
+            dev.query_transmittance_profile_grad(scene, o, dn, t, gt)
+        diff = [float((x.double() - y.double()).abs().max() / y.double().abs().max()) for x, y in zip(a, b)]
+        del a, b
+        fm, cm = [], []
+        for _ in range(args.repeats):
+            fm.append(interval(fused)[0])
+            cm.append(interval(composed)[0])
+        parts = {name: statistics.median(interval(fn)[0] for _ in range(args.repeats))
+                 for name, fn in (("walk_without_atomics_ms", rows_only), ("walk_with_the_rows_adds_ms", features_only),
+                                  ("profile_gradient_of_grad_tau_ms", lambda: dev.query_transmittance_profile_grad(scene, o, dn, t, gt)))}
+        f_ms, c_ms = statistics.median(fm), statistics.median(cm)
+        f_sp, c_sp = max(fm) - min(fm), max(cm) - min(cm)
+        out.append({"scene": f"make_random_{args.gaussians}", "gaussians": N, "rays": n, "K": K, "C": C, "fused_ms": f_ms,
+                    "composed_ms": c_ms, "composed_over_fused": c_ms / f_ms, "fused_spread_ms": f_sp, "composed_spread_ms": c_sp,
+                    "fused_faster_by_more_than_the_spreads": bool(c_ms - f_ms > max(f_sp, c_sp)), "fused_parts": parts,
+                    "fused_torch_peak_mib": peak(fused), "composed_torch_peak_mib": peak(composed),
+                    "fused_workspace_mib": {"s": n * K * 8 / 2.0 ** 20, "grad_tau": n * K * 4 / 2.0 ** 20, "tr": 0.0,
+                                            "staging": (10 + C) * N * 8 / 2.0 ** 20},
+                    "max_difference_over_max": {"grad": diff[0], "grad_features": diff[1]},
+                    "all_ms": {"fused": fm, "composed": cm}})
+    return {"radiance_grad": out, "library": os.path.basename(vr._lib.LIB_PATH),
+            "timing": "HIP-event intervals on torch's current stream, the two sides alternating after a warm-up of each, inputs and the "
+                      "forward's Tr on the device; spread = max - min of a side's intervals; torch peak = torch's peak allocation during "
+                      "one call over what was allocated before it; the fused side's workspaces are the library's own allocations, which "
+                      "torch does not see: their sizes are computed from the shape (vr_query_host.cpp), not measured"}
 
 
 def sigmagrad(args, dev, timed):

@@ -42,6 +42,10 @@
 // --query-radiance RAYS.bin K FEATURES.bin (the two files above) prints MixtureQuery::radiance of the file's rays at
 // --query-profile's K distances per ray with the quadrature weights q[i][k] = tmax_i / K in f32: one line `rq <ray index>
 // <n_pairs> <opacity and C channels as hex words>` per ray, then one line `rt <ray index> <K hex words of Tr>` per ray.
+// --query-radiance-grad RAYS.bin K FEATURES.bin (the same files, samples and q) prints MixtureQuery::radiance_gradient with all
+// weights 1 and opacity weights 0: one line `Rg <scene index> <10 hex words>` per Gaussian, one line `Rf <scene index> <C hex
+// words>` per Gaussian (the gradient with respect to its row), then per ray one line `Rq <ray index> <K hex words>` (d/d q)
+// and one line `Rt <ray index> <K hex words>` (d/d tau).
 // --upload-device (Gaussian scenes, one GPU): copies the loaded scene's rows to device memory and uploads them with
 // HipIntegrator::upload_device (vr_upload_gaussians_device: records, boxes and tree computed on the device), then
 // renders the scene the context holds.
@@ -261,6 +265,42 @@ static int run_query_radiance(const Scene& scene, const std::string& path, int K
     return 0;
 }
 
+// --query-radiance-grad: the fused gradient of the sum of --query-radiance's channels, over the same samples and weights.
+static int run_query_radiance_grad(const Scene& scene, const std::string& path, int K, const std::string& feat_path) {
+    if (K <= 0) throw std::runtime_error("--query-radiance-grad: K must be positive");
+    std::vector<Ray> rays;
+    std::vector<float> tmax;
+    std::vector<Eigen::Vector3f> pos;
+    read_query_file(path, rays, tmax, pos);
+    uint32_t C = 0;
+    const std::vector<float> feat = read_feature_file(feat_path, C);
+    std::vector<float> t(rays.size() * (size_t)K), q(t.size()), gf, gq, gt;
+    for (size_t i = 0; i < rays.size(); ++i)
+        for (int k = 0; k < K; ++k) {
+            t[i * (size_t)K + k] = tmax[i] * (float)(k + 1) / (float)K;
+            q[i * (size_t)K + k] = tmax[i] / (float)K;
+        }
+    const std::vector<float> g = MixtureQuery(scene).radiance_gradient(rays, t, (uint32_t)K, feat, C, {}, {}, q, true, &gf, &gq, &gt);
+    for (size_t i = 0; i < g.size() / 10; ++i) {
+        std::printf("Rg %zu", i);
+        for (int k = 0; k < 10; ++k) std::printf(" %08x", fbits(g[10 * i + k]));
+        std::printf("\n");
+    }
+    for (size_t i = 0; i < gf.size() / C; ++i) {
+        std::printf("Rf %zu", i);
+        for (uint32_t k = 0; k < C; ++k) std::printf(" %08x", fbits(gf[C * i + k]));
+        std::printf("\n");
+    }
+    for (size_t i = 0; i < rays.size(); ++i) {
+        std::printf("Rq %zu", i);
+        for (int k = 0; k < K; ++k) std::printf(" %08x", fbits(gq[i * (size_t)K + k]));
+        std::printf("\nRt %zu", i);
+        for (int k = 0; k < K; ++k) std::printf(" %08x", fbits(gt[i * (size_t)K + k]));
+        std::printf("\n");
+    }
+    return 0;
+}
+
 // --upload-device: the scene's rows as four device arrays, uploaded from there.
 static void upload_from_device_memory(vr_ctx* ctx, const Scene& scene) {
     if (scene.volume_type != Scene::VolumeType::GAUSSIANS) throw std::runtime_error("--upload-device needs a Gaussian scene");
@@ -316,7 +356,7 @@ int main(int argc, char** argv) try {
     uint64_t seed = 0;
     float lr = 1e-2f;
     std::string ref_path, sfd_out, gif_path, query_path, query_grad_path, query_ray_grad_path, query_sigma_grad_path, query_profile_path,
-        query_features_path, features_path, query_radiance_path;
+        query_features_path, features_path, query_radiance_path, query_radiance_grad_path;
     int radiance_k = 0;
     int profile_k = 0;
     int frames = 120;
@@ -350,6 +390,7 @@ int main(int argc, char** argv) try {
         else if (a == "--query-sigma-grad") query_sigma_grad_path = next();
         else if (a == "--query-features") { query_features_path = next(); features_path = next(); }
         else if (a == "--query-radiance") { query_radiance_path = next(); radiance_k = std::atoi(next()); features_path = next(); }
+        else if (a == "--query-radiance-grad") { query_radiance_grad_path = next(); radiance_k = std::atoi(next()); features_path = next(); }
         else if (a == "--query-profile") { query_profile_path = next(); profile_k = std::atoi(next()); }
         else if (a == "--gif") gif_path = next();
         else if (a == "--frames") frames = std::atoi(next());
@@ -412,6 +453,7 @@ int main(int argc, char** argv) try {
     if (!query_sigma_grad_path.empty()) return run_query_sigma_grad(scene, query_sigma_grad_path);
     if (!query_features_path.empty()) return run_query_features(scene, query_features_path, features_path);
     if (!query_radiance_path.empty()) return run_query_radiance(scene, query_radiance_path, radiance_k, features_path);
+    if (!query_radiance_grad_path.empty()) return run_query_radiance_grad(scene, query_radiance_grad_path, radiance_k, features_path);
     if (!query_profile_path.empty()) return run_query_profile(scene, query_profile_path, profile_k);
 
     if (!gif_path.empty()) {  // main.cpp:81-114
